@@ -1,6 +1,16 @@
 """Headline benchmark: SMER train tokens/s (+ infill tokens/s) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-infill] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--no-infill] [--no-cpu] ...
+
+A plain run sets up, runs W warm-up and K timed steps of the headline
+workload below and prints the result line; --dump-outputs DIR also writes
+what the last timed step computed (see dump_outputs).  Every other leg (the
+per-launch GEMM roofline steps, C4 fp8 / bf16, the infill blocks, the fp32
+decode lines, the CPU baseline, the data-pipeline rate and, under DP, the
+strong-scaling and bf16-all-reduce steps) runs only with --full, where the
+--no-* switches drop single legs; the result line then fills their blocks,
+which a plain run leaves null.
 
 Workload (BASELINE.json configs[1] / SURVEY.md §8d C2): 6-layer encoder +
 6-layer decoder, d_model 512, 8 heads, FF 2048, V 309, per GPU B=32 source
@@ -102,7 +112,30 @@ def params_in_sync(model, dev, world):
     return all(torch.equal(allh[0], x) for x in allh[1:])
 
 
-def bench_train(args, dev, rank, world, precision="bf16", grad_wire=None):
+DUMP_SAMPLE = 1 << 22  # elements kept of each flat buffer (16 MB as float32)
+
+
+def dump_outputs(path, model, loss):
+    """--dump-outputs: what a caller of the timed step holds after the last
+    timed step, as float32 <name>.npy files under `path`: `loss` (the step's
+    return value), and `params` / `grads`, the model's flat fp32 master
+    parameters after that step's Adam update and the flat gradient it was
+    computed from.  The C2 buffers are 44 M elements each, so a fixed seeded
+    sample of DUMP_SAMPLE positions (sorted, the same for both) is written;
+    a buffer no larger than that is written whole."""
+    os.makedirs(path, exist_ok=True)
+    flat, grad = model.flat_parameters().detach(), model.flat_grad().detach()
+    n = flat.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(20240607).integers(0, n, DUMP_SAMPLE))
+        idx = torch.from_numpy(idx).to(flat.device)
+        flat, grad = flat[idx], grad[idx]
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    np.save(os.path.join(path, "params.npy"), flat.float().cpu().numpy())
+    np.save(os.path.join(path, "grads.npy"), grad.float().cpu().numpy())
+
+
+def bench_train(args, dev, rank, world, precision="bf16", grad_wire=None, dump=None):
     from smer_music_generation_amd import ops
     from smer_music_generation_amd.synth import synth_training_batch
     from smer_music_generation_amd.train import Trainer
@@ -114,6 +147,8 @@ def bench_train(args, dev, rank, world, precision="bf16", grad_wire=None):
     b = synth_training_batch(1000 + rank, v, args.batch, args.seq, args.tgt)
     bt = {k: torch.from_numpy(np.asarray(x)).to(dev) for k, x in b.items()}
     dt, loss = timed_steps(lambda: tr.step(bt), args.steps, args.warmup, dev, world)
+    if dump and rank == 0:
+        dump_outputs(dump, m, loss)
     # The per-launch GEMM timing (HIP events around every smer_gemm call)
     # runs over a second, separate set of K steps so that the event records
     # do not slow the timed steps above.  Those steps run the weight
@@ -441,6 +476,14 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline train step (GEMM roofline steps, "
+                         "C4, infill, C5, fp32 infill, CPU baseline, data pipeline, the DP "
+                         "comparison steps); the --no-* switches below drop single legs of it")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's loss and a fixed "
+                         "sample of the updated parameters and of the gradients as float32 "
+                         "DIR/<name>.npy (rank 0)")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--seq", type=int, default=1024)
     ap.add_argument("--tgt", type=int, default=256)
@@ -571,6 +614,8 @@ def data_feed(per_gpu_tokens_per_s, seconds=3.0):
 
 def main():
     args = parse_args()
+    if not args.full:  # a plain run: the headline steps only
+        args.roofline = args.c4 = args.infill = args.c5 = args.fp32_infill = args.cpu = False
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
 
@@ -616,11 +661,11 @@ def main():
         head.batch = per_rank_batch(args.global_batch, world)
     else:
         head = args
-    tr = bench_train(head, dev, rank, world, grad_wire=wire)
+    tr = bench_train(head, dev, rank, world, grad_wire=wire, dump=args.dump_outputs)
     # DP, weak headline: the strong-scaling step beside it (global batch
     # --batch split over the ranks), SURVEY §8e "report both"
     tr_strong = None
-    if world > 1 and not strong:
+    if args.full and world > 1 and not strong:
         import copy
         a = copy.copy(args)
         a.roofline = False
@@ -629,7 +674,7 @@ def main():
     # DP only: the same step with the opt-in bf16 gradient all-reduce
     # (half the xGMI bytes), reported beside the fp32 (parity) headline
     tr_alt = None
-    if world > 1 and wire is None:
+    if args.full and world > 1 and wire is None:
         import copy
         a = copy.copy(head)
         a.roofline = False

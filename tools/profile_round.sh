@@ -15,7 +15,7 @@ mkdir -p $OUT
 # as in bench.py's event-timed steps (the product path overlaps them)
 export SMER_WGRAD_OVERLAP=0
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
-  python3 $R/bench.py --steps 5 --warmup 2 --no-infill --no-cpu --no-c4 > $OUT/trace.log 2>&1
+  python3 $R/bench.py --full --steps 5 --warmup 2 --no-infill --no-cpu --no-c4 > $OUT/trace.log 2>&1
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- \
   python3 $R/bench.py --steps 2 --warmup 1 --no-infill --no-cpu --no-roofline --no-c4 > $OUT/fetch.log 2>&1
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o run -- \

@@ -29,7 +29,7 @@ def run(*args):
 train = run(os.path.join(ROOT, "tools", "prof_summary.py"),
             os.path.join(src, "trace", "run_kernel_stats.csv"), steps, "30")
 with open(os.path.join(dst, tag + "_train_kernel_stats.txt"), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 "
+    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 2 "
             "--no-infill --no-cpu --no-c4  with SMER_WGRAD_OVERLAP=0, i.e. weight gradients on the "
             "main stream so each kernel's duration is its own (%s steps traced: 2 warm-up + 5 timed + 5 "
             "event-timed; per-step = total/%s)\n" % (steps, steps) + train)
