@@ -37,6 +37,9 @@
  *                        grammar loop on device: float64 softmax, sort, cdf
  *                        search and redraws on the numpy MT19937 stream
  *                        (generation.py:33-95, 528-687)
+ *   smer_grammar_sample_step_tp  the same with a temperature and a nucleus
+ *                        threshold per request, read from device memory
+ *                        (generation.py:11-30, 41-95: sampling(p, t))
  *   smer_layernorm_*     residual LayerNorm, eps 1e-5 (transformer.py:392,395,
  *                        462,466,469; final norms 274-275, 329-330)
  *   smer_embed_*         embedding gather x sqrt(d) + sinusoidal PE + dropout
@@ -336,6 +339,27 @@ int smer_grammar_sample_step(int R, int V, const float* logits, long ldl, int32_
                              int trash_pos, int max_span, const int32_t* src_len, int64_t* ids,
                              int32_t* meta, int32_t* out_tok, int cap, uint32_t* mt, int32_t* ctl,
                              int32_t* ring, int ring_n, smer_stream_t stream);
+/* smer_grammar_sample_step with the temperature t and the nucleus threshold
+ * p of the reference's sampling() (generation.py:11-30, 41-95), one pair per
+ * request: tp double [R, 2] in device memory, tp[r] = {t, p}, p < 0 meaning
+ * None.  The kernel reads tp on every step, so a captured step serves any
+ * values.  e = exp(where(keep, f64(logit), -100) / t) (mask first, then an
+ * IEEE float64 division), probs = e / np.sum(e).  p < 0: as above.  p >= 0
+ * (`nucleus`): q = probs / (sequential sum + 1e-5), sort descending (ties:
+ * descending index), c = sequential cumsum; the candidates are the sort
+ * positions 0 .. first(c > p) (all V when none exceeds p; p = 0 keeps the
+ * top token and still consumes one uniform); cp = q / sequential sum over the
+ * candidates, cdf = sequential cumsum(cp) / cdf[-1], id = first cdf > u.
+ * Redraws draw again from the same cdf.  state[r][8] bit 1 as above (NaN from
+ * an overflowing exp at a small t included).  The caller validates t finite
+ * and > 0, p negative or finite.  {1.0, -1.0} gives smer_grammar_sample_step's
+ * bits (x / 1.0 is exact). */
+int smer_grammar_sample_step_tp(int R, int V, const float* logits, long ldl, int32_t* state, int nst,
+                                const int8_t* targets, int max_masks, const uint8_t* keep,
+                                const uint8_t* reject, const uint8_t* cls, int eos, int m0,
+                                int trash_pos, int max_span, const int32_t* src_len, int64_t* ids,
+                                int32_t* meta, int32_t* out_tok, int cap, uint32_t* mt, int32_t* ctl,
+                                int32_t* ring, int ring_n, const double* tp, smer_stream_t stream);
 
 int smer_layernorm_fwd(int dtype, int M, int N, const void* x, long ldx,
                        const float* gamma, const float* beta, float eps,

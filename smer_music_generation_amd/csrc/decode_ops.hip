@@ -547,18 +547,31 @@ __device__ __forceinline__ uint32_t f32_ord(float f) {
 #endif
 #define SSTAMP(k) do { if (SMER_SAMPLE_STAMPS && lane == 0) mt[640 + (k)] = (uint32_t)__builtin_amdgcn_s_memtime(); } while (0)
 
-template <bool RING>
+// TP: the request's temperature and nucleus threshold come from tp[r] (double
+// [R, 2]: t, p; p < 0 = None), read from device memory on every step, so a
+// captured step serves any values.  e = exp(masked / t) (mask first, then a
+// true float64 division, generation.py:28-30 of the reference); with p >= 0
+// the reference's `nucleus` (generation.py:11-25) replaces weighted_sampling:
+//   q = probs / (T + 1e-5), sorted descending, c = cumsum(q_sorted),
+//   candidates = sort positions 0 .. first(c > p) (all when none exceeds p),
+//   cp = q / sum(q[candidates]), cdf = cumsum(cp) / cdf[-1], one uniform.
+// sum(q[candidates]) is c at the last candidate: builtin sum() from 0 and
+// np.cumsum add the same numbers in the same order.  !TP is t = 1, p = None
+// with the division folded away (x / 1.0 is exact: the same bits).
+template <bool RING, bool TP>
 __global__ __launch_bounds__(64) void grammar_sample_kernel(
     int R, int V, const float* __restrict__ logits, long ldl, int32_t* __restrict__ state, int nst,
     const int8_t* __restrict__ targets, int max_masks, const uint8_t* __restrict__ keep,
     const uint8_t* __restrict__ reject, const uint8_t* __restrict__ cls, int eos, int m0, int trash_pos,
     int max_span, const int32_t* __restrict__ src_len, int64_t* __restrict__ ids,
     int32_t* __restrict__ meta, int M, int32_t* __restrict__ out_tok, int cap,
-    int32_t* __restrict__ alive, int32_t* __restrict__ ring, int ring_n, uint32_t* __restrict__ mt) {
+    int32_t* __restrict__ alive, int32_t* __restrict__ ring, int ring_n, uint32_t* __restrict__ mt,
+    const double* __restrict__ tp) {
   // one wave; element i of a row lives in lane i / 8, slot i % 8
   __shared__ uint32_t key[624];
   __shared__ double pe[SMX];   // e, then p by vocabulary index
   __shared__ double sp[SMX];   // p in sort order, then the normalised cdf
+  __shared__ double cq[TP ? SMX : 1];  // nucleus: c, the cumulative sum of the sorted q
   __shared__ uint64_t kA[SMX];  // fast path: the compacted keys of set A
   __shared__ double bc[2];
   __shared__ int pwl[17];
@@ -600,8 +613,9 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
   // a request's state row, mask targets and logits (indices clamped, not
   // guarded: a guarded load waits right behind itself); request 0's with the
   // batch above, request r + 1's under request r's work
-  auto fetch = [&](int r, int& sv, int& tgv, float (&lg)[8]) {
+  auto fetch = [&](int r, int& sv, int& tgv, float (&lg)[8], double& tpv) {
     const int rr = min(r, R - 1);
+    if constexpr (TP) tpv = tp[2 * (long)rr + (lane & 1)];  // even lanes t, odd lanes p
     sv = state[(long)rr * nst + min(lane, nst - 1)];
     tgv = (int)targets[(long)rr * max_masks + min(lane, max_masks - 1)];
     const float* lr = logits + (long)(2 * rr + 1) * ldl;
@@ -610,7 +624,8 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
   };
   int sv_n, tgv_n;
   float lg_n[8];
-  fetch(0, sv_n, tgv_n, lg_n);
+  double tp_n = 0.;
+  fetch(0, sv_n, tgv_n, lg_n, tp_n);
   int pos = (int)mt[624];
   __syncthreads();
   SSTAMP(1);
@@ -621,8 +636,11 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
     float lg8[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) lg8[j] = lg_n[j];
-    fetch(r + 1, sv_n, tgv_n, lg_n);
+    const double tpv = tp_n;
+    fetch(r + 1, sv_n, tgv_n, lg_n, tp_n);
     if (__shfl(sv, ST_DONE, 64)) continue;  // wave-uniform
+    const double temp = TP ? __shfl(tpv, 0, 64) : 1.0, pnuc = TP ? __shfl(tpv, 1, 64) : -1.0;
+    const bool nuc = TP && pnuc >= 0.0;  // wave-uniform
     const int flags = __shfl(sv, ST_FLAGS, 64), len = __shfl(sv, ST_LEN, 64),
               midx = __shfl(sv, ST_MIDX, 64), nmask = __shfl(sv, ST_NMASK, 64),
               nowhole = __shfl(sv, ST_NOWHOLE, 64), cnt = __shfl(sv, ST_COUNT, 64),
@@ -631,17 +649,37 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
     const int code = grammar_state(flags, len, tgt, nowhole);
     const uint8_t* kp = tk + code * V;
     const uint8_t* rj = tr + code * V;
-    // e = exp(where(keep, float64(logit), -100.0)); sort keys: the masked
-    // float32 logit's order image (the probabilities' order: exp and the two
-    // normalisations are monotone and keep distinct float32 inputs distinct)
-    // above the index (ties: larger index first)
+    // e = exp(where(keep, float64(logit), -100.0) / t); sort keys: the masked
+    // float32 logit's order image (the probabilities' order: t > 0, and the
+    // division, exp and the two normalisations are monotone and keep distinct
+    // float32 inputs distinct) above the index (ties: larger index first)
     uint64_t kv[8];
+    if constexpr (!TP) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int i = lane * 8 + j;
-      const float x = (i < V && kp[i]) ? lg8[j] : -100.f;
-      kv[j] = i < V ? ((uint64_t)f32_ord(x) << 32) | (uint32_t)i : 0ull;
-      pe[i] = i < V ? exp((double)x) : 0.;
+      for (int j = 0; j < 8; ++j) {
+        const int i = lane * 8 + j;
+        const float x = (i < V && kp[i]) ? lg8[j] : -100.f;
+        kv[j] = i < V ? ((uint64_t)f32_ord(x) << 32) | (uint32_t)i : 0ull;
+        pe[i] = i < V ? exp((double)x) : 0.;
+      }
+    } else {
+      double xs[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int i = lane * 8 + j;
+        const float x = (i < V && kp[i]) ? lg8[j] : -100.f;
+        kv[j] = i < V ? ((uint64_t)f32_ord(x) << 32) | (uint32_t)i : 0ull;
+        xs[j] = (double)x;
+      }
+      if (temp != 1.0) {  // wave-uniform; x / 1.0 = x, so t = 1 skips the divisions
+#pragma unroll
+        for (int j = 0; j < 8; ++j) xs[j] = xs[j] / temp;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int i = lane * 8 + j;
+        pe[i] = i < V ? exp(xs[j]) : 0.;
+      }
     }
     __syncthreads();
     SSTAMP(2);
@@ -661,7 +699,7 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
     if (lane == 0) bc[1] = seq_sum(pe, V);
     __syncthreads();
     SSTAMP(4);
-    const double T = bc[1];
+    const double T = nuc ? bc[1] + 1e-5 : bc[1];  // nucleus: probs /= (sum(probs) + 1e-5)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int i = lane * 8 + j;
@@ -676,10 +714,45 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
     // 1.0 exactly, every draw u < 1 lands in A, and B is never needed.  Any
     // kept logit below -100, none >= -60, no A, or a pB check that fails
     // takes the full 512-key path (numpy's arithmetic either way).
+    // With a temperature the masked elements sit at -100 / t: "some kept
+    // logit >= -60" becomes (x + 100) / t >= 40, i.e. x >= -100 + 40 t (pB <=
+    // e^-40 of the largest p, below 2^-54; only a filter for rows whose pB
+    // check would fail: that check runs on the scaled p themselves).
+    // Nucleus: the candidates are a prefix of the sort order and c a
+    // sequential sum from its start, so when c at A's last position exceeds
+    // p the threshold crossing lies inside A, neither B nor the pB check
+    // matters, and A's sort serves; otherwise the full path.
     double cd[8];
     int sidx[8];
     double total;
     bool fast;
+    // nucleus, from q in sort order (sp) and c (cq), sort position s = lane *
+    // El + e over N positions: the candidates' cdf into cd (-1 past them)
+    auto nucleus_cdf = [&](int El, int N) {
+      int first = N;
+#pragma unroll
+      for (int e = 7; e >= 0; --e) {
+        const int s = lane * El + e;
+        if (e < El && s < N && cq[TP ? s : 0] > pnuc) first = s;
+      }
+      const uint64_t m = __ballot(first < N);  // s grows with the lane: the lowest lane's is the first
+      const int K = m ? __shfl(first, __builtin_ctzll(m), 64) + 1 : N;
+      const double den = cq[TP ? K - 1 : 0];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int s = lane * El + e;
+        if (e < El && s < K) sp[s] = sp[s] / den;
+      }
+      __syncthreads();
+      if (lane == 0) bc[0] = seq_cumsum(sp, sp, K);
+      __syncthreads();
+      total = bc[0];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int s = lane * El + e;
+        cd[e] = (e < El && s < K) ? sp[s] / total : -1.0;
+      }
+    };
     {
       uint32_t am = 0u;
       bool c_any = false, hi = false;
@@ -689,9 +762,9 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
         const float x = (i < V && kp[i]) ? lg8[j] : -100.f;
         if (i < V && x > -100.f) am |= 1u << j;
         if (i < V && x < -100.f) c_any = true;
-        if (i < V && x >= -60.f) hi = true;
+        if (i < V && (TP ? (double)x >= -100.0 + 40.0 * temp : x >= -60.f)) hi = true;
       }
-      fast = !__any(c_any) && __any(hi) && __any(am != 0u);
+      fast = !__any(c_any) && (nuc || __any(hi)) && __any(am != 0u);
       if (fast) {
         // compact A's keys into LDS (prefix over lanes), pad to the network size
         int incl = __popc(am);
@@ -727,11 +800,14 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
           pB = pe[bl * 8 + bj];
         }
         __syncthreads();
-        if (lane == 0) bc[0] = seq_cumsum(sp, sp, NA);
+        if (lane == 0) bc[0] = seq_cumsum(sp, nuc ? cq : sp, NA);
         __syncthreads();
         SSTAMP(7);
         total = bc[0];
-        if (pB * 18014398509481984.0 > total) {  // 2^54: the B terms would not vanish
+        if (nuc) {
+          if (total > pnuc) nucleus_cdf(E, NA);
+          else fast = false;  // the crossing is not inside A (or c is NaN)
+        } else if (pB * 18014398509481984.0 > total) {  // 2^54: the B terms would not vanish
           fast = false;
         } else {
 #pragma unroll
@@ -756,14 +832,18 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
       }
       __syncthreads();
       SSTAMP(6);
-      if (lane == 0) bc[0] = seq_cumsum(sp, sp, V);
+      if (lane == 0) bc[0] = seq_cumsum(sp, nuc ? cq : sp, V);
       __syncthreads();
       SSTAMP(7);
       total = bc[0];
+      if (nuc) {
+        nucleus_cdf(8, V);
+      } else {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int s = lane * 8 + j;
-        cd[j] = s < V ? sp[s] / total : 2.0;
+        for (int j = 0; j < 8; ++j) {
+          const int s = lane * 8 + j;
+          cd[j] = s < V ? sp[s] / total : 2.0;
+        }
       }
     }
     const bool bad = !(fabs(total - 1.0) <= 1e-9);  // the host path hands such rows to np.random.choice
@@ -814,34 +894,68 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
   }
 }
 
+namespace {
+int launch_grammar_sample(int R, int V, const float* logits, long ldl, int32_t* state, int nst,
+                          const int8_t* targets, int max_masks, const uint8_t* keep, const uint8_t* reject,
+                          const uint8_t* cls, int eos, int m0, int trash_pos, int max_span,
+                          const int32_t* src_len, int64_t* ids, int32_t* meta, int32_t* out_tok, int cap,
+                          uint32_t* mt, int32_t* ctl, int32_t* ring, int ring_n, const double* tp,
+                          smer_stream_t stream) {
+  SMER_REQUIRE(R > 0 && V > 0 && V <= SMX && nst >= 9 && max_masks > 0 && cap > 0,
+               "smer_grammar_sample_step[_tp]: sizes (V <= 512)");
+  SMER_REQUIRE(ldl >= V, "smer_grammar_sample_step[_tp]: logits row stride");
+  SMER_REQUIRE(logits && state && targets && keep && reject && cls && src_len && ids && meta && out_tok && mt && ctl,
+               "smer_grammar_sample_step[_tp]: null pointer");
+  SMER_REQUIRE(eos >= 0 && eos < V && m0 >= 0 && m0 < V && trash_pos > 0 && max_span > 1,
+               "smer_grammar_sample_step[_tp]: token ids");
+  hipStream_t s = (hipStream_t)stream;
+  void* dring = nullptr;
+  if (ring) {
+    if (hipHostGetDevicePointer(&dring, ring, 0) != hipSuccess || dring == nullptr) {
+      (void)hipGetLastError();
+      dring = ring;
+    }
+  }
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, s, R, V, logits, ldl, state, nst, targets, max_masks, keep,
+                       reject, cls, eos, m0, trash_pos, max_span, src_len, ids, meta, 2 * R, out_tok, cap, ctl,
+                       (int32_t*)dring, ring ? ring_n : 0, mt, tp);
+  };
+  if (ring) {
+    if (tp) go(grammar_sample_kernel<true, true>);
+    else go(grammar_sample_kernel<true, false>);
+  } else {
+    if (tp) go(grammar_sample_kernel<false, true>);
+    else go(grammar_sample_kernel<false, false>);
+  }
+  SMER_CHECK_LAUNCH("smer_grammar_sample_step");
+  return SMER_OK;
+}
+}  // namespace
+
 extern "C" int smer_grammar_sample_step(int R, int V, const float* logits, long ldl, int32_t* state,
                                         int nst, const int8_t* targets, int max_masks, const uint8_t* keep,
                                         const uint8_t* reject, const uint8_t* cls, int eos, int m0,
                                         int trash_pos, int max_span, const int32_t* src_len, int64_t* ids,
                                         int32_t* meta, int32_t* out_tok, int cap, uint32_t* mt,
                                         int32_t* ctl, int32_t* ring, int ring_n, smer_stream_t stream) {
-  SMER_REQUIRE(R > 0 && V > 0 && V <= SMX && nst >= 9 && max_masks > 0 && cap > 0,
-               "smer_grammar_sample_step: sizes (V <= 512)");
-  SMER_REQUIRE(ldl >= V, "smer_grammar_sample_step: logits row stride");
-  SMER_REQUIRE(logits && state && targets && keep && reject && cls && src_len && ids && meta && out_tok && mt && ctl,
-               "smer_grammar_sample_step: null pointer");
-  SMER_REQUIRE(eos >= 0 && eos < V && m0 >= 0 && m0 < V && trash_pos > 0 && max_span > 1,
-               "smer_grammar_sample_step: token ids");
-  hipStream_t s = (hipStream_t)stream;
-  if (ring) {
-    void* dring = nullptr;
-    if (hipHostGetDevicePointer(&dring, ring, 0) != hipSuccess || dring == nullptr) {
-      (void)hipGetLastError();
-      dring = ring;
-    }
-    hipLaunchKernelGGL(grammar_sample_kernel<true>, dim3(1), dim3(64), 0, s, R, V, logits, ldl, state, nst,
-                       targets, max_masks, keep, reject, cls, eos, m0, trash_pos, max_span, src_len, ids, meta,
-                       2 * R, out_tok, cap, ctl, (int32_t*)dring, ring_n, mt);
-  } else {
-    hipLaunchKernelGGL(grammar_sample_kernel<false>, dim3(1), dim3(64), 0, s, R, V, logits, ldl, state, nst,
-                       targets, max_masks, keep, reject, cls, eos, m0, trash_pos, max_span, src_len, ids, meta,
-                       2 * R, out_tok, cap, ctl, nullptr, 0, mt);
-  }
-  SMER_CHECK_LAUNCH("smer_grammar_sample_step");
-  return SMER_OK;
+  return launch_grammar_sample(R, V, logits, ldl, state, nst, targets, max_masks, keep,
+                               reject, cls, eos, m0, trash_pos, max_span, src_len, ids, meta, out_tok, cap, mt,
+                               ctl, ring, ring_n, nullptr, stream);
+}
+
+// The same step with a temperature and a nucleus threshold per request: tp
+// double [R, 2] on the device (t, p; p < 0 = None), read on every step.
+extern "C" int smer_grammar_sample_step_tp(int R, int V, const float* logits, long ldl, int32_t* state,
+                                           int nst, const int8_t* targets, int max_masks,
+                                           const uint8_t* keep, const uint8_t* reject, const uint8_t* cls,
+                                           int eos, int m0, int trash_pos, int max_span,
+                                           const int32_t* src_len, int64_t* ids, int32_t* meta,
+                                           int32_t* out_tok, int cap, uint32_t* mt, int32_t* ctl,
+                                           int32_t* ring, int ring_n, const double* tp,
+                                           smer_stream_t stream) {
+  SMER_REQUIRE(tp != nullptr, "smer_grammar_sample_step_tp: null tp");
+  return launch_grammar_sample(R, V, logits, ldl, state, nst, targets, max_masks,
+                               keep, reject, cls, eos, m0, trash_pos, max_span, src_len, ids, meta, out_tok, cap,
+                               mt, ctl, ring, ring_n, tp, stream);
 }

@@ -464,7 +464,8 @@ class DecodeSession:
             if sample:
                 ops.grammar_sample_step(self.logits_t, self.g_state, self.g_targets, self.g_keep,
                                         self.g_reject, self.g_cls, self.g_srclen, self.ids_t,
-                                        self.meta_t, self.g_out, self.g_mt, self.g_alive, **gargs)
+                                        self.meta_t, self.g_out, self.g_mt, self.g_alive, tp=self.g_tp,
+                                        **gargs)
                 return
             ops.grammar_greedy_step(self.logits_t, self.g_state, self.g_targets, self.g_keep,
                                     self.g_cls, self.g_srclen, self.ids_t, self.meta_t, self.g_out,
@@ -485,17 +486,35 @@ class DecodeSession:
         t_c = time.perf_counter()
         return g, ring, rv, t_a, t_b, t_c
 
-    def sampled_decode(self, spans, keep, reject, cls, *, eos, m0, lookahead=3, max_span=100):
-        """The sampled infill loop (the reference's default weighted_sampling
-        with its redraws) on device: each step is one replay of the captured
+    def sampled_decode(self, spans, keep, reject, cls, *, eos, m0, lookahead=3, max_span=100,
+                       t=1.0, p=None):
+        """The sampled infill loop (the reference's sampling(): softmax with
+        temperature, then weighted_sampling or, with p, nucleus, and its
+        redraws) on device: each step is one replay of the captured
         decoder step + csrc/decode_ops.hip grammar_sample_kernel, which draws
         from numpy's global MT19937 stream -- its state is handed to the
         device here and handed back to np.random afterwards, so the host
-        stream continues exactly as if the host had drawn.  Returns
+        stream continues exactly as if the host had drawn.  t, p: scalars or
+        one value per span (p None = the whole distribution); the kernel
+        reads them from a device buffer on every step, so calls with other
+        values replay the same captured graph.  Returns
         (per-request emitted ids, steps, error flags, per-request redraw
         failure flags)."""
         if all(sp.done for sp in spans):  # nothing to draw: np.random stays untouched
             return [[] for _ in spans], 0, np.zeros(len(spans), dtype=np.int32), [[] for _ in spans]
+        n = len(spans)
+        ts = list(t) if isinstance(t, (list, tuple, np.ndarray)) else [t] * n
+        ps = list(p) if isinstance(p, (list, tuple, np.ndarray)) else [p] * n
+        if len(ts) != n or len(ps) != n:
+            raise ValueError("sampled_decode: one t and one p per span")
+        tp_h = np.empty((self.R, 2), dtype=np.float64)
+        tp_h[:, 0], tp_h[:, 1] = 1.0, -1.0
+        for r in range(n):
+            tp_h[r, 0] = float(ts[r])
+            tp_h[r, 1] = -1.0 if ps[r] is None else float(ps[r])
+        if not (np.isfinite(tp_h).all() and (tp_h[:, 0] > 0).all() and
+                all(q is None or float(q) >= 0 for q in ps)):
+            raise ValueError("sampled_decode: t must be finite and > 0, p None or finite and >= 0")
         st0 = np.random.get_state()
         if st0[0] != "MT19937":
             raise RuntimeError("sampled_decode: np.random is not MT19937")
@@ -503,7 +522,7 @@ class DecodeSession:
         mt_h[:624] = st0[1]
         mt_h[624] = int(st0[2])
         res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
-                                   max_span=max_span, sample=(reject, mt_h))
+                                   max_span=max_span, sample=(reject, mt_h, tp_h))
         m = self.g_mt.cpu().numpy().view(np.uint32)
         np.random.set_state(("MT19937", m[:624].copy(), int(m[624]), st0[3], st0[4]))
         ids, steps, err, step_ms = res
@@ -564,8 +583,11 @@ class DecodeSession:
             if getattr(self, "g_reject", None) is None or tuple(self.g_reject.shape) != tuple(keep.shape):
                 # (a captured graph keyed on another keep shape is never replayed for this one)
                 self.g_reject = torch.zeros(keep.shape, dtype=torch.uint8, device=dev)
+            if getattr(self, "g_tp", None) is None:
+                self.g_tp = torch.zeros(self.R, 2, dtype=torch.float64, device=dev)
             self.g_mt.copy_(mt_t)
             self.g_reject.copy_(reject_t)
+            self.g_tp.copy_(torch.from_numpy(sample[2]))
         if gc is not None and gc["key"] == gkey:
             # the captured step + grammar graph of an earlier call with the
             # same shapes: refresh its persistent inputs in place and replay

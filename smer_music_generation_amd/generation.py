@@ -16,6 +16,9 @@ Differences, all opt-in keywords with reference defaults:
     fp32 whatever precision the model trains in (bit-exact ids); None
     decodes at the model's own precision.
   * `generation_batch(...)`: many requests decoded in lockstep.
+  * `t=1.0, p=None` on `generation_all` / `infill` / `generation_batch`: the
+    temperature and nucleus threshold of the reference's `sampling()`, which
+    its own `generation_all` never passes on.
 The grammar state machine, the -100 logit masking, the float64 softmax and
 the numpy RNG consumption are the reference's, so with the same
 `np.random` state the same token ids come out.
@@ -147,6 +150,36 @@ def sampling(logit, vocab, p=None, t=1.0, greedy=False, **flags):
     return weighted_sampling(probs)
 
 
+def _check_tp(t, p, n=None):
+    """Validated (t, p) of a call; with n, one pair per request (scalars are
+    repeated, sequences must have n entries).  t finite and > 0; p None, or
+    finite and >= 0.  Raises ValueError; draws nothing."""
+    def seq(x):
+        return isinstance(x, (list, tuple, np.ndarray))
+    if n is None:
+        if seq(t) or seq(p):
+            raise ValueError("t and p are scalars here")
+        ts, ps = [t], [p]
+    else:
+        ts = list(t) if seq(t) else [t] * n
+        ps = list(p) if seq(p) else [p] * n
+        if len(ts) != n or len(ps) != n:
+            raise ValueError("t and p: one value, or one per request (%d)" % n)
+    out = []
+    for a, b in zip(ts, ps):
+        try:
+            a = float(a)
+            b = None if b is None else float(b)
+        except (TypeError, ValueError):
+            raise ValueError("t must be a number, p a number or None") from None
+        if not (np.isfinite(a) and a > 0.0):
+            raise ValueError("temperature t must be finite and > 0 (got %r)" % a)
+        if b is not None and not (np.isfinite(b) and b >= 0.0):
+            raise ValueError("nucleus threshold p must be None, or finite and >= 0 (got %r)" % b)
+        out.append((a, b))
+    return out[0] if n is None else out
+
+
 def gen_nopeek_mask(length):
     m = (torch.triu(torch.ones(length, length)) == 1).transpose(0, 1)
     return m.float().masked_fill(m == 0, float("-inf")).masked_fill(m == 1, 0.0)
@@ -248,8 +281,11 @@ def grammar_tables(vocab, all_controls):
 class _Span:
     """Decoding state of one request: mask index, span tokens, grammar flags."""
 
-    def __init__(self, vocab, src, mask_target, all_controls, no_whole, greedy, logger):
+    def __init__(self, vocab, src, mask_target, all_controls, no_whole, greedy, logger, t=1.0,
+                 p=None):
         self.v = vocab
+        self.t = t
+        self.p = p
         self.src = src
         self.mask_target = mask_target
         self.all_controls = set(int(c) for c in all_controls)
@@ -276,12 +312,12 @@ class _Span:
         return self.tgt_inp + self.this_in
 
     def _draw(self, logit, check, failmsg, flags):
-        idx = sampling(logit, self.v, greedy=self.greedy, **flags)
+        idx = sampling(logit, self.v, p=self.p, t=self.t, greedy=self.greedy, **flags)
         if check is None:
             return idx
         n = 0
         while check(idx):
-            idx = sampling(logit, self.v, greedy=self.greedy, **flags)
+            idx = sampling(logit, self.v, p=self.p, t=self.t, greedy=self.greedy, **flags)
             n += 1
             if n > 10:
                 if self.logger is not None:
@@ -424,7 +460,7 @@ class _Precision:
 
 def generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
                    bars_to_generate, *, greedy=False, use_kv_cache=True, stats=None,
-                   precision="fp32", warm=True, device_grammar=True):
+                   precision="fp32", warm=True, device_grammar=True, t=1.0, p=None):
     """`generation.py:468-696`.  Returns (restored '<U9' tokens,
     mask_track_names, mask_bar_names) or None (nothing masked / on error,
     after printing it, as the reference does).  `stats` (a dict, opt-in)
@@ -441,14 +477,23 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
     (bf16 for a default-constructed model: faster, ids may differ at
     near-ties); the batched serving API `generation_batch` keeps None.
     device_grammar: (KV-cached path) run the grammar and the draws on the
-    device inside the captured decode step -- greedy argmax, or the default
-    weighted sampling on numpy's MT19937 stream handed to the device and back
+    device inside the captured decode step -- greedy argmax, or sampling
+    on numpy's MT19937 stream handed to the device and back
     (csrc/decode_ops.hip grammar_sample_kernel) -- with no host round trip
-    per token; False keeps the per-token host loop."""
+    per token; False keeps the per-token host loop.
+    t, p: the temperature and the nucleus threshold of the reference's
+    `sampling()` (softmax of masked logits / t; with p, the draw is among the
+    most probable tokens whose cumulative probability first exceeds p).  The
+    defaults are the reference's own call (the whole distribution at t = 1).
+    Every path -- device, host loop, use_kv_cache=False -- draws from the same
+    distribution on the same stream.  A t that is not finite and > 0, or a p
+    that is neither None nor finite and >= 0, raises ValueError before
+    anything is drawn."""
+    t, p = _check_tp(t, p)
     with _Precision(model, precision):
         return _generation_all(model, events, device, vocab, logger, all_controls,
                                tracks_to_generate, bars_to_generate, greedy, use_kv_cache, stats,
-                               warm, device_grammar)
+                               warm, device_grammar, t, p)
 
 
 _REJECT_CACHE = {}
@@ -479,7 +524,8 @@ def _sampled_on_device(sess, st, vocab, all_controls, logger):
     keep, cls = grammar_tables(vocab, all_controls)
     rng0 = np.random.get_state()
     seqs, steps, err, fails = sess.sampled_decode([st], keep, reject_table(vocab), cls,
-                                                  eos=vocab.eos_index, m0=vocab.char2index('m_0'))
+                                                  eos=vocab.eos_index, m0=vocab.char2index('m_0'),
+                                                  t=st.t, p=st.p)
     if err[0] & 2:
         np.random.set_state(rng0)
         return None
@@ -495,11 +541,12 @@ def _sampled_on_device(sess, st, vocab, all_controls, logger):
 
 
 def _generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
-                    bars_to_generate, greedy, use_kv_cache, stats, warm=True, device_grammar=True):
+                    bars_to_generate, greedy, use_kv_cache, stats, warm=True, device_grammar=True,
+                    t=1.0, p=None):
     try:
         src, mtn, mbn, target, no_whole = _prepare(events, vocab, tracks_to_generate,
                                                    bars_to_generate)
-        st = _Span(vocab, src, target, all_controls, no_whole, greedy, logger)
+        st = _Span(vocab, src, target, all_controls, no_whole, greedy, logger, t, p)
         if st.n_masks == 0:
             return None
         model.eval()
@@ -517,7 +564,7 @@ def _generation_all(model, events, device, vocab, logger, all_controls, tracks_t
                     if n is not None:
                         steps = n
                     else:  # fresh span, same RNG start: the host loop below
-                        st = _Span(vocab, src, target, all_controls, no_whole, greedy, logger)
+                        st = _Span(vocab, src, target, all_controls, no_whole, greedy, logger, t, p)
                         sess.prefill([0], [src])
                 fed = 0
                 while not st.done:
@@ -617,27 +664,37 @@ def _batch_session(model, R, Smax, Tmax, precision, exact_tmax=False, warm=True)
 
 def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logger=None,
                      max_tgt=None, precision=None, return_stats=False, device_grammar=True,
-                     warm=True):
+                     warm=True, t=1.0, p=None):
     """Decode many infill requests in lockstep on one KV-cached session.
 
     requests: list of (events, tracks_to_generate, bars_to_generate).
-    Greedy decoding runs the grammar on device (`device_grammar`, the
+    Decoding runs the grammar on device (`device_grammar`, the
     default): the step graph ends in the grammar kernel that picks every
     request's token and writes the next step's feed, so steps replay back
     to back; the emitted ids are then replayed through the host `_Span`s,
     which rebuild exactly the reference's event lists (and log the
-    reference's redraw failures).  `device_grammar=False` (or sampling)
-    keeps the per-step host loop.
+    reference's redraw failures).  With greedy=False the kernel is the
+    sampler (vocabularies up to 512 tokens): it draws for the requests in
+    order on numpy's MT19937 stream, as the host loop does, so the tokens and
+    the np.random state afterwards are the host loop's.
+    `device_grammar=False` keeps the per-step host loop.
+    t, p: temperature and nucleus threshold (see generation_all), one value
+    or one per request; validated before anything is drawn (ValueError).
     warm: reuse (and keep) this model's cached decode session, as a serving
     process would; False builds a private session freed after the call
     (see also clear_decode_sessions).
     Returns a list of (restored, mask_track_names, mask_bar_names) (None
     where nothing was masked), and optionally {'tokens', 'steps'}."""
     t0 = time.perf_counter()
+    tps = _check_tp(t, p, len(requests))
     preps = [_prepare(list(ev), vocab, tr, br) for ev, tr, br in requests]
-    spans = [_Span(vocab, p[0], p[3], all_controls, p[4], greedy, logger) for p in preps]
+
+    def fresh_spans():
+        return [_Span(vocab, q[0], q[3], all_controls, q[4], greedy, logger, a, b)
+                for q, (a, b) in zip(preps, tps)]
+    spans = fresh_spans()
     R = len(requests)
-    Smax = max(len(p[0]) for p in preps)
+    Smax = max(len(q[0]) for q in preps)
     Tmax = max_tgt or max(128, 100 * max(s.n_masks for s in spans) + 8)
     model.eval()
     tokens = steps = 0
@@ -645,7 +702,7 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
         sess = _batch_session(model, R, Smax, Tmax, precision, exact_tmax=max_tgt is not None,
                               warm=warm)
         t1 = time.perf_counter()
-        sess.prefill(list(range(R)), [p[0] for p in preps])
+        sess.prefill(list(range(R)), [q[0] for q in preps])
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         t_dev = 0.0
@@ -666,8 +723,8 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                 raise ValueError("decoder prefix exceeds session max_tgt %d" % (sess.Tmax - 1))
             # key rows the decode steps attended to (SURVEY §8d infill bytes):
             # request r's i-th step reads its S_r memory rows and i+1 prefix rows
-            kv_reads = int(sum(len(q) * len(p[0]) + len(q) * (len(q) + 1) // 2
-                               for q, p in zip(seqs, preps)))
+            kv_reads = int(sum(len(q) * len(pr[0]) + len(q) * (len(q) + 1) // 2
+                               for q, pr in zip(seqs, preps)))
             for sp, seq in zip(spans, seqs):
                 if logger is None:  # no redraw report to log: commit only
                     sp.commit_all(seq)
@@ -678,6 +735,38 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                 if not sp.done:
                     raise RuntimeError("device grammar and host replay disagree")
                 tokens += len(seq)
+        elif device_grammar and vocab.vocab_size <= 512:
+            keep, cls = grammar_tables(vocab, all_controls)
+            rng0 = np.random.get_state()
+            ts = time.perf_counter()
+            seqs, dsteps, err, fails = sess.sampled_decode(
+                spans, keep, reject_table(vocab), cls, eos=vocab.eos_index,
+                m0=vocab.char2index('m_0'), t=[a for a, _ in tps], p=[b for _, b in tps])
+            t_dev = time.perf_counter() - ts
+            if np.any(err & 2):
+                # some row's probabilities missed 1 by more than 1e-9
+                # (np.random.choice territory): same RNG start, fresh spans,
+                # and the whole batch goes through the host loop below
+                np.random.set_state(rng0)
+                spans = fresh_spans()
+                sess.prefill(list(range(R)), [q[0] for q in preps])
+                t_dev = 0.0
+            else:
+                if np.any(err & 1):
+                    raise ValueError("decoder prefix exceeds session max_tgt %d" % (sess.Tmax - 1))
+                steps = dsteps
+                # replay in the host loop's order (step by step, requests in
+                # order): the redraw-failure lines come out in its order too
+                for k in range(max([len(q) for q in seqs] + [0])):
+                    for sp, seq, fl in zip(spans, seqs, fails):
+                        if k < len(seq):
+                            if fl[k] and logger is not None:
+                                logger.info(sp.spec()[2])
+                            sp.commit(seq[k])
+                for sp, seq in zip(spans, seqs):
+                    if not sp.done:
+                        raise RuntimeError("device grammar and host replay disagree")
+                    tokens += len(seq)
         while True:
             live = [i for i in range(R) if not spans[i].done]
             if not live:
@@ -704,11 +793,11 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
             tokens += len(live)
             steps += 1
     out = []
-    for p, st in zip(preps, spans):
+    for q, st in zip(preps, spans):
         if st.n_masks == 0:
             out.append(None)
             continue
-        out.append((restore_marked_input(_src_tokens(vocab, p[0]), st.total), p[1], p[2]))
+        out.append((restore_marked_input(_src_tokens(vocab, q[0]), st.total), q[1], q[2]))
     if return_stats:
         t3 = time.perf_counter()
         return out, {"tokens": tokens, "steps": steps, "prepare_s": t1 - t0,

@@ -617,11 +617,13 @@ def grammar_greedy_step(logits, state, targets, keep, cls, src_len, ids, meta, o
 
 
 def grammar_sample_step(logits, state, targets, keep, reject, cls, src_len, ids, meta, out_tok, mt,
-                        ctl, *, eos, m0, trash_pos, max_span=100, ring=None):
+                        ctl, *, eos, m0, trash_pos, max_span=100, ring=None, tp=None):
     """The sampled grammar step (smer_grammar_sample_step): mt uint32 [625]
     (numpy MT19937 key + position, updated in place), ctl int32 [3]; with
     `ring` (pinned host int32 [n]) the live count lands in ring[step % n],
-    else in ctl[0]."""
+    else in ctl[0].  tp (float64 [R, 2] on the device: each request's
+    temperature and nucleus threshold, negative = None) selects
+    smer_grammar_sample_step_tp, which reads it on every step."""
     R, nst = state.shape
     V = keep.shape[1]
     for t, dt in ((state, torch.int32), (targets, torch.int8), (keep, torch.uint8),
@@ -636,11 +638,17 @@ def grammar_sample_step(logits, state, targets, keep, reject, cls, src_len, ids,
         raise RuntimeError("grammar_sample_step: shape mismatch")
     if ring is not None and (ring.dtype != torch.int32 or not ring.is_pinned()):
         raise RuntimeError("grammar_sample_step: ring must be pinned int32")
-    call("smer_grammar_sample_step", R, V, _p(logits), _ld(logits), _p(state), nst, _p(targets),
-         targets.shape[1], _p(keep), _p(reject), _p(cls), int(eos), int(m0), int(trash_pos),
-         int(max_span), _p(src_len), _p(ids), _p(meta), _p(out_tok), out_tok.shape[1], _p(mt),
-         _p(ctl), ring.data_ptr() if ring is not None else None, ring.numel() if ring is not None else 0,
-         _stream())
+    args = (R, V, _p(logits), _ld(logits), _p(state), nst, _p(targets),
+            targets.shape[1], _p(keep), _p(reject), _p(cls), int(eos), int(m0), int(trash_pos),
+            int(max_span), _p(src_len), _p(ids), _p(meta), _p(out_tok), out_tok.shape[1], _p(mt),
+            _p(ctl), ring.data_ptr() if ring is not None else None, ring.numel() if ring is not None else 0)
+    if tp is None:
+        call("smer_grammar_sample_step", *args, _stream())
+        return
+    if tp.dtype != torch.float64 or not tp.is_contiguous() or tuple(tp.shape) != (R, 2) or \
+            tp.device != state.device:
+        raise RuntimeError("grammar_sample_step: tp must be contiguous float64 [R, 2] on the device")
+    call("smer_grammar_sample_step_tp", *args, _p(tp), _stream())
 
 
 # ---------------------------------------------------------------------------

@@ -1,0 +1,346 @@
+"""Temperature and nucleus sampling on the device decode path
+(csrc/decode_ops.hip grammar_sample_kernel<.., TP>, smer_grammar_sample_step_tp):
+the kernel alone against the host sampler, then the plugin and the batched
+calls against their per-token host loops, tokens and np.random state."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+dev = "cuda"
+CTRL = ['key', 'tensile', 'density', 'polyphony', 'occupation']
+TS = (0.8, 1.0, 1.3, 0.5, 3.0)
+PS = (None, 0.0, 0.5, 0.9, 0.999, 1.0)
+FLAG_SETS = [(1, 5, 0), (2, 5, 0), (4, 5, 0), (8, 5, 0), (0, 1, 0), (0, 1, 1), (0, 5, 0), (0, 1, 4)]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+
+
+def _golden(golden_dir):
+    z = np.load(os.path.join(golden_dir, "forward_train_micro.npz"))
+    meta = json.load(open(os.path.join(golden_dir, "forward_train_micro.json")))
+    return z, meta
+
+
+def _model(z, meta, precision):
+    from smer_music_generation_amd.model import ScoreTransformer
+    c = meta["config"]
+    m = ScoreTransformer(309, c["d_model"], c["nhead"], c["num_encoder_layers"],
+                         c["num_decoder_layers"], c["dim_feedforward"], c["max_seq_length"], 0.0,
+                         0.0, precision=precision)
+    sd = {k[2:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("w/")}
+    sd["pos_enc.pe"] = m.pos_enc.pe.clone()
+    m.load_state_dict(sd)
+    return m.to(dev)
+
+
+def _requests(golden_dir, n):
+    from smer_music_generation_amd.synth import synth_events
+    g = json.load(open(os.path.join(golden_dir, "infill_micro.json")))
+    reqs = [(synth_events(60 + i, n_bars=6 + i, n_tracks=3), [i % 3], [2, 3] if i % 2 else [4])
+            for i in range(n)]
+    return reqs, g["all_controls"]
+
+
+class _Log:
+    def __init__(self):
+        self.lines = []
+
+    def info(self, msg):
+        self.lines.append(msg)
+
+
+def _rng_state():
+    st = np.random.get_state()
+    return st[1].copy(), int(st[2])
+
+
+def _same(a, b):
+    return a[1] == b[1] and np.array_equal(a[0], b[0])
+
+
+def _state_code(f, ln, tg):
+    return (0 if f & 1 else 1 if f & 2 else 2 if f & 4 else 4 if f & 8 else
+            (10 if tg == 0 else 5 + tg) if ln == 1 else 11)
+
+
+def kernel_rows(V, n_rows=240, seed=3):
+    """The rows of the kernel test: row i has (t, p) = (TS[i % 5], PS[(i // 5)
+    % 6]) (every pair of the grid, 8 times) and the grammar state FLAG_SETS[i
+    % 8].  Row kinds as in test_device_sampler_draws_match_numpy_on_random_rows:
+    i % 10 == 7 has kept logits below -100 (full 512-key sort), i % 10 == 3
+    sits around -80 (t = 0.5 there: above and below the fast path's -100 +
+    40 t), i % 10 == 5 has logits at exactly -100 (ties with the masked
+    ones).  The t = 3 rows are lifted by 12 so that the masked tokens, at
+    -100 / 3, stay below 1e-12 of the row (condition (a) of the test)."""
+    rng = np.random.default_rng(seed)
+    rows = (rng.standard_normal((n_rows, V)) * rng.uniform(0.5, 6.0, (n_rows, 1))).astype(np.float32)
+    rows[4::5] += np.float32(12.0)
+    rows[7::10, ::13] = -130.0
+    rows[3::10] = rows[3::10] * 0.25 - 78.0
+    rows[5::10, ::17] = -100.0
+    tp = [(TS[i % 5], PS[(i // 5) % 6]) for i in range(n_rows)]
+    return rows, tp
+
+
+def host_conditions(row, keep, t, p):
+    """(a) V * exp((-100 - max kept logit) / t), to stay below 1e-12: no draw
+    lands among the tied masked tokens (not under test);
+    (b) min |c_i - p| of the nucleus' cumulative sums, to stay above 1e-9:
+    the one-ulp difference between the device's and numpy's exp cannot move
+    the threshold (inf without a nucleus)."""
+    a = len(row) * np.exp((-100.0 - float(row[keep].max())) / t)
+    if p is None:
+        return a, np.inf
+    lg = np.where(keep, row.astype(np.float64), -100.0)
+    e = np.exp(lg / t)
+    probs = e / np.sum(e)
+    q = probs / (np.add.accumulate(probs)[-1] + 1e-5)
+    c = np.cumsum(np.sort(q)[::-1])
+    return a, float(np.min(np.abs(c - p)))
+
+
+def test_device_sampler_with_t_and_p_matches_host_on_random_rows():
+    """grammar_sample_kernel<TP> alone, 4 requests per launch, each with its
+    own (t, p) from the grid: every id, every redraw-failure bit and the
+    final MT19937 key and position equal the host's sampling(..., p, t) +
+    the redraw loop on the same stream.  Conditions (a)-(c) hold for every
+    row (asserted: no row is left out)."""
+    from smer_music_generation_amd import ops as O
+    from smer_music_generation_amd.generation import (grammar_spec, grammar_tables, reject_table,
+                                                       sampling)
+    from smer_music_generation_amd.vocab import WordVocab
+    v = WordVocab(0, CTRL)
+    V = v.vocab_size
+    keep, cls = grammar_tables(v, v.density_indices + v.occupation_indices)
+    rej = reject_table(v)
+    rows, tp = kernel_rows(V)
+    n_rows, R = len(rows), 4
+    assert {x for x in tp} == {(t, p) for t in TS for p in PS}
+    np.random.seed(11)
+    host = []
+    worst_a, worst_b = 0.0, np.inf
+    for i in range(n_rows):
+        f, ln, tg = FLAG_SETS[i % len(FLAG_SETS)]
+        code = _state_code(f, ln, tg)
+        t, p = tp[i]
+        a, b = host_conditions(rows[i], keep[code].astype(bool), t, p)
+        worst_a, worst_b = max(worst_a, a), min(worst_b, b)
+        flags, chk, _ = grammar_spec(v, code)
+        idx = sampling(rows[i], v, p, t, **flags)
+        n = 0
+        fail = False
+        if chk is not None:
+            while chk(idx):
+                idx = sampling(rows[i], v, p, t, **flags)
+                n += 1
+                if n > 10:
+                    fail = True
+                    break
+        host.append((int(idx), fail))
+    st_host = np.random.get_state()
+    print("worst (a) %.3g (< 1e-12), worst (b) %.3g (> 1e-9)" % (worst_a, worst_b))
+    assert worst_a < 1e-12, worst_a
+    assert worst_b > 1e-9, worst_b
+    np.random.seed(11)
+    st0 = np.random.get_state()
+    mt = torch.from_numpy(np.concatenate([st0[1], [st0[2]]]).astype(np.uint32).view(np.int32)).to(dev)
+    keep_t = torch.from_numpy(keep).to(dev)
+    rej_t = torch.from_numpy(rej).to(dev)
+    cls_t = torch.from_numpy(cls).to(dev)
+    src_len = torch.ones(R, dtype=torch.int32, device=dev)
+    dev_ids, errs = [], []
+    for i0 in range(0, n_rows, R):
+        st = np.zeros((R, 12), dtype=np.int32)
+        tg_h = np.zeros((R, 1), dtype=np.int8)
+        lg_h = np.zeros((2 * R, V), dtype=np.float32)
+        tp_h = np.zeros((R, 2), dtype=np.float64)
+        for r in range(R):
+            f, ln, tg = FLAG_SETS[(i0 + r) % len(FLAG_SETS)]
+            st[r, 1], st[r, 2], st[r, 4] = f, ln, 1
+            tg_h[r, 0] = tg
+            lg_h[2 * r + 1] = rows[i0 + r]
+            t, p = tp[i0 + r]
+            tp_h[r] = (t, -1.0 if p is None else p)
+        state = torch.from_numpy(st).to(dev)
+        out = torch.zeros(R, 4, dtype=torch.int32, device=dev)
+        O.grammar_sample_step(torch.from_numpy(lg_h).to(dev), state, torch.from_numpy(tg_h).to(dev),
+                              keep_t, rej_t, cls_t, src_len,
+                              torch.zeros(2 * R, dtype=torch.int64, device=dev),
+                              torch.zeros(4, 2 * R, dtype=torch.int32, device=dev), out, mt,
+                              torch.zeros(3, dtype=torch.int32, device=dev),
+                              eos=v.eos_index, m0=v.char2index('m_0'), trash_pos=200,
+                              tp=torch.from_numpy(tp_h).to(dev))
+        x = out[:, 0].cpu().numpy()
+        dev_ids += [(int(k) & 0xFFFF, bool(int(k) >> 16)) for k in x]
+        errs += state[:, 8].cpu().numpy().tolist()
+    mth = mt.cpu().numpy().view(np.uint32)
+    assert not any(e & 2 for e in errs)  # (c)
+    assert dev_ids == host
+    assert int(mth[624]) == st_host[2] and np.array_equal(mth[:624], st_host[1])
+
+
+def test_device_sampler_tp_defaults_are_the_plain_step():
+    """t = 1, p = None through the tp entry: the ids, the stream and the
+    state rows of smer_grammar_sample_step on the same inputs."""
+    from smer_music_generation_amd import ops as O
+    from smer_music_generation_amd.generation import grammar_tables, reject_table
+    from smer_music_generation_amd.vocab import WordVocab
+    v = WordVocab(0, CTRL)
+    V = v.vocab_size
+    keep, cls = grammar_tables(v, v.density_indices + v.occupation_indices)
+    rows, _ = kernel_rows(V, n_rows=40, seed=5)
+    R = 4
+    res = {}
+    for with_tp in (False, True):
+        np.random.seed(12)
+        st0 = np.random.get_state()
+        mt = torch.from_numpy(np.concatenate([st0[1], [st0[2]]]).astype(np.uint32).view(np.int32)).to(dev)
+        outs = []
+        for i0 in range(0, len(rows), R):
+            st = np.zeros((R, 12), dtype=np.int32)
+            lg_h = np.zeros((2 * R, V), dtype=np.float32)
+            for r in range(R):
+                f, ln, _ = FLAG_SETS[(i0 + r) % len(FLAG_SETS)]
+                st[r, 1], st[r, 2], st[r, 4] = f, ln, 1
+                lg_h[2 * r + 1] = rows[i0 + r]
+            state = torch.from_numpy(st).to(dev)
+            out = torch.zeros(R, 4, dtype=torch.int32, device=dev)
+            tp_t = torch.tensor([[1.0, -1.0]] * R, dtype=torch.float64, device=dev) if with_tp else None
+            O.grammar_sample_step(torch.from_numpy(lg_h).to(dev), state,
+                                  torch.zeros(R, 1, dtype=torch.int8, device=dev),
+                                  torch.from_numpy(keep).to(dev), torch.from_numpy(reject_table(v)).to(dev),
+                                  torch.from_numpy(cls).to(dev), torch.ones(R, dtype=torch.int32, device=dev),
+                                  torch.zeros(2 * R, dtype=torch.int64, device=dev),
+                                  torch.zeros(4, 2 * R, dtype=torch.int32, device=dev), out, mt,
+                                  torch.zeros(3, dtype=torch.int32, device=dev),
+                                  eos=v.eos_index, m0=v.char2index('m_0'), trash_pos=200, tp=tp_t)
+            outs.append((out.cpu().numpy().copy(), state.cpu().numpy().copy()))
+        res[with_tp] = (outs, mt.cpu().numpy().copy())
+    for (oa, sa), (ob, sb) in zip(res[False][0], res[True][0]):
+        assert np.array_equal(oa, ob) and np.array_equal(sa, sb)
+    assert np.array_equal(res[False][1], res[True][1])
+
+
+def _plugin_runs(m, v, reqs, ctl, precision, calls):
+    """generation_all over `reqs`, call i with calls[i] keywords, on the
+    device and on the host loop: (tokens, log lines, RNG state) per call."""
+    from smer_music_generation_amd.generation import generation_all
+    runs = {}
+    for dg in (True, False):
+        np.random.seed(77)
+        out, logs, states = [], [], []
+        for (ev, tr, br), kw in zip(reqs, calls):
+            lg = _Log()
+            res = generation_all(m, list(ev), dev, v, lg, ctl, tr, br, precision=precision,
+                                 device_grammar=dg, **kw)
+            assert res is not None
+            out.append(([str(x) for x in res[0]], res[1], res[2]))
+            logs.append(lg.lines)
+            states.append(_rng_state())
+        runs[dg] = (out, logs, states)
+    return runs
+
+
+@pytest.mark.parametrize("precision", ["fp32", None])
+def test_plugin_with_t_and_p_matches_host_loop(golden_dir, precision):
+    """generation_all(t=0.8, p=0.9) on 3 requests: the device path returns
+    the host loop's tokens, logs its redraw lines and leaves np.random in its
+    state after every call."""
+    from smer_music_generation_amd.vocab import WordVocab
+    z, meta = _golden(golden_dir)
+    m = _model(z, meta, "fp32")
+    v = WordVocab(0, CTRL)
+    reqs, ctl = _requests(golden_dir, 3)
+    runs = _plugin_runs(m, v, reqs, ctl, precision, [dict(t=0.8, p=0.9)] * 3)
+    a, b = runs[True], runs[False]
+    assert a[0] == b[0]
+    assert a[1] == b[1]
+    assert all(_same(x, y) for x, y in zip(a[2], b[2]))
+
+
+def test_batch_sampled_on_device_matches_host_loop(golden_dir):
+    """generation_batch(greedy=False) with one (t, p) per request: the
+    device sampler gives the host loop's outputs, redraw lines and final
+    np.random state."""
+    from smer_music_generation_amd import generation as G
+    from smer_music_generation_amd.vocab import WordVocab
+    z, meta = _golden(golden_dir)
+    m = _model(z, meta, "fp32")
+    v = WordVocab(0, CTRL)
+    reqs, ctl = _requests(golden_dir, 3)
+    res = {}
+    for dg in (True, False):
+        np.random.seed(31)
+        lg = _Log()
+        out, stats = G.generation_batch(m, [(list(e), t, b) for e, t, b in reqs], v, ctl, greedy=False,
+                                        logger=lg, device_grammar=dg, t=[1.0, 0.7, 1.3],
+                                        p=[None, 0.9, 0.5], return_stats=True)
+        res[dg] = ([([str(x) for x in o[0]], o[1], o[2]) for o in out], lg.lines, _rng_state(),
+                   stats["tokens"], stats["steps"])
+    assert res[True][0] == res[False][0]
+    assert res[True][1] == res[False][1]
+    assert _same(res[True][2], res[False][2])
+    assert res[True][3:] == res[False][3:] and res[True][3] > 0
+    sess = [s for s in G._BATCH_SESSIONS.values() if s.R == 3 and s.model is m]
+    assert sess and getattr(sess[0], "g_tp", None) is not None  # the device sampler ran
+
+
+def test_other_t_and_p_replay_the_same_captured_graph(golden_dir):
+    """Two warm plugin calls with different (t, p) replay one captured step
+    graph (the kernel reads both from device memory), and each matches its
+    host-loop run."""
+    from smer_music_generation_amd import generation as G
+    from smer_music_generation_amd.vocab import WordVocab
+    z, meta = _golden(golden_dir)
+    m = _model(z, meta, "fp32")
+    v = WordVocab(0, CTRL)
+    reqs, ctl = _requests(golden_dir, 1)
+    ev, tr, br = reqs[0]
+    calls = [dict(t=0.7, p=0.5), dict(t=1.3, p=None), dict(t=1.0, p=0.999)]
+    host = []
+    np.random.seed(8)
+    for kw in calls:
+        res = G.generation_all(m, list(ev), dev, v, None, ctl, tr, br, device_grammar=False, **kw)
+        host.append(([str(x) for x in res[0]], _rng_state()))
+    G.clear_decode_sessions(m)
+    np.random.seed(8)
+    graphs = []
+    for kw, (want, st_want) in zip(calls, host):
+        res = G.generation_all(m, list(ev), dev, v, None, ctl, tr, br, **kw)
+        assert [str(x) for x in res[0]] == want
+        assert _same(_rng_state(), st_want)
+        sess = [s for s in G._BATCH_SESSIONS.values() if s.R == 1 and s.model is m]
+        assert len(sess) == 1
+        graphs.append(sess[0]._greedy["graph"])
+    assert graphs[1] is graphs[0] and graphs[2] is graphs[0]
+
+
+def test_explicit_defaults_equal_omitted(golden_dir):
+    """t=1.0, p=None spelled out: the tokens and the RNG state of the call
+    without them."""
+    from smer_music_generation_amd import generation as G
+    from smer_music_generation_amd.vocab import WordVocab
+    z, meta = _golden(golden_dir)
+    m = _model(z, meta, "fp32")
+    v = WordVocab(0, CTRL)
+    reqs, ctl = _requests(golden_dir, 2)
+    res = {}
+    for kw in ({}, dict(t=1.0, p=None)):
+        np.random.seed(19)
+        outs = []
+        for ev, tr, br in reqs:
+            r = G.generation_all(m, list(ev), dev, v, None, ctl, tr, br, **kw)
+            outs.append([str(x) for x in r[0]])
+        b = G.generation_batch(m, [(list(e), t, q) for e, t, q in reqs], v, ctl, greedy=False, **kw)
+        outs.append([[str(x) for x in o[0]] for o in b])
+        res[bool(kw)] = (outs, _rng_state())
+    assert res[True][0] == res[False][0]
+    assert _same(res[True][1], res[False][1])
