@@ -243,6 +243,28 @@ int smer_attn_decode_qln(int n_rows, int H, int D, const void* y, long ldy, cons
                          long row_stride, long req_stride, long head_stride, const int32_t* row_req,
                          const int32_t* row_nkeys, void* o, long ldo, float scale,
                          smer_stream_t stream);
+/* smer_attn_decode / smer_attn_decode_qln over SHARED memories (several
+ * decodes of one encoded source): group_tab holds n_groups int32 pairs
+ * {first row, row count}; the rows first .. first+count-1 all attend the
+ * memory of request slot row_req[first].  One block serves up to 4 rows of
+ * a group and loads each K / V key step once for all of them; every output
+ * row (and x_out row) has the bits the per-row entry writes for it.  Rows
+ * in no group are left untouched.  bf16; D 32 or 64 (qln: D 64, dmodel in
+ * {512, 768, 1024}); 16-B aligned pointers and strides.  The table is read
+ * on the device at run time: a captured launch serves any split of the same
+ * (n_rows, n_groups). */
+int smer_attn_decode_shared(int dtype, int n_rows, int H, int D, const void* q, long ldq,
+                            const void* kcache, const void* vcache, long row_stride,
+                            long req_stride, long head_stride, const int32_t* row_req,
+                            const int32_t* row_nkeys, const int32_t* group_tab, int n_groups,
+                            void* o, long ldo, float scale, smer_stream_t stream);
+int smer_attn_decode_shared_qln(int n_rows, int H, int D, const void* y, long ldy,
+                                const float* gamma, const float* beta, float eps, const void* wq,
+                                long ldw, const float* bq, void* x_out, long ldx, int dmodel,
+                                const void* kcache, const void* vcache, long row_stride,
+                                long req_stride, long head_stride, const int32_t* row_req,
+                                const int32_t* row_nkeys, const int32_t* group_tab, int n_groups,
+                                void* o, long ldo, float scale, smer_stream_t stream);
 /* smer_linear_decode with the post-norm LayerNorm in its prologue: the
  * Linear's input is LN(Y) (row statistics and normalisation bit-identical
  * to smer_layernorm_fwd with the same eps), also stored to X when X is

@@ -56,6 +56,11 @@ SIGNATURES = {
     "smer_attn_decode_qln": (c_int, [c_int, c_int, c_int, P, c_long, P, P, c_float, P, c_long, P,
                                      P, c_long, c_int, P, P, c_long, c_long, c_long, P, P, P, c_long,
                                      c_float, P]),
+    "smer_attn_decode_shared": (c_int, [c_int, c_int, c_int, c_int, P, c_long, P, P, c_long, c_long,
+                                        c_long, P, P, P, c_int, P, c_long, c_float, P]),
+    "smer_attn_decode_shared_qln": (c_int, [c_int, c_int, c_int, P, c_long, P, P, c_float, P, c_long,
+                                            P, P, c_long, c_int, P, P, c_long, c_long, c_long, P, P,
+                                            P, c_int, P, c_long, c_float, P]),
     "smer_kv_scatter_heads": (c_int, [c_int, c_int, c_int, c_int, P, c_long, P, c_long, c_long,
                                       c_long, P, P, P]),
     "smer_kv_scatter": (c_int, [c_int, c_int, c_int, P, c_long, P, c_long, c_long, P, P, P]),

@@ -1836,6 +1836,302 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_vec_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Decode cross attention over a SHARED memory (variations: several decodes
+// of one encoded source).  attn_decode_vec_kernel reads a request's K / V
+// once per (row, head) block; here one block serves a chunk of up to G rows
+// of a source group: each key step's K / V registers are loaded once and
+// applied to the running (m, l, acc[VEC]) of every row of the chunk.  Per
+// row the arithmetic is attn_decode_vec_kernel's, operation for operation
+// (key-to-lane-group assignment, one rescale per UNR keys, shuffle merge,
+// LDS merge in wave order, inv), so every output row has that kernel's bits;
+// only the loads are shared.  bf16.
+//
+// group_tab[g] = {first row, row count}: the rows first .. first+count-1
+// attend the memory of request slot row_req[first].  Block y is chunk c of
+// the group found by walking the table; a chunk takes the group's rows in
+// the order (odd offsets, then even offsets), so that in a decode session
+// (two row slots per take: even mostly one-key dummies, odd live) the live
+// rows share chunks and the dummy chunks do one key step.  A row takes part
+// in a key step only while the step starts below its own key count.
+constexpr int DEC_SHARED_G = 4;
+
+template <int LPK, int UNR, int KPB>
+__device__ __forceinline__ void dec_shared_row_step(const float (&qv)[8], const uint4 (&kr)[UNR],
+                                                    const uint4 (&vr)[UNR], int j0, int grp, int nk,
+                                                    float& m, float& l, float (&acc)[8]) {
+  constexpr int VEC = 8;
+  float sc[UNR];
+  float mx = m;
+#pragma unroll
+  for (int u = 0; u < UNR; ++u) {
+    float kv[VEC];
+    cvt16b<bf16>(kr[u], kv);
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) s = fmaf(qv[i], kv[i], s);
+    s = group_sum<LPK>(s);
+    sc[u] = (j0 + u * KPB + grp) < nk ? s : -INFINITY;
+    mx = fmaxf(mx, sc[u]);
+  }
+  if (mx != -INFINITY) {  // group-uniform: some key of this step is valid
+    const float c = __expf(m - mx);
+    l *= c;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) acc[i] *= c;
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const float p = __expf(sc[u] - mx);
+      float vv[VEC];
+      cvt16b<bf16>(vr[u], vv);
+      l += p;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) acc[i] = fmaf(p, vv[i], acc[i]);
+    }
+    m = mx;
+  }
+}
+
+// dec_q_prologue for the rows of a chunk: wave i normalises row i (the
+// arithmetic of one wave of dec_q_prologue, whichever wave runs it), the
+// head's Wq slice is loaded once and applied to every row that needs q.
+template <int D, int NT, int DM, int G, typename PF>
+__device__ __forceinline__ void dec_q_prologue_shared(const DecQ& dq, int h, const int (&rows)[G],
+                                                      const int (&nkr)[G], int nr, int tid,
+                                                      float (*qs)[D], bf16 (*xs)[DM], bool store_x,
+                                                      PF pf) {
+  constexpr int TPO = NT / D;    // threads per query value
+  constexpr int KT = DM / TPO;   // K per thread (multiple of 8)
+  static_assert(NT / 64 >= G, "dec_q_prologue_shared: one wave per row");
+  const int lane = tid & 63, wave = tid >> 6;
+  const int d = tid / TPO, part = tid % TPO;
+  const bf16* wr = static_cast<const bf16*>(dq.wq) + (long)(h * D + d) * dq.ldw + part * KT;
+  constexpr int NC = (DM + 511) / 512;  // 16-B chunks per lane
+  constexpr int NCH = DM / 8;
+  // wave w reads the row it may normalise (w < nr), the others row 0
+  int r = rows[0];
+#pragma unroll
+  for (int i = 1; i < G; ++i)
+    if (wave == i && i < nr) r = rows[i];
+  bf16x8 yv[NC];
+  float4 gv[NC][2], bv[NC][2];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int ch = min(lane + 64 * c, NCH - 1);
+    yv[c] = *reinterpret_cast<const bf16x8*>(static_cast<const bf16*>(dq.y) + (long)r * dq.ldy + ch * 8);
+    gv[c][0] = *reinterpret_cast<const float4*>(dq.gamma + ch * 8);
+    gv[c][1] = *reinterpret_cast<const float4*>(dq.gamma + ch * 8 + 4);
+    bv[c][0] = *reinterpret_cast<const float4*>(dq.beta + ch * 8);
+    bv[c][1] = *reinterpret_cast<const float4*>(dq.beta + ch * 8 + 4);
+  }
+  bf16x8 wv[KT / 8];
+#pragma unroll
+  for (int j = 0; j < KT / 8; ++j) wv[j] = *reinterpret_cast<const bf16x8*>(wr + 8 * j);
+  __builtin_amdgcn_sched_barrier(0);
+  pf();
+  __builtin_amdgcn_sched_barrier(0);
+  if (wave < nr) {
+    float v[NC][8], mu, rs;
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[c][i] = (float)yv[c][i];
+    ln_stats_loaded<NC>(v, DM, dq.eps, lane, mu, rs);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int ch = lane + 64 * c;
+      if (ch < NCH) {
+        const float g[8] = {gv[c][0].x, gv[c][0].y, gv[c][0].z, gv[c][0].w,
+                            gv[c][1].x, gv[c][1].y, gv[c][1].z, gv[c][1].w};
+        const float b[8] = {bv[c][0].x, bv[c][0].y, bv[c][0].z, bv[c][0].w,
+                            bv[c][1].x, bv[c][1].y, bv[c][1].z, bv[c][1].w};
+        bf16x8 o;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = (bf16)ln_apply(v[c][i], mu, rs, g[i], b[i]);
+        *reinterpret_cast<bf16x8*>(&xs[wave][ch * 8]) = o;
+        if (store_x && dq.x_out) *reinterpret_cast<bf16x8*>(static_cast<bf16*>(dq.x_out) + (long)r * dq.ldx + ch * 8) = o;
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    if (g < nr && (SMER_DEC_QSKIP ? nkr[g] > 1 : true)) {  // block-uniform
+      float acc = 0.f;
+#pragma unroll
+      for (int j = 0; j < KT / 8; ++j) {
+        const bf16x8 xv = *reinterpret_cast<const bf16x8*>(&xs[g][part * KT + 8 * j]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc = fmaf((float)xv[i], (float)wv[j][i], acc);
+      }
+#pragma unroll
+      for (int w = 1; w < TPO; w <<= 1) acc += __shfl_xor(acc, w, 64);
+      if (part == 0) qs[g][d] = (float)(bf16)(acc + dq.bq[h * D + d]);
+    } else if (part == 0) {
+      qs[g][d] = 0.f;
+    }
+  }
+  __syncthreads();
+}
+
+template <int LPK, int UNR, int NW, bool PIPE, int QP, int G>
+__global__ __launch_bounds__(64 * NW) void attn_decode_shared_kernel(
+    int n_rows, const bf16* __restrict__ q, long ldq, const bf16* __restrict__ kc,
+    const bf16* __restrict__ vc, long row_stride, long req_stride, long head_stride,
+    const int32_t* __restrict__ row_req, const int32_t* __restrict__ row_nkeys,
+    const int32_t* __restrict__ group_tab, int n_groups, bf16* __restrict__ o, long ldo, float scale,
+    DecQ dq) {
+  constexpr int VEC = 8;
+  constexpr int GPW = 64 / LPK;  // key groups per wave
+  constexpr int KPB = NW * GPW;  // keys per block step
+  __shared__ float red_m[G][NW][LPK], red_l[G][NW][LPK], red_a[G][NW][LPK][VEC];
+  const int h = blockIdx.x, tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int sub = lane % LPK, grp = wave * GPW + lane / LPK;
+  // this block's chunk: walk the group table (block-uniform)
+  int c = blockIdx.y, first = 0, cnt = 0;
+  bool found = false;
+  for (int g = 0; g < n_groups && !found; ++g) {
+    first = group_tab[2 * g];
+    cnt = group_tab[2 * g + 1];
+    const int nch = cnt > 0 ? (cnt + G - 1) / G : 0;
+    if (c < nch) found = true;
+    else c -= nch;
+  }
+  if (!found || first < 0 || first > n_rows - cnt) return;
+  const int nr = min(G, cnt - c * G);  // rows of this chunk
+  const int n_odd = cnt >> 1;
+  int rows[G], nkr[G];
+  int nk = 0;  // the longest row of the chunk: the keys this block walks
+#pragma unroll
+  for (int i = 0; i < G; ++i) {
+    const int p = c * G + (i < nr ? i : 0);
+    rows[i] = p < n_odd ? first + 2 * p + 1 : first + 2 * (p - n_odd);
+    nkr[i] = i < nr ? row_nkeys[rows[i]] : 0;
+    nk = max(nk, nkr[i]);
+  }
+  const long base = (long)row_req[first] * req_stride + h * head_stride + sub * VEC;
+  float qv[G][VEC], m[G], l[G], acc[G][VEC];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    m[g] = -INFINITY;
+    l[g] = 0.f;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) acc[g][i] = 0.f;
+  }
+  auto load_step = [&](int j0, uint4 (&kr)[UNR], uint4 (&vr)[UNR]) {
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int j = j0 + u * KPB + grp;
+      const long off = base + (long)(j < nk ? j : 0) * row_stride;
+      if constexpr (NW == 8) {  // long memories: once-read per step, stream non-temporally
+        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 a = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kc + off));
+        const u32x4 b = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vc + off));
+        kr[u] = make_uint4(a.x, a.y, a.z, a.w);
+        vr[u] = make_uint4(b.x, b.y, b.z, b.w);
+      } else {
+        kr[u] = *reinterpret_cast<const uint4*>(kc + off);
+        vr[u] = *reinterpret_cast<const uint4*>(vc + off);
+      }
+    }
+  };
+  uint4 kr[UNR], vr[UNR];
+  constexpr bool early = QP > 0 && SMER_DEC_QLN_EARLY;
+  if constexpr (QP > 0) {
+    __shared__ float qs[G][LPK * VEC];
+    __shared__ __attribute__((aligned(16))) bf16 xs[G][QP];
+    dec_q_prologue_shared<LPK * VEC, 64 * NW, QP, G>(dq, h, rows, nkr, nr, tid, qs, xs, h == 0, [&] {
+      if constexpr (early) {
+        if (nk > 0) load_step(0, kr, vr);
+      }
+    });
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) qv[g][i] = qs[g][sub * VEC + i];
+  } else {
+#pragma unroll
+    for (int g = 0; g < G; ++g) load16b<bf16>(q + (long)rows[g] * ldq + h * (LPK * VEC) + sub * VEC, qv[g]);
+  }
+  if ((PIPE || QP == 0) && !early && nk > 0) load_step(0, kr, vr);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) qv[g][i] *= scale;
+  for (int j0 = 0; j0 < nk; j0 += KPB * UNR) {
+    uint4 kn[UNR], vn[UNR];
+    if constexpr (PIPE) {
+      if (j0 + KPB * UNR < nk) load_step(j0 + KPB * UNR, kn, vn);
+    } else {
+      if ((QP != 0 && !early) || j0 != 0) load_step(j0, kr, vr);
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+      if (j0 < nkr[g])  // block-uniform: a one-key row stops after the first step
+        dec_shared_row_step<LPK, UNR, KPB>(qv[g], kr, vr, j0, grp, nkr[g], m[g], l[g], acc[g]);
+    if constexpr (PIPE) {
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        kr[u] = kn[u];
+        vr[u] = vn[u];
+      }
+    }
+  }
+  // merge the groups of a wave (lanes with equal `sub`), per row
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    if (g < nr) {
+#pragma unroll
+      for (int w = LPK; w < 64; w <<= 1) {
+        const float mo = __shfl_xor(m[g], w, 64), lo = __shfl_xor(l[g], w, 64);
+        const float mn = fmaxf(m[g], mo);
+        const float c0 = m[g] == -INFINITY ? 0.f : __expf(m[g] - mn);
+        const float c1 = mo == -INFINITY ? 0.f : __expf(mo - mn);
+        l[g] = l[g] * c0 + lo * c1;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) acc[g][i] = acc[g][i] * c0 + __shfl_xor(acc[g][i], w, 64) * c1;
+        m[g] = mn;
+      }
+      if (lane < LPK) {
+        red_m[g][wave][lane] = m[g];
+        red_l[g][wave][lane] = l[g];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) red_a[g][wave][lane][i] = acc[g][i];
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < G * LPK) {
+    const int g = tid / LPK, t = tid % LPK;
+    if (g >= nr) return;
+    float mm = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) mm = fmaxf(mm, red_m[g][w][t]);
+    float ll = 0.f, out[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) out[i] = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const float c = red_m[g][w][t] == -INFINITY ? 0.f : __expf(red_m[g][w][t] - mm);
+      ll += red_l[g][w][t] * c;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) out[i] += red_a[g][w][t][i] * c;
+    }
+    const float inv = ll > 0.f ? 1.f / ll : 0.f;
+    // (rows[] indexed by a per-thread g: recomputed rather than a dynamic
+    // register-array index)
+    const int p = c * G + g;
+    const int r = p < n_odd ? first + 2 * p + 1 : first + 2 * (p - n_odd);
+    bf16* op = o + (long)r * ldo + h * (LPK * VEC) + t * VEC;
+    bf16x8 tv;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) tv[i] = (bf16)(out[i] * inv);
+    *reinterpret_cast<bf16x8*>(op) = tv;
+  }
+}
+
 template <typename T>
 __global__ void kv_scatter_kernel(int n_rows, int width, const T* __restrict__ src, long lds,
                                   T* __restrict__ cache, long row_stride, long req_stride,
@@ -2364,6 +2660,98 @@ extern "C" int smer_attn_decode(int dtype, int n_rows, int H, int D, const void*
   else
     return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_attn_decode: dtype");
   SMER_CHECK_LAUNCH("smer_attn_decode");
+  return SMER_OK;
+}
+
+// Decode cross attention over shared memories (attn_decode_shared_kernel):
+// the variant by cache capacity exactly as smer_attn_decode / _qln choose
+// theirs, so each row's bits are those entries'.  Grid: every group has at
+// most one partial chunk, so n_rows / G + n_groups chunks bound any split.
+static bool dec_shared_args_ok(int n_rows, int n_groups, const int32_t* group_tab) {
+  return n_rows >= 0 && n_groups >= 0 && (n_groups == 0 || group_tab);
+}
+
+extern "C" int smer_attn_decode_shared(int dtype, int n_rows, int H, int D, const void* q, long ldq,
+                                       const void* kcache, const void* vcache, long row_stride,
+                                       long req_stride, long head_stride, const int32_t* row_req,
+                                       const int32_t* row_nkeys, const int32_t* group_tab, int n_groups,
+                                       void* o, long ldo, float scale, smer_stream_t stream) {
+  if (dtype != SMER_BF16) return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_attn_decode_shared: bf16 only");
+  SMER_REQUIRE((D == 32 || D == 64) && H > 0, "smer_attn_decode_shared: head dim 32 or 64");
+  SMER_REQUIRE(dec_shared_args_ok(n_rows, n_groups, group_tab), "smer_attn_decode_shared: group table");
+  if (n_rows == 0 || n_groups == 0) return SMER_OK;
+  SMER_REQUIRE(q && kcache && vcache && o && row_req && row_nkeys, "smer_attn_decode_shared: null pointer");
+  if (head_stride <= 0) head_stride = D;
+  auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
+  SMER_REQUIRE(al(q) && al(kcache) && al(vcache) && al(o) && ldq % 8 == 0 && ldo % 8 == 0 &&
+                   row_stride % 8 == 0 && req_stride % 8 == 0 && head_stride % 8 == 0,
+               "smer_attn_decode_shared: 16-B alignment / strides");
+  hipStream_t s = (hipStream_t)stream;
+  constexpr int G = DEC_SHARED_G;
+  dim3 grid(H, n_rows / G + n_groups);
+  const long cap_rows = head_stride != D ? head_stride / (row_stride > 0 ? row_stride : 1)
+                                         : req_stride / (row_stride > 0 ? row_stride : 1);
+  const bool big = cap_rows >= 512;
+  const bool pipe = cap_rows >= 2048 || (big && (long)n_rows * H <= 128 && smer_dec_pipe_small());
+#define SMER_DEC_SH(L, U, W, P)                                                                      \
+  hipLaunchKernelGGL((attn_decode_shared_kernel<L, U, W, P, 0, G>), grid, dim3(64 * W), 0, s, n_rows, \
+                     (const bf16*)q, ldq, (const bf16*)kcache, (const bf16*)vcache, row_stride,      \
+                     req_stride, head_stride, row_req, row_nkeys, group_tab, n_groups, (bf16*)o, ldo, \
+                     scale, DecQ{})
+  if (D == 32) {
+    if (pipe) SMER_DEC_SH(4, 4, 8, true); else if (big) SMER_DEC_SH(4, 4, 8, false); else SMER_DEC_SH(4, 2, 4, false);
+  } else {
+    if (pipe) SMER_DEC_SH(8, 4, 8, true); else if (big) SMER_DEC_SH(8, 4, 8, false); else SMER_DEC_SH(8, 2, 4, false);
+  }
+#undef SMER_DEC_SH
+  SMER_CHECK_LAUNCH("smer_attn_decode_shared");
+  return SMER_OK;
+}
+
+extern "C" int smer_attn_decode_shared_qln(int n_rows, int H, int D, const void* y, long ldy,
+                                           const float* gamma, const float* beta, float eps,
+                                           const void* wq, long ldw, const float* bq, void* x_out,
+                                           long ldx, int dmodel, const void* kcache, const void* vcache,
+                                           long row_stride, long req_stride, long head_stride,
+                                           const int32_t* row_req, const int32_t* row_nkeys,
+                                           const int32_t* group_tab, int n_groups, void* o, long ldo,
+                                           float scale, smer_stream_t stream) {
+  SMER_REQUIRE(D == 64 && H > 0, "smer_attn_decode_shared_qln: head dim 64");
+  SMER_REQUIRE(dmodel == 512 || dmodel == 768 || dmodel == 1024,
+               "smer_attn_decode_shared_qln: d_model 512 / 768 / 1024 (else: Linear + smer_attn_decode_shared)");
+  SMER_REQUIRE(dec_shared_args_ok(n_rows, n_groups, group_tab), "smer_attn_decode_shared_qln: group table");
+  if (n_rows == 0 || n_groups == 0) return SMER_OK;
+  SMER_REQUIRE(y && gamma && beta && wq && bq && kcache && vcache && o && row_req && row_nkeys,
+               "smer_attn_decode_shared_qln: null pointer");
+  if (head_stride <= 0) head_stride = D;
+  auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
+  SMER_REQUIRE(al(y) && al(gamma) && al(beta) && al(wq) && al(kcache) && al(vcache) && al(o) &&
+                   (!x_out || al(x_out)) && ldy % 8 == 0 && ldw % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0 &&
+                   row_stride % 8 == 0 && req_stride % 8 == 0 && head_stride % 8 == 0,
+               "smer_attn_decode_shared_qln: 16-B alignment / strides");
+  DecQ dq{y, ldy, gamma, beta, eps, wq, ldw, bq, x_out, ldx, dmodel};
+  hipStream_t s = (hipStream_t)stream;
+  constexpr int G = DEC_SHARED_G;
+  dim3 grid(H, n_rows / G + n_groups);
+  const long cap_rows = head_stride != D ? head_stride / (row_stride > 0 ? row_stride : 1)
+                                         : req_stride / (row_stride > 0 ? row_stride : 1);
+  const bool pipe = cap_rows >= 2048;
+#define SMER_DEC_SHQ(P, DM)                                                                          \
+  hipLaunchKernelGGL((attn_decode_shared_kernel<8, 4, 8, P, DM, G>), grid, dim3(512), 0, s, n_rows,  \
+                     (const bf16*)nullptr, 0L, (const bf16*)kcache, (const bf16*)vcache, row_stride, \
+                     req_stride, head_stride, row_req, row_nkeys, group_tab, n_groups, (bf16*)o, ldo, \
+                     scale, dq)
+  if (pipe) {
+    if (dmodel == 512) SMER_DEC_SHQ(true, 512);
+    else if (dmodel == 768) SMER_DEC_SHQ(true, 768);
+    else SMER_DEC_SHQ(true, 1024);
+  } else {
+    if (dmodel == 512) SMER_DEC_SHQ(false, 512);
+    else if (dmodel == 768) SMER_DEC_SHQ(false, 768);
+    else SMER_DEC_SHQ(false, 1024);
+  }
+#undef SMER_DEC_SHQ
+  SMER_CHECK_LAUNCH("smer_attn_decode_shared_qln");
   return SMER_OK;
 }
 

@@ -51,7 +51,8 @@ def _capture(stream, fn):
 
 
 class DecodeSession:
-    def __init__(self, model, max_requests, max_src, max_tgt, precision=None, use_graph=True):
+    def __init__(self, model, max_requests, max_src, max_tgt, precision=None, use_graph=True,
+                 max_sources=None):
         if precision is not None:
             model.set_precision(precision)
         self.model = model
@@ -63,6 +64,12 @@ class DecodeSession:
             raise RuntimeError("DecodeSession needs the model on a ROCm GPU")
         self.dev = dev
         self.R, self.Smax = int(max_requests), int(max_src)
+        # encoded sources are slots of their own: several request slots (the
+        # takes of one request) may be bound to one source slot and then share
+        # its cross-attention memory.  Default: one source slot per request.
+        self.NS = self.R if max_sources is None else int(max_sources)
+        if not 1 <= self.NS <= self.R:
+            raise ValueError("max_sources must be in 1..max_requests")
         self.Tmax = int(max_tgt) + 1  # + trash slot
         d = eng.d
         self.d = d
@@ -70,10 +77,10 @@ class DecodeSession:
             model.pos_enc.extend(max(self.Smax, self.Tmax))
         self.self_kv = [torch.zeros(self.R, self.Tmax, 2 * d, dtype=self.dt, device=dev)
                         for _ in range(eng.n_dec)]
-        # cross-attention memory, head-major [R, K|V, H, Smax, D]: each
-        # (request, head) streams one contiguous key run per decode step
+        # cross-attention memory, head-major [sources, K|V, H, Smax, D]: each
+        # (source, head) is one contiguous key run per decode step
         H, D = eng.H, eng.D
-        self.cross_kv = [torch.zeros(self.R, 2, H, self.Smax, D, dtype=self.dt, device=dev)
+        self.cross_kv = [torch.zeros(self.NS, 2, H, self.Smax, D, dtype=self.dt, device=dev)
                          for _ in range(eng.n_dec)]
         self.src_len = np.zeros(self.R, dtype=np.int64)
         self.W = eng.weights(self.dt)
@@ -82,6 +89,16 @@ class DecodeSession:
         self.M = M
         self.ids_t = torch.zeros(M, dtype=torch.int64, device=dev)
         self.meta_t = torch.zeros(4, M, dtype=torch.int32, device=dev)
+        # the request-to-source binding, device data written at prefill and
+        # read by the cross attention of the captured step (never baked into
+        # a graph, and outside meta_t, which the grammar kernels rewrite every
+        # step): src_t[row] = source slot of the row's request; grp_t[g] =
+        # (first row, row count) of the g-th run of requests on one source
+        self.req_src = np.minimum(np.arange(self.R), self.NS - 1).astype(np.int32)
+        self.src_t = torch.zeros(M, dtype=torch.int32, device=dev)
+        self.grp_t = torch.zeros(self.NS, 2, dtype=torch.int32, device=dev)
+        self.prefill_rows = 0
+        self._bind()
         self.ids_h = torch.zeros(M, dtype=torch.int64).pin_memory()
         self.meta_h = torch.zeros(4, M, dtype=torch.int32).pin_memory()
         self.logits_h = torch.zeros(M, eng.V, dtype=torch.float32).pin_memory()
@@ -109,8 +126,60 @@ class DecodeSession:
         self.graph = None
 
     # ------------------------------------------------------------------
+    def _bind(self):
+        """Write the request-to-source binding (self.req_src) to the device:
+        the per-row source index and the group table (ordinary copies)."""
+        runs = []
+        for r, s in enumerate(self.req_src.tolist()):
+            if runs and runs[-1][0] == s:
+                runs[-1][2] += 1
+            else:
+                runs.append([s, r, 1])
+        if len(runs) > self.NS or len({s for s, _, _ in runs}) != len(runs):
+            raise ValueError("the request slots of a source must be consecutive")
+        tab = np.zeros((self.NS, 2), dtype=np.int32)
+        for g, (_, r0, n) in enumerate(runs):
+            tab[g] = (2 * r0, 2 * n)
+        self.src_t.copy_(torch.from_numpy(np.repeat(self.req_src, 2)))
+        self.grp_t.copy_(torch.from_numpy(tab))
+
     def prefill(self, slots, srcs):
-        """Encode `srcs` (list of 1-D int arrays) into request `slots`."""
+        """Encode `srcs` (list of 1-D int arrays) into request `slots`:
+        request slot s is bound to source slot s."""
+        slots = [int(s) for s in slots]
+        if slots and max(slots) >= self.NS:
+            raise ValueError("request slot %d has no source slot of its own (max_sources %d)"
+                             % (max(slots), self.NS))
+        lens = self._encode(slots, srcs)
+        for b, s in enumerate(slots):
+            self.req_src[s] = s
+            self.src_len[s] = lens[b]
+        self._bind()
+
+    def prefill_takes(self, srcs, takes):
+        """Encode srcs[i] ONCE into source slot i and bind takes[i]
+        consecutive request slots to it (request slots 0, 1, .. in order):
+        the takes of one source share its cross-attention memory.  Slots past
+        sum(takes) stay bound to the last source (they are never live)."""
+        takes = [int(n) for n in takes]
+        if len(takes) != len(srcs) or any(n < 1 for n in takes):
+            raise ValueError("prefill_takes: one take count >= 1 per source")
+        if len(srcs) > self.NS or sum(takes) > self.R:
+            raise ValueError("prefill_takes: %d sources / %d takes exceed the session (%d / %d)"
+                             % (len(srcs), sum(takes), self.NS, self.R))
+        lens = self._encode(list(range(len(srcs))), srcs)
+        r = 0
+        for i, n in enumerate(takes):
+            self.req_src[r:r + n] = i
+            self.src_len[r:r + n] = lens[i]
+            r += n
+        self.req_src[r:] = len(srcs) - 1
+        self._bind()
+
+    def _encode(self, slots, srcs):
+        """Run the encoder over `srcs` and scatter every decoder layer's
+        cross-attention K / V of the memories into source `slots`.  Returns
+        the source lengths."""
         eng, W, dt, dev, d = self.eng, self.W, self.dt, self.dev, self.d
         H, D = eng.H, eng.D
         B = len(slots)
@@ -153,8 +222,8 @@ class DecodeSession:
             ops.kv_scatter_heads(kvc, self.cross_kv[li], req_t, pos_t, H=H, D=D,
                                  req_stride=2 * H * self.Smax * D, kv_stride=H * self.Smax * D,
                                  head_stride=self.Smax * D)
-        for b, s in enumerate(slots):
-            self.src_len[s] = lens[b]
+        self.prefill_rows = B * S
+        return lens
 
     # ------------------------------------------------------------------
     def _run(self):
@@ -162,6 +231,7 @@ class DecodeSession:
         eng, W, dt, dev, d = self.eng, self.W, self.dt, self.dev, self.d
         H, D, M = eng.H, eng.D, self.M
         pos_t, req_t, nks_t, nkc_t = self.meta_t[0], self.meta_t[1], self.meta_t[2], self.meta_t[3]
+        src_t = self.src_t  # cross attention: the row's SOURCE slot
         pe = self.model.pos_enc.pe
         pe2 = pe.view(pe.shape[0], pe.shape[2])
         x = torch.empty(M, d, dtype=dt, device=dev)
@@ -211,7 +281,7 @@ class DecodeSession:
             qc = ops.linear(x1, L.cq_w, L.cq_b)
             cc = self.cross_kv[li]
             oc = torch.empty(M, d, dtype=dt, device=dev)
-            ops.attn_decode(qc, cc, cc.view(-1)[H * self.Smax * D:], req_t, nkc_t, oc, H=H, D=D,
+            ops.attn_decode(qc, cc, cc.view(-1)[H * self.Smax * D:], src_t, nkc_t, oc, H=H, D=D,
                             row_stride=D, req_stride=cstride, head_stride=self.Smax * D,
                             scale=scale)
             y2 = ops.linear(oc, L.ca_ow, L.ca_ob, residual=x1)
@@ -258,6 +328,22 @@ class DecodeSession:
         # the batch (a request's tokens may not depend on its batch-mates):
         # on whenever the shape allows it.
         self._qln = D == 64 and d in (512, 768, 1024) and os.environ.get("SMER_DECODE_QLN", "1") == "1"
+        # cross attention reads the row's SOURCE slot: takes that share a
+        # source share one prefill and one memory, and the per-row kernels
+        # read it through the indirection.  SMER_DECODE_SHARED=1 (fewer
+        # sources than requests): the grouped kernels instead, which load
+        # each K / V key step once per chunk of a group's rows and write the
+        # per-row kernels' bits.  Off by default: measured slower (C2 shapes,
+        # 4 sources x 8 takes: 426 vs 289 us per replayed step,
+        # tools/variations_probe.py) -- the repeated reads of the
+        # per-row blocks hit in the caches, and the grouped form leaves 64
+        # walking blocks for 256 CUs.  (Never for a half of the rows, whose
+        # group table would be another one.)
+        src_t = self.src_t[r0:r1]
+        shared = (self.NS < self.R and D in (32, 64) and (r0, r1) == (0, self.M)
+                  and os.environ.get("SMER_DECODE_SHARED", "0") == "1")
+        self._shared = shared
+        ckw = dict(H=H, D=D, row_stride=D, req_stride=cstride, head_stride=self.Smax * D, scale=scale)
         y_prev = n_prev = None
         for li, L in enumerate(W.dec):
             cache = self.self_kv[li]
@@ -275,16 +361,20 @@ class DecodeSession:
             x1 = torch.empty(M, d, dtype=dt, device=dev)
             cc = self.cross_kv[li]
             oc = torch.empty(M, d, dtype=dt, device=dev)
+            vc = cc.view(-1)[H * self.Smax * D:]
             if self._qln:  # LN1 + cross Q inside the cross-attention blocks
-                ops.attn_decode_qln(y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b, cc,
-                                    cc.view(-1)[H * self.Smax * D:], req_t, nkc_t, oc, H=H, D=D,
-                                    row_stride=D, req_stride=cstride, head_stride=self.Smax * D,
-                                    scale=scale, x_out=x1)
+                if shared:
+                    ops.attn_decode_shared_qln(y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b, cc, vc, src_t, nkc_t,
+                                               self.grp_t, oc, x_out=x1, **ckw)
+                else:
+                    ops.attn_decode_qln(y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b, cc, vc, src_t, nkc_t, oc,
+                                        x_out=x1, **ckw)
             else:
                 qc = ops.linear_decode_ln(y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b, x_out=x1)
-                ops.attn_decode(qc, cc, cc.view(-1)[H * self.Smax * D:], req_t, nkc_t, oc, H=H, D=D,
-                                row_stride=D, req_stride=cstride, head_stride=self.Smax * D,
-                                scale=scale)
+                if shared:
+                    ops.attn_decode_shared(qc, cc, vc, src_t, nkc_t, self.grp_t, oc, **ckw)
+                else:
+                    ops.attn_decode(qc, cc, vc, src_t, nkc_t, oc, **ckw)
             y2 = ops.linear(oc, L.ca_ow, L.ca_ob, residual=x1)
             x2 = torch.empty(M, d, dtype=dt, device=dev)
             h = ops.linear_decode_ln(y2, L.n2[0], L.n2[1], L.l1_w, L.l1_b, relu=True, x_out=x2)
@@ -314,6 +404,10 @@ class DecodeSession:
         # layer; each block re-reads its head's 128 KB of Wq from L2, so not
         # for many rows)
         qln = self._split_f32 and d == 512 and M <= 4 and os.environ.get("SMER_DECODE_QLN_F32", "1") == "1"
+        # (fp32 has no grouped cross-attention kernel: takes that share a
+        # source run these kernels on the source's slot -- one prefill and one
+        # cache, the loads not shared)
+        src_t = self.src_t
         y_prev = n_prev = None
         for li, L in enumerate(W.dec):
             cache = self.self_kv[li]
@@ -335,21 +429,21 @@ class DecodeSession:
             if qln:
                 part = torch.empty(M, H, ops.DEC_SPLITS, 68, device=dev)
                 ops.attn_decode_split_qln_f32(y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b, cc,
-                                              cc.view(-1)[H * self.Smax * D:], req_t, nkc_t, part, H=H, D=D,
+                                              cc.view(-1)[H * self.Smax * D:], src_t, nkc_t, part, H=H, D=D,
                                               row_stride=D, req_stride=cstride, head_stride=self.Smax * D,
                                               scale=scale, x_out=x1)
                 y2 = ops.linear_decode_merge_f32(part, L.ca_ow, L.ca_ob, M=M, residual=x1)
             elif self._split_f32:  # 8 key slices per (row, head), merged by the out-projection
                 qc = ops.linear_decode_ln(y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b, x_out=x1)
                 part = torch.empty(M, H, ops.DEC_SPLITS, 68, device=dev)
-                ops.attn_decode_split_f32(qc, cc, cc.view(-1)[H * self.Smax * D:], req_t, nkc_t, part, H=H,
+                ops.attn_decode_split_f32(qc, cc, cc.view(-1)[H * self.Smax * D:], src_t, nkc_t, part, H=H,
                                           D=D, row_stride=D, req_stride=cstride, head_stride=self.Smax * D,
                                           scale=scale)
                 y2 = ops.linear_decode_merge_f32(part, L.ca_ow, L.ca_ob, M=M, residual=x1)
             else:
                 qc = ops.linear_decode_ln(y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b, x_out=x1)
                 oc = torch.empty(M, d, dtype=dt, device=dev)
-                ops.attn_decode(qc, cc, cc.view(-1)[H * self.Smax * D:], req_t, nkc_t, oc, H=H, D=D,
+                ops.attn_decode(qc, cc, cc.view(-1)[H * self.Smax * D:], src_t, nkc_t, oc, H=H, D=D,
                                 row_stride=D, req_stride=cstride, head_stride=self.Smax * D, scale=scale)
                 y2 = ops.linear(oc, L.ca_ow, L.ca_ob, residual=x1)
             x2 = torch.empty(M, d, dtype=dt, device=dev)

@@ -180,6 +180,23 @@ def _check_tp(t, p, n=None):
     return out[0] if n is None else out
 
 
+def _check_variations(variations, n=None):
+    """Validated take counts of a call: an int >= 1 (n None: the plugin call,
+    returns it), or with n requests an int or one int per request (returns
+    the list).  Raises ValueError; touches neither the model nor np.random."""
+    def one(x):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or x < 1:
+            raise ValueError("variations must be an int >= 1 (got %r)" % (x,))
+        return int(x)
+    if isinstance(variations, (list, tuple, np.ndarray)):
+        if n is None:
+            raise ValueError("variations is one int here")
+        if len(variations) != n:
+            raise ValueError("variations: one int, or one per request (%d)" % n)
+        return [one(x) for x in variations]
+    return one(variations) if n is None else [one(variations)] * n
+
+
 def gen_nopeek_mask(length):
     m = (torch.triu(torch.ones(length, length)) == 1).transpose(0, 1)
     return m.float().masked_fill(m == 0, float("-inf")).masked_fill(m == 1, 0.0)
@@ -460,7 +477,7 @@ class _Precision:
 
 def generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
                    bars_to_generate, *, greedy=False, use_kv_cache=True, stats=None,
-                   precision="fp32", warm=True, device_grammar=True, t=1.0, p=None):
+                   precision="fp32", warm=True, device_grammar=True, t=1.0, p=None, variations=None):
     """`generation.py:468-696`.  Returns (restored '<U9' tokens,
     mask_track_names, mask_bar_names) or None (nothing masked / on error,
     after printing it, as the reference does).  `stats` (a dict, opt-in)
@@ -488,8 +505,31 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
     Every path -- device, host loop, use_kv_cache=False -- draws from the same
     distribution on the same stream.  A t that is not finite and > 0, or a p
     that is neither None nor finite and >= 0, raises ValueError before
-    anything is drawn."""
+    anything is drawn.
+    variations: an int n >= 1 returns a LIST of n results, n takes of the
+    request decoded in lockstep on one session whose n request slots share
+    ONE encoded source (one prefill, one cross-attention memory): exactly
+    generation_batch([request] * n, greedy=greedy, precision=precision) on
+    the same np.random stream.  None (default) is the single result.  The
+    print-and-return-None on error holds for the call as a whole (KV-cached
+    path only; anything else than an int >= 1 raises ValueError)."""
     t, p = _check_tp(t, p)
+    if variations is not None:
+        n = _check_variations(variations)
+        if not use_kv_cache:
+            raise ValueError("variations needs the KV-cached path (use_kv_cache=True)")
+        with _Precision(model, precision):
+            try:
+                out, st = generation_batch(model, [(events, tracks_to_generate, bars_to_generate)],
+                                           vocab, all_controls, greedy=greedy, logger=logger,
+                                           return_stats=True, device_grammar=device_grammar, warm=warm,
+                                           t=t, p=p, variations=[n])
+                if stats is not None:
+                    stats["steps"] = st["steps"]
+                return out[0]
+            except Exception as e:  # reference behaviour (generation.py:695-696)
+                print(e)
+                return None
     with _Precision(model, precision):
         return _generation_all(model, events, device, vocab, logger, all_controls,
                                tracks_to_generate, bars_to_generate, greedy, use_kv_cache, stats,
@@ -589,8 +629,8 @@ def _generation_all(model, events, device, vocab, logger, all_controls, tracks_t
 infill = generation_all
 
 
-# Warm decode sessions of generation_batch, one per (model, precision, R),
-# at most two kept: the KV caches, step buffers and the captured step +
+# Warm decode sessions of generation_batch, one per (model, precision, R,
+# source count), at most two kept: the KV caches, step buffers and the captured step +
 # grammar graph persist across calls (a serving process keeps them; capturing
 # costs ~10 ms at C2).  A cached session is reused when the call's sources and
 # prefix fit AND its cache capacities fall in the same decode-attention
@@ -628,7 +668,7 @@ def _plugin_capacity(Smax, Tmax):
     return S, T
 
 
-def _batch_session(model, R, Smax, Tmax, precision, exact_tmax=False, warm=True):
+def _batch_session(model, R, Smax, Tmax, precision, exact_tmax=False, warm=True, sources=None):
     """A decode session for this call.  A cached one is reused only when it
     still addresses the model's current weight buffers (moving the model
     re-flattens them) and, for an explicit max_tgt, has exactly that
@@ -639,11 +679,12 @@ def _batch_session(model, R, Smax, Tmax, precision, exact_tmax=False, warm=True)
     last call), so prefill and the captured step read current weights."""
     if precision is not None:
         model.set_precision(precision)
+    NS = R if sources is None else int(sources)
     if not warm:
-        return DecodeSession(model, R, Smax, Tmax)
+        return DecodeSession(model, R, Smax, Tmax, max_sources=NS)
     if R == 1 and not exact_tmax:
         Smax, Tmax = _plugin_capacity(Smax, Tmax)
-    key = (id(model), model.precision, R)
+    key = (id(model), model.precision, R, NS)
     s = _BATCH_SESSIONS.get(key)
     fits = (s is not None and s.model is model and s.Smax >= Smax and s.Tmax >= Tmax + 1
             and (s.Tmax == Tmax + 1 or not exact_tmax)
@@ -654,7 +695,7 @@ def _batch_session(model, R, Smax, Tmax, precision, exact_tmax=False, warm=True)
             s.W = W
             s.src_len[:] = 0
             return s
-    s = DecodeSession(model, R, Smax, Tmax)
+    s = DecodeSession(model, R, Smax, Tmax, max_sources=NS)
     _BATCH_SESSIONS.pop(key, None)
     while len(_BATCH_SESSIONS) >= 2:
         _BATCH_SESSIONS.pop(next(iter(_BATCH_SESSIONS)))
@@ -664,7 +705,7 @@ def _batch_session(model, R, Smax, Tmax, precision, exact_tmax=False, warm=True)
 
 def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logger=None,
                      max_tgt=None, precision=None, return_stats=False, device_grammar=True,
-                     warm=True, t=1.0, p=None):
+                     warm=True, t=1.0, p=None, variations=None):
     """Decode many infill requests in lockstep on one KV-cached session.
 
     requests: list of (events, tracks_to_generate, bars_to_generate).
@@ -683,26 +724,46 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
     warm: reuse (and keep) this model's cached decode session, as a serving
     process would; False builds a private session freed after the call
     (see also clear_decode_sessions).
+    variations: None, or the number of takes per request (an int, or one
+    int per request; t and p apply to all takes of a request).  The call
+    then behaves exactly like this call on the list in which request i
+    appears variations[i] times in a row -- same session sizes, tokens, redraw
+    log lines, np.random state, 'tokens' and 'steps' -- but every request is
+    encoded ONCE and its takes share one cross-attention memory
+    (DecodeSession.prefill_takes), and entry i of the result is the list of
+    its takes' results (None where nothing was masked).
     Returns a list of (restored, mask_track_names, mask_bar_names) (None
-    where nothing was masked), and optionally {'tokens', 'steps'}."""
+    where nothing was masked), and optionally {'tokens', 'steps', 'sources',
+    'prefill_rows', ..}."""
     t0 = time.perf_counter()
     tps = _check_tp(t, p, len(requests))
+    takes = None if variations is None else _check_variations(variations, len(requests))
     preps = [_prepare(list(ev), vocab, tr, br) for ev, tr, br in requests]
+    srcs = [q[0] for q in preps]
+    if takes is not None:  # the expanded list: take k of request i is a request of its own
+        preps = [q for q, n in zip(preps, takes) for _ in range(n)]
+        tps = [x for x, n in zip(tps, takes) for _ in range(n)]
 
     def fresh_spans():
         return [_Span(vocab, q[0], q[3], all_controls, q[4], greedy, logger, a, b)
                 for q, (a, b) in zip(preps, tps)]
     spans = fresh_spans()
-    R = len(requests)
+    R = len(preps)
     Smax = max(len(q[0]) for q in preps)
     Tmax = max_tgt or max(128, 100 * max(s.n_masks for s in spans) + 8)
     model.eval()
     tokens = steps = 0
     with torch.no_grad():
         sess = _batch_session(model, R, Smax, Tmax, precision, exact_tmax=max_tgt is not None,
-                              warm=warm)
+                              warm=warm, sources=len(srcs))
+
+        def prefill():
+            if takes is None:
+                sess.prefill(list(range(R)), srcs)
+            else:
+                sess.prefill_takes(srcs, takes)
         t1 = time.perf_counter()
-        sess.prefill(list(range(R)), [q[0] for q in preps])
+        prefill()
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         t_dev = 0.0
@@ -723,8 +784,13 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                 raise ValueError("decoder prefix exceeds session max_tgt %d" % (sess.Tmax - 1))
             # key rows the decode steps attended to (SURVEY §8d infill bytes):
             # request r's i-th step reads its S_r memory rows and i+1 prefix rows
-            kv_reads = int(sum(len(q) * len(pr[0]) + len(q) * (len(q) + 1) // 2
-                               for q, pr in zip(seqs, preps)))
+            # (a memory shared by several takes is read once per step in
+            # which one of them is live)
+            kv_reads = int(sum(len(q) * (len(q) + 1) // 2 for q in seqs))
+            k0 = 0
+            for src, n in zip(srcs, takes or [1] * R):
+                kv_reads += max(len(q) for q in seqs[k0:k0 + n]) * len(src)
+                k0 += n
             for sp, seq in zip(spans, seqs):
                 if logger is None:  # no redraw report to log: commit only
                     sp.commit_all(seq)
@@ -749,7 +815,7 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                 # and the whole batch goes through the host loop below
                 np.random.set_state(rng0)
                 spans = fresh_spans()
-                sess.prefill(list(range(R)), [q[0] for q in preps])
+                prefill()
                 t_dev = 0.0
             else:
                 if np.any(err & 1):
@@ -798,11 +864,18 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
             out.append(None)
             continue
         out.append((restore_marked_input(_src_tokens(vocab, q[0]), st.total), q[1], q[2]))
+    if takes is not None:  # entry i: the list of request i's takes
+        nested, k0 = [], 0
+        for n in takes:
+            nested.append(None if out[k0] is None else out[k0:k0 + n])
+            k0 += n
+        out = nested
     if return_stats:
         t3 = time.perf_counter()
         return out, {"tokens": tokens, "steps": steps, "prepare_s": t1 - t0,
                      "prefill_s": t2 - t1, "decode_s": t3 - t2, "step_call_s": t_dev,
                      "request_latency_s": latency, "kv_row_reads": kv_reads,
                      "generated": [list(st.total) for st in spans],
+                     "sources": len(srcs), "prefill_rows": int(sess.prefill_rows),
                      "decode_phases_s": dict(getattr(sess, "phase_s", {}))}
     return out

@@ -336,6 +336,37 @@ def attn_decode_qln(y, gamma, beta, wq, bq, kcache, vcache, row_req, row_nkeys, 
          _p(row_nkeys), _p(out), _ld(out), float(scale), _stream())
 
 
+DEC_SHARED_G = 4  # rows per block of the shared decode attention (csrc DEC_SHARED_G)
+
+
+def attn_decode_shared(q, kcache, vcache, row_req, row_nkeys, group_tab, out, *, H, D, row_stride,
+                       req_stride, scale, head_stride=0):
+    """attn_decode over shared memories: group_tab int32 [n_groups, 2] =
+    (first row, row count), the rows of a group attending the memory of
+    request slot row_req[first row]; each K / V key step is loaded once per
+    chunk of a group's rows.  bf16; the per-row entry's bits."""
+    call("smer_attn_decode_shared", dtype_code(q.dtype), q.shape[0], H, D, _p(q), _ld(q), _p(kcache),
+         _p(vcache), int(row_stride), int(req_stride), int(head_stride), _p(row_req),
+         _p(row_nkeys), _p(group_tab), _n_groups(group_tab), _p(out), _ld(out), float(scale), _stream())
+
+
+def attn_decode_shared_qln(y, gamma, beta, wq, bq, kcache, vcache, row_req, row_nkeys, group_tab, out,
+                           *, H, D, row_stride, req_stride, scale, head_stride=0, x_out=None, eps=1e-5):
+    """attn_decode_qln over shared memories (see attn_decode_shared)."""
+    M, dm = y.shape
+    call("smer_attn_decode_shared_qln", M, H, D, _p(y), _ld(y), _p(gamma), _p(beta), float(eps),
+         _p(wq), _ld(wq), _p(bq), _p(x_out), _ld(x_out) if x_out is not None else 0, dm, _p(kcache),
+         _p(vcache), int(row_stride), int(req_stride), int(head_stride), _p(row_req),
+         _p(row_nkeys), _p(group_tab), _n_groups(group_tab), _p(out), _ld(out), float(scale), _stream())
+
+
+def _n_groups(group_tab):
+    if (group_tab.dtype != torch.int32 or group_tab.dim() != 2 or group_tab.shape[1] != 2
+            or not group_tab.is_contiguous()):
+        raise RuntimeError("smer op: group_tab must be a contiguous int32 [n_groups, 2] tensor")
+    return group_tab.shape[0]
+
+
 DEC_SPLITS = 8  # key slices of attn_decode_split_f32 (csrc DEC_NS)
 
 
