@@ -40,6 +40,9 @@
  *   smer_grammar_sample_step_tp  the same with a temperature and a nucleus
  *                        threshold per request, read from device memory
  *                        (generation.py:11-30, 41-95: sampling(p, t))
+ *   smer_grammar_sample_step_rows  the same on one MT19937 stream per
+ *                        request (a seed per request), the requests in
+ *                        parallel
  *   smer_layernorm_*     residual LayerNorm, eps 1e-5 (transformer.py:392,395,
  *                        462,466,469; final norms 274-275, 329-330)
  *   smer_embed_*         embedding gather x sqrt(d) + sinusoidal PE + dropout
@@ -382,6 +385,29 @@ int smer_grammar_sample_step_tp(int R, int V, const float* logits, long ldl, int
                                 int trash_pos, int max_span, const int32_t* src_len, int64_t* ids,
                                 int32_t* meta, int32_t* out_tok, int cap, uint32_t* mt, int32_t* ctl,
                                 int32_t* ring, int ring_n, const double* tp, smer_stream_t stream);
+/* smer_grammar_sample_step_tp on one MT19937 stream per request instead of
+ * the one shared stream (not a reference operation: the reference draws every
+ * request from np.random; a request seeded s draws what
+ * np.random.RandomState(s) would give it, generation.py:11-95).  mt: uint32,
+ * request r's 624 key words and position at mt + r * ldmt, ldmt >= 625 (a
+ * freshly seeded RandomState has position 624); each row is updated in place.
+ * tp may be NULL: {1.0, None} for every request.  A request's ids, state row,
+ * feed rows and stream are what smer_grammar_sample_step_tp with R = 1 gives
+ * for that request alone, so nothing orders the draws across requests and the
+ * step runs one block per request.  A request with `done` set keeps its
+ * stream untouched and writes no ids or meta.  Live count: ring == NULL:
+ * ctl[0], zeroed on the stream by this call and added to by every live
+ * request; else ctl int32 [3] {live count, tickets, step} zeroed once by the
+ * caller and the count lands in ring[step % ring_n], exactly as
+ * smer_grammar_greedy_step / _ring.  V <= 512.  Status return, no allocation,
+ * no synchronisation. */
+int smer_grammar_sample_step_rows(int R, int V, const float* logits, long ldl, int32_t* state, int nst,
+                                  const int8_t* targets, int max_masks, const uint8_t* keep,
+                                  const uint8_t* reject, const uint8_t* cls, int eos, int m0,
+                                  int trash_pos, int max_span, const int32_t* src_len, int64_t* ids,
+                                  int32_t* meta, int32_t* out_tok, int cap, uint32_t* mt, long ldmt,
+                                  int32_t* ctl, int32_t* ring, int ring_n, const double* tp,
+                                  smer_stream_t stream);
 
 int smer_layernorm_fwd(int dtype, int M, int N, const void* x, long ldx,
                        const float* gamma, const float* beta, float eps,

@@ -18,6 +18,8 @@
 // all requests in parallel).  The number of requests still live after the
 // step is counted into *alive, which the kernel's caller zeroes first
 // (smer_grammar_greedy_step issues the memset on the same stream).
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -545,7 +547,7 @@ __device__ __forceinline__ uint32_t f32_ord(float f) {
 #ifndef SMER_SAMPLE_STAMPS
 #define SMER_SAMPLE_STAMPS 0  // tools/build_variant.sh ... -DSMER_SAMPLE_STAMPS=1: phase clocks in mt[640..]
 #endif
-#define SSTAMP(k) do { if (SMER_SAMPLE_STAMPS && lane == 0) mt[640 + (k)] = (uint32_t)__builtin_amdgcn_s_memtime(); } while (0)
+#define SSTAMP(k) do { if (SMER_SAMPLE_STAMPS && !ROWS && lane == 0) mt[640 + (k)] = (uint32_t)__builtin_amdgcn_s_memtime(); } while (0)
 
 // TP: the request's temperature and nucleus threshold come from tp[r] (double
 // [R, 2]: t, p; p < 0 = None), read from device memory on every step, so a
@@ -558,7 +560,13 @@ __device__ __forceinline__ uint32_t f32_ord(float f) {
 // sum(q[candidates]) is c at the last candidate: builtin sum() from 0 and
 // np.cumsum add the same numbers in the same order.  !TP is t = 1, p = None
 // with the division folded away (x / 1.0 is exact: the same bits).
-template <bool RING, bool TP>
+// ROWS: one MT19937 stream per request (mt + r * ldmt: 624 key words and the
+// position) instead of the one shared stream, so nothing orders the draws
+// across requests: one block per request (r = blockIdx.x) runs the same body
+// on its own stream, and the live count is taken as grammar_greedy_kernel
+// takes it (atomic add, then the ticket).  !ROWS is the serial walk over
+// the shared stream, whose draw order is the host loop's.
+template <bool RING, bool TP, bool ROWS>
 __global__ __launch_bounds__(64) void grammar_sample_kernel(
     int R, int V, const float* __restrict__ logits, long ldl, int32_t* __restrict__ state, int nst,
     const int8_t* __restrict__ targets, int max_masks, const uint8_t* __restrict__ keep,
@@ -566,7 +574,7 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
     int max_span, const int32_t* __restrict__ src_len, int64_t* __restrict__ ids,
     int32_t* __restrict__ meta, int M, int32_t* __restrict__ out_tok, int cap,
     int32_t* __restrict__ alive, int32_t* __restrict__ ring, int ring_n, uint32_t* __restrict__ mt,
-    const double* __restrict__ tp) {
+    const double* __restrict__ tp, long ldmt) {
   // one wave; element i of a row lives in lane i / 8, slot i % 8
   __shared__ uint32_t key[624];
   __shared__ double pe[SMX];   // e, then p by vocabulary index
@@ -578,6 +586,8 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
   __shared__ __attribute__((aligned(16))) uint8_t tk[13 * SMX], tr[13 * SMX];  // keep / reject tables
   __shared__ uint8_t tcls[SMX];
   const int lane = threadIdx.x;
+  const int r_lo = ROWS ? (int)blockIdx.x : 0, r_hi = ROWS ? r_lo + 1 : R;
+  if constexpr (ROWS) mt += (long)r_lo * ldmt;
   SSTAMP(0);
   // every input load of the step in one batch (one memory latency, not a
   // chain of them): the MT key, the grammar tables, the first request
@@ -625,20 +635,26 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
   int sv_n, tgv_n;
   float lg_n[8];
   double tp_n = 0.;
-  fetch(0, sv_n, tgv_n, lg_n, tp_n);
+  fetch(r_lo, sv_n, tgv_n, lg_n, tp_n);
   int pos = (int)mt[624];
   __syncthreads();
   SSTAMP(1);
   int live = 0;
-  for (int r = 0; r < R; ++r) {
+  for (int r = r_lo; r < r_hi; ++r) {
     int32_t* st = state + (long)r * nst;
     const int sv = sv_n, tgv = tgv_n;
     float lg8[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) lg8[j] = lg_n[j];
     const double tpv = tp_n;
-    fetch(r + 1, sv_n, tgv_n, lg_n, tp_n);
-    if (__shfl(sv, ST_DONE, 64)) continue;  // wave-uniform
+    if constexpr (!ROWS) fetch(r + 1, sv_n, tgv_n, lg_n, tp_n);
+    if (__shfl(sv, ST_DONE, 64)) {  // wave-uniform
+      if constexpr (ROWS) {  // its stream stays as it is; the step still counts the block
+        if (RING && lane == 0) grammar_ring_ticket(alive, ring, ring_n, R);
+        return;
+      }
+      continue;
+    }
     const double temp = TP ? __shfl(tpv, 0, 64) : 1.0, pnuc = TP ? __shfl(tpv, 1, 64) : -1.0;
     const bool nuc = TP && pnuc >= 0.0;  // wave-uniform
     const int flags = __shfl(sv, ST_FLAGS, 64), len = __shfl(sv, ST_LEN, 64),
@@ -884,7 +900,13 @@ __global__ __launch_bounds__(64) void grammar_sample_kernel(
   for (int i = lane; i < 624; i += 64) mt[i] = key[i];
   if (lane == 0) {
     mt[624] = (uint32_t)pos;
-    if (RING) {
+    if constexpr (ROWS) {
+      if (live) {
+        if (RING) __hip_atomic_fetch_add(&alive[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else atomicAdd(alive, 1);  // zeroed by the caller's memset
+      }
+      if (RING) grammar_ring_ticket(alive, ring, ring_n, R);
+    } else if (RING) {
       const int s = alive[2];
       __hip_atomic_store(&ring[s % ring_n], live, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       alive[2] = s + 1;
@@ -899,15 +921,15 @@ int launch_grammar_sample(int R, int V, const float* logits, long ldl, int32_t* 
                           const int8_t* targets, int max_masks, const uint8_t* keep, const uint8_t* reject,
                           const uint8_t* cls, int eos, int m0, int trash_pos, int max_span,
                           const int32_t* src_len, int64_t* ids, int32_t* meta, int32_t* out_tok, int cap,
-                          uint32_t* mt, int32_t* ctl, int32_t* ring, int ring_n, const double* tp,
-                          smer_stream_t stream) {
+                          uint32_t* mt, long ldmt, bool rows, int32_t* ctl, int32_t* ring, int ring_n,
+                          const double* tp, smer_stream_t stream) {
   SMER_REQUIRE(R > 0 && V > 0 && V <= SMX && nst >= 9 && max_masks > 0 && cap > 0,
-               "smer_grammar_sample_step[_tp]: sizes (V <= 512)");
-  SMER_REQUIRE(ldl >= V, "smer_grammar_sample_step[_tp]: logits row stride");
+               "smer_grammar_sample_step[_tp|_rows]: sizes (V <= 512)");
+  SMER_REQUIRE(ldl >= V, "smer_grammar_sample_step[_tp|_rows]: logits row stride");
   SMER_REQUIRE(logits && state && targets && keep && reject && cls && src_len && ids && meta && out_tok && mt && ctl,
-               "smer_grammar_sample_step[_tp]: null pointer");
+               "smer_grammar_sample_step[_tp|_rows]: null pointer");
   SMER_REQUIRE(eos >= 0 && eos < V && m0 >= 0 && m0 < V && trash_pos > 0 && max_span > 1,
-               "smer_grammar_sample_step[_tp]: token ids");
+               "smer_grammar_sample_step[_tp|_rows]: token ids");
   hipStream_t s = (hipStream_t)stream;
   void* dring = nullptr;
   if (ring) {
@@ -916,17 +938,26 @@ int launch_grammar_sample(int R, int V, const float* logits, long ldl, int32_t* 
       dring = ring;
     }
   }
+  // rows: one block per request, each on its own stream; without a ring the
+  // blocks add themselves to ctl[0], zeroed here (as smer_grammar_greedy_step)
+  if (rows && !ring && hipMemsetAsync(ctl, 0, sizeof(int32_t), s) != hipSuccess)
+    return smer_set_error(SMER_ERR_HIP, "smer_grammar_sample_step_rows: memset");
   auto go = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, s, R, V, logits, ldl, state, nst, targets, max_masks, keep,
-                       reject, cls, eos, m0, trash_pos, max_span, src_len, ids, meta, 2 * R, out_tok, cap, ctl,
-                       (int32_t*)dring, ring ? ring_n : 0, mt, tp);
+    hipLaunchKernelGGL(kernel, dim3(rows ? R : 1), dim3(64), 0, s, R, V, logits, ldl, state, nst, targets,
+                       max_masks, keep, reject, cls, eos, m0, trash_pos, max_span, src_len, ids, meta, 2 * R,
+                       out_tok, cap, ctl, (int32_t*)dring, ring ? ring_n : 0, mt, tp, ldmt);
+  };
+  auto pick = [&](auto rg, auto t) {
+    constexpr bool RG = decltype(rg)::value, T = decltype(t)::value;
+    if (rows) go(grammar_sample_kernel<RG, T, true>);
+    else go(grammar_sample_kernel<RG, T, false>);
   };
   if (ring) {
-    if (tp) go(grammar_sample_kernel<true, true>);
-    else go(grammar_sample_kernel<true, false>);
+    if (tp) pick(std::true_type{}, std::true_type{});
+    else pick(std::true_type{}, std::false_type{});
   } else {
-    if (tp) go(grammar_sample_kernel<false, true>);
-    else go(grammar_sample_kernel<false, false>);
+    if (tp) pick(std::false_type{}, std::true_type{});
+    else pick(std::false_type{}, std::false_type{});
   }
   SMER_CHECK_LAUNCH("smer_grammar_sample_step");
   return SMER_OK;
@@ -941,7 +972,7 @@ extern "C" int smer_grammar_sample_step(int R, int V, const float* logits, long 
                                         int32_t* ctl, int32_t* ring, int ring_n, smer_stream_t stream) {
   return launch_grammar_sample(R, V, logits, ldl, state, nst, targets, max_masks, keep,
                                reject, cls, eos, m0, trash_pos, max_span, src_len, ids, meta, out_tok, cap, mt,
-                               ctl, ring, ring_n, nullptr, stream);
+                               625, false, ctl, ring, ring_n, nullptr, stream);
 }
 
 // The same step with a temperature and a nucleus threshold per request: tp
@@ -957,5 +988,26 @@ extern "C" int smer_grammar_sample_step_tp(int R, int V, const float* logits, lo
   SMER_REQUIRE(tp != nullptr, "smer_grammar_sample_step_tp: null tp");
   return launch_grammar_sample(R, V, logits, ldl, state, nst, targets, max_masks,
                                keep, reject, cls, eos, m0, trash_pos, max_span, src_len, ids, meta, out_tok, cap,
-                               mt, ctl, ring, ring_n, tp, stream);
+                               mt, 625, false, ctl, ring, ring_n, tp, stream);
+}
+
+// The same step on one MT19937 stream per request: mt + r * ldmt holds request
+// r's 624 key words and position (ldmt >= 625), and the requests run in
+// parallel, one block each.  tp may be null: {1.0, None} for every request.
+// A request that is done keeps its stream as it is.  The live count: ctl[0]
+// (zeroed on the stream here) without a ring, ring[step % ring_n] with one
+// (ctl int32 [3] zeroed once by the caller), as smer_grammar_greedy_step[_ring].
+extern "C" int smer_grammar_sample_step_rows(int R, int V, const float* logits, long ldl, int32_t* state,
+                                             int nst, const int8_t* targets, int max_masks,
+                                             const uint8_t* keep, const uint8_t* reject, const uint8_t* cls,
+                                             int eos, int m0, int trash_pos, int max_span,
+                                             const int32_t* src_len, int64_t* ids, int32_t* meta,
+                                             int32_t* out_tok, int cap, uint32_t* mt, long ldmt,
+                                             int32_t* ctl, int32_t* ring, int ring_n, const double* tp,
+                                             smer_stream_t stream) {
+  SMER_REQUIRE(ldmt >= 625, "smer_grammar_sample_step_rows: mt row stride (ldmt >= 625)");
+  SMER_REQUIRE(!ring || ring_n > 0, "smer_grammar_sample_step_rows: ring size");
+  return launch_grammar_sample(R, V, logits, ldl, state, nst, targets, max_masks,
+                               keep, reject, cls, eos, m0, trash_pos, max_span, src_len, ids, meta, out_tok, cap,
+                               mt, ldmt, true, ctl, ring, ring_n, tp, stream);
 }

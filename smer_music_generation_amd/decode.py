@@ -118,6 +118,7 @@ class DecodeSession:
         ptr = self.model.pos_enc.pe.data_ptr()
         if ptr != self._pe_ptr:
             self.graph = None
+            self._graphs = {}
             self._greedy = None
             self._pe_ptr = ptr
 
@@ -533,29 +534,54 @@ class DecodeSession:
     # greedy decode with the grammar on device (csrc/decode_ops.hip)
     # ------------------------------------------------------------------
     N_STATE = 12
+    LDMT = 640  # words per request of g_mt_rows (625 used: rows start 256-byte aligned)
+
+    def _bind_grammar(self, bufs):
+        """Make one captured graph's buffers the session's g_* attributes."""
+        for k, v in bufs.items():
+            setattr(self, k, v)
 
     def _capture_greedy(self, st, tg, keep, cls, cap, nm, eos, m0, lookahead, max_span, use_ring,
-                        sample=False):
+                        mode="greedy"):
         """Persistent grammar buffers + the captured (decoder step + grammar)
-        graph, reused by later greedy_decode calls of the same shapes."""
+        graph, reused by later calls of the same mode and shapes.  mode:
+        "greedy", "stream" (the sampler on the one shared MT19937 stream) or
+        "rows" (the sampler on one stream per request).  The buffers a graph
+        addresses belong to it (returned, and kept with it in self._graphs):
+        the graphs of the other modes keep theirs."""
         dev = self.dev
-        self.g_state = torch.from_numpy(st).to(dev)
-        self.g_targets = torch.from_numpy(tg).to(dev)
-        self.g_keep = torch.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8)).to(dev)
-        self.g_cls = torch.from_numpy(np.ascontiguousarray(cls, dtype=np.uint8)).to(dev)
-        self.g_srclen = torch.from_numpy(self.src_len.astype(np.int32)).to(dev)
-        self.g_out = torch.zeros(self.R, cap, dtype=torch.int32, device=dev)
+        bufs = dict(
+            g_state=torch.from_numpy(st).to(dev),
+            g_targets=torch.from_numpy(tg).to(dev),
+            g_keep=torch.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8)).to(dev),
+            g_cls=torch.from_numpy(np.ascontiguousarray(cls, dtype=np.uint8)).to(dev),
+            g_srclen=torch.from_numpy(self.src_len.astype(np.int32)).to(dev),
+            g_out=torch.zeros(self.R, cap, dtype=torch.int32, device=dev))
+        if mode != "greedy":
+            bufs["g_reject"] = torch.zeros(keep.shape, dtype=torch.uint8, device=dev)
+            bufs["g_tp"] = torch.zeros(self.R, 2, dtype=torch.float64, device=dev)
+            if mode == "rows":
+                bufs["g_mt_rows"] = torch.zeros(self.R, self.LDMT, dtype=torch.int32, device=dev)
+            else:
+                bufs["g_mt"] = torch.zeros(625, dtype=torch.int32, device=dev)
         # live counts: the step's grammar kernel publishes its count into a
         # pinned host ring itself (no per-step memset / D2H copy between the
         # replays); SMER_GRAMMAR_RING=0: memset + copy per step (A/B)
         ring = torch.zeros(2 * lookahead + 2, dtype=torch.int32).pin_memory()
         rv = ring.numpy()
-        self.g_alive = torch.zeros(3 if use_ring else 1, dtype=torch.int32, device=dev)
+        bufs["g_alive"] = torch.zeros(3 if use_ring else 1, dtype=torch.int32, device=dev)
+        self._bind_grammar(bufs)
         gargs = dict(eos=eos, m0=m0, trash_pos=self.Tmax - 1, max_span=max_span,
                      ring=ring if use_ring else None)
 
         def grammar():
-            if sample:
+            if mode == "rows":
+                ops.grammar_sample_step_rows(self.logits_t, self.g_state, self.g_targets, self.g_keep,
+                                             self.g_reject, self.g_cls, self.g_srclen, self.ids_t,
+                                             self.meta_t, self.g_out, self.g_mt_rows, self.g_alive,
+                                             tp=self.g_tp, **gargs)
+                return
+            if mode == "stream":
                 ops.grammar_sample_step(self.logits_t, self.g_state, self.g_targets, self.g_keep,
                                         self.g_reject, self.g_cls, self.g_srclen, self.ids_t,
                                         self.meta_t, self.g_out, self.g_mt, self.g_alive, tp=self.g_tp,
@@ -578,10 +604,10 @@ class DecodeSession:
         torch.cuda.current_stream().wait_stream(gs)
         torch.cuda.synchronize()
         t_c = time.perf_counter()
-        return g, ring, rv, t_a, t_b, t_c
+        return g, ring, rv, t_a, t_b, t_c, bufs
 
     def sampled_decode(self, spans, keep, reject, cls, *, eos, m0, lookahead=3, max_span=100,
-                       t=1.0, p=None):
+                       t=1.0, p=None, seeds=None):
         """The sampled infill loop (the reference's sampling(): softmax with
         temperature, then weighted_sampling or, with p, nucleus, and its
         redraws) on device: each step is one replay of the captured
@@ -591,7 +617,13 @@ class DecodeSession:
         stream continues exactly as if the host had drawn.  t, p: scalars or
         one value per span (p None = the whole distribution); the kernel
         reads them from a device buffer on every step, so calls with other
-        values replay the same captured graph.  Returns
+        values replay the same captured graph.
+        seeds (one int in [0, 2**32) per span): span r draws from its own
+        stream np.random.RandomState(seeds[r]) instead, built here on the host
+        and copied to the device; the step then ends in the one-block-per-
+        request form of the kernel (smer_grammar_sample_step_rows), a second
+        captured graph kept beside the unseeded one, and np.random is neither
+        read nor written.  Other seeds replay that graph.  Returns
         (per-request emitted ids, steps, error flags, per-request redraw
         failure flags)."""
         if all(sp.done for sp in spans):  # nothing to draw: np.random stays untouched
@@ -609,16 +641,30 @@ class DecodeSession:
         if not (np.isfinite(tp_h).all() and (tp_h[:, 0] > 0).all() and
                 all(q is None or float(q) >= 0 for q in ps)):
             raise ValueError("sampled_decode: t must be finite and > 0, p None or finite and >= 0")
-        st0 = np.random.get_state()
-        if st0[0] != "MT19937":
-            raise RuntimeError("sampled_decode: np.random is not MT19937")
-        mt_h = np.empty(625, dtype=np.uint32)
-        mt_h[:624] = st0[1]
-        mt_h[624] = int(st0[2])
-        res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
-                                   max_span=max_span, sample=(reject, mt_h, tp_h))
-        m = self.g_mt.cpu().numpy().view(np.uint32)
-        np.random.set_state(("MT19937", m[:624].copy(), int(m[624]), st0[3], st0[4]))
+        if seeds is not None:
+            if len(seeds) != n:
+                raise ValueError("sampled_decode: one seed per span")
+            # a freshly seeded state: the key after init_genrand, position 624
+            # (the first draw twists); slots past the spans are done and only
+            # need some valid state
+            mt_h = np.zeros((self.R, self.LDMT), dtype=np.uint32)
+            for r in range(self.R):
+                s0 = np.random.RandomState(int(seeds[r]) if r < n else 0).get_state()
+                mt_h[r, :624] = s0[1]
+                mt_h[r, 624] = int(s0[2])
+            res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
+                                       max_span=max_span, sample=(reject, mt_h, tp_h, True))
+        else:
+            st0 = np.random.get_state()
+            if st0[0] != "MT19937":
+                raise RuntimeError("sampled_decode: np.random is not MT19937")
+            mt_h = np.empty(625, dtype=np.uint32)
+            mt_h[:624] = st0[1]
+            mt_h[624] = int(st0[2])
+            res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
+                                       max_span=max_span, sample=(reject, mt_h, tp_h, False))
+            m = self.g_mt.cpu().numpy().view(np.uint32)
+            np.random.set_state(("MT19937", m[:624].copy(), int(m[624]), st0[3], st0[4]))
         ids, steps, err, step_ms = res
         fails = [[(x >> 16) & 1 for x in q] for q in ids]
         return [[x & 0xFFFF for x in q] for q in ids], steps, err, fails
@@ -666,26 +712,18 @@ class DecodeSession:
         if not feeds:
             return [[] for _ in range(R)], 0, np.zeros(R, dtype=np.int32), []
         use_ring = os.environ.get("SMER_GRAMMAR_RING", "1") != "0" or sample is not None
+        # one captured graph per mode, side by side: a process that alternates
+        # between greedy, unseeded and seeded calls replays, never recaptures
+        mode = "greedy" if sample is None else "rows" if sample[3] else "stream"
         gkey = (nm, int(max_span), int(eos), int(m0), int(lookahead), use_ring, keep.shape, cls.shape,
-                sample is not None)
-        gc = getattr(self, "_greedy", None)
-        if sample is not None:
-            reject_t = torch.from_numpy(np.ascontiguousarray(sample[0], dtype=np.uint8))
-            mt_t = torch.from_numpy(sample[1].view(np.int32))
-            if getattr(self, "g_mt", None) is None:
-                self.g_mt = torch.zeros(625, dtype=torch.int32, device=dev)
-            if getattr(self, "g_reject", None) is None or tuple(self.g_reject.shape) != tuple(keep.shape):
-                # (a captured graph keyed on another keep shape is never replayed for this one)
-                self.g_reject = torch.zeros(keep.shape, dtype=torch.uint8, device=dev)
-            if getattr(self, "g_tp", None) is None:
-                self.g_tp = torch.zeros(self.R, 2, dtype=torch.float64, device=dev)
-            self.g_mt.copy_(mt_t)
-            self.g_reject.copy_(reject_t)
-            self.g_tp.copy_(torch.from_numpy(sample[2]))
+                mode)
+        graphs = self.__dict__.setdefault("_graphs", {})
+        gc = graphs.get(mode)
         if gc is not None and gc["key"] == gkey:
             # the captured step + grammar graph of an earlier call with the
             # same shapes: refresh its persistent inputs in place and replay
             t_a = t_b = time.perf_counter()
+            self._bind_grammar(gc["bufs"])
             self.eng.weights(self.dt)  # re-casts the bf16 weights in place if they moved
             self.g_state.copy_(torch.from_numpy(st))
             self.g_targets.copy_(torch.from_numpy(tg))
@@ -700,10 +738,16 @@ class DecodeSession:
             torch.cuda.synchronize()
             t_c = time.perf_counter()
         else:
-            g, ring, rv, t_a, t_b, t_c = self._capture_greedy(st, tg, keep, cls, cap, nm, eos, m0,
-                                                             lookahead, max_span, use_ring,
-                                                             sample is not None)
-            self._greedy = {"key": gkey, "graph": g, "ring": ring}
+            graphs.pop(mode, None)  # frees its buffers before the new ones are made
+            g, ring, rv, t_a, t_b, t_c, bufs = self._capture_greedy(st, tg, keep, cls, cap, nm, eos, m0,
+                                                                   lookahead, max_span, use_ring, mode)
+            gc = graphs[mode] = {"key": gkey, "graph": g, "ring": ring, "bufs": bufs}
+        self._greedy = gc  # the graph of this call
+        if sample is not None:
+            self.g_reject.copy_(torch.from_numpy(np.ascontiguousarray(sample[0], dtype=np.uint8)))
+            mt_dst = self.g_mt_rows if mode == "rows" else self.g_mt
+            mt_dst.copy_(torch.from_numpy(sample[1].view(np.int32)))
+            self.g_tp.copy_(torch.from_numpy(sample[2]))
         self._load_feeds(feeds)
         max_steps = max([s.n_masks for s in spans] + [0]) * (max_span + 1) + 2
         inflight = []

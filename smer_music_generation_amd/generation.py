@@ -19,6 +19,10 @@ Differences, all opt-in keywords with reference defaults:
   * `t=1.0, p=None` on `generation_all` / `infill` / `generation_batch`: the
     temperature and nucleus threshold of the reference's `sampling()`, which
     its own `generation_all` never passes on.
+  * `seed=None` on the same three: an int (or, batched, one per request)
+    gives every request its own `np.random.RandomState(seed)` stream instead
+    of the global `np.random` one, so its tokens depend on its seed and its
+    logits alone (not on the batch around it), and `np.random` is left alone.
 The grammar state machine, the -100 logit masking, the float64 softmax and
 the numpy RNG consumption are the reference's, so with the same
 `np.random` state the same token ids come out.
@@ -39,7 +43,7 @@ from .wire import (change_controls, fill_empty_bars, mask_bar_and_track,  # noqa
 # --------------------------------------------------------------------------
 # sampling (generation.py:11-95)
 # --------------------------------------------------------------------------
-def nucleus(probs, p):
+def nucleus(probs, p, rng=np.random):
     probs /= (sum(probs) + 1e-5)
     sorted_probs = np.sort(probs)[::-1]
     sorted_index = np.argsort(probs)[::-1]
@@ -51,7 +55,7 @@ def nucleus(probs, p):
         cand = sorted_index[:]
     cp = np.array([probs[i] for i in cand])
     cp /= sum(cp)
-    return np.random.choice(cand, size=1, p=cp)[0]
+    return rng.choice(cand, size=1, p=cp)[0]
 
 
 def softmax_with_temperature(logits, temperature):
@@ -59,7 +63,7 @@ def softmax_with_temperature(logits, temperature):
     return e / np.sum(e)
 
 
-def weighted_sampling(probs):
+def weighted_sampling(probs, rng=np.random):
     # the reference's builtin sum() adds left to right from 0: the last
     # element of the (sequential) cumulative sum is that number exactly, in
     # 1/12 of the time; probs[argsort] holds np.sort's values (ties are
@@ -71,11 +75,12 @@ def weighted_sampling(probs):
         raise TypeError("weighted_sampling expects float64 probabilities")
     probs /= np.add.accumulate(probs)[-1]
     sorted_index = np.argsort(probs)[::-1]
-    return _choice1(sorted_index, probs[sorted_index])
+    return _choice1(sorted_index, probs[sorted_index], rng)
 
 
-def _choice1(a, p):
-    """np.random.choice(a, size=1, p=p)[0] on the global RandomState, without
+def _choice1(a, p, rng=np.random):
+    """rng.choice(a, size=1, p=p)[0] (rng: a RandomState, or the np.random
+    module, whose functions are the global RandomState's methods), without
     its argument checks (a third of the per-token host time): NumPy's legacy
     `RandomState.choice` with replacement draws ONE `random_sample` and
     returns a[searchsorted(cdf / cdf[-1], u, side='right')], so the same
@@ -86,9 +91,9 @@ def _choice1(a, p):
     cdf = np.cumsum(p)
     total = cdf[-1]
     if not (abs(total - 1.0) <= 1e-9) or not (p >= 0.0).all():
-        return np.random.choice(a, size=1, p=p)[0]
+        return rng.choice(a, size=1, p=p)[0]
     cdf /= total
-    u = np.random.random_sample(1)
+    u = rng.random_sample(1)
     return a[cdf.searchsorted(u, side='right')][0]
 
 
@@ -136,8 +141,9 @@ def allowed_ids(vocab, **flags):
     return keep
 
 
-def sampling(logit, vocab, p=None, t=1.0, greedy=False, **flags):
-    """`generation.py:41-95` with vectorised masking."""
+def sampling(logit, vocab, p=None, t=1.0, greedy=False, rng=np.random, **flags):
+    """`generation.py:41-95` with vectorised masking.  rng: the stream the
+    draw comes from (np.random: the global one, as the reference)."""
     if isinstance(logit, torch.Tensor):
         logit = logit.squeeze().detach().cpu().numpy()
     lg = np.where(allowed_ids(vocab, **flags), np.asarray(logit, dtype=np.float32).astype(np.float64),
@@ -146,8 +152,8 @@ def sampling(logit, vocab, p=None, t=1.0, greedy=False, **flags):
     if greedy:
         return int(np.argmax(probs))
     if p is not None:
-        return nucleus(probs, p)
-    return weighted_sampling(probs)
+        return nucleus(probs, p, rng)
+    return weighted_sampling(probs, rng)
 
 
 def _check_tp(t, p, n=None):
@@ -195,6 +201,46 @@ def _check_variations(variations, n=None):
             raise ValueError("variations: one int, or one per request (%d)" % n)
         return [one(x) for x in variations]
     return one(variations) if n is None else [one(variations)] * n
+
+
+SEED_MAX = 2 ** 32 - 1
+
+
+def _check_seed(seed, n=None, takes=None):
+    """Validated seeds of a call.  None stays None (the global np.random
+    stream, today's behaviour); otherwise the list of effective seeds, one
+    per request slot in the expanded order: an int in [0, 2**32 - 1] (n None:
+    the plugin call), or with n requests an int for all of them or one int
+    per request -- a None inside a sequence is an error, a call is seeded
+    throughout or not at all.  takes (an int for the plugin call, else one
+    count per request): take k (0-based) of a request seeded s draws from
+    seed s + k, so it can be regenerated alone with seed=s + k, and s + takes
+    - 1 must not exceed 2**32 - 1.  Derived seeds of different requests may
+    coincide: keeping them apart is the caller's business.  Raises
+    ValueError; touches neither the model nor np.random."""
+    if seed is None:
+        return None
+
+    def one(x):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or \
+                not 0 <= x <= SEED_MAX:
+            raise ValueError("seed must be an int in [0, 2**32 - 1] (got %r)" % (x,))
+        return int(x)
+    if isinstance(seed, (list, tuple, np.ndarray)):
+        if n is None:
+            raise ValueError("seed is one int here")
+        if len(seed) != n:
+            raise ValueError("seed: one int, or one per request (%d)" % n)
+        seeds = [one(x) for x in seed]
+    else:
+        seeds = [one(seed)] * (1 if n is None else n)
+    if takes is None:
+        return seeds
+    counts = [takes] * len(seeds) if isinstance(takes, (int, np.integer)) else list(takes)
+    for s0, k in zip(seeds, counts):
+        if s0 + k - 1 > SEED_MAX:
+            raise ValueError("seed %d with %d variations: take seeds run past 2**32 - 1" % (s0, k))
+    return [s0 + j for s0, k in zip(seeds, counts) for j in range(k)]
 
 
 def gen_nopeek_mask(length):
@@ -299,10 +345,11 @@ class _Span:
     """Decoding state of one request: mask index, span tokens, grammar flags."""
 
     def __init__(self, vocab, src, mask_target, all_controls, no_whole, greedy, logger, t=1.0,
-                 p=None):
+                 p=None, rng=np.random):
         self.v = vocab
         self.t = t
         self.p = p
+        self.rng = rng  # the stream of this request's draws (np.random: the global one)
         self.src = src
         self.mask_target = mask_target
         self.all_controls = set(int(c) for c in all_controls)
@@ -329,12 +376,13 @@ class _Span:
         return self.tgt_inp + self.this_in
 
     def _draw(self, logit, check, failmsg, flags):
-        idx = sampling(logit, self.v, p=self.p, t=self.t, greedy=self.greedy, **flags)
+        idx = sampling(logit, self.v, p=self.p, t=self.t, greedy=self.greedy, rng=self.rng, **flags)
         if check is None:
             return idx
         n = 0
         while check(idx):
-            idx = sampling(logit, self.v, p=self.p, t=self.t, greedy=self.greedy, **flags)
+            idx = sampling(logit, self.v, p=self.p, t=self.t, greedy=self.greedy, rng=self.rng,
+                           **flags)
             n += 1
             if n > 10:
                 if self.logger is not None:
@@ -477,7 +525,8 @@ class _Precision:
 
 def generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
                    bars_to_generate, *, greedy=False, use_kv_cache=True, stats=None,
-                   precision="fp32", warm=True, device_grammar=True, t=1.0, p=None, variations=None):
+                   precision="fp32", warm=True, device_grammar=True, t=1.0, p=None, variations=None,
+                   seed=None):
     """`generation.py:468-696`.  Returns (restored '<U9' tokens,
     mask_track_names, mask_bar_names) or None (nothing masked / on error,
     after printing it, as the reference does).  `stats` (a dict, opt-in)
@@ -512,10 +561,23 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
     generation_batch([request] * n, greedy=greedy, precision=precision) on
     the same np.random stream.  None (default) is the single result.  The
     print-and-return-None on error holds for the call as a whole (KV-cached
-    path only; anything else than an int >= 1 raises ValueError)."""
+    path only; anything else than an int >= 1 raises ValueError).
+    seed: None (default) draws from the global np.random stream, as the
+    reference does.  An int s in [0, 2**32 - 1] draws from a stream of the
+    call's own, np.random.RandomState(s): the tokens are those of
+    `np.random.seed(s); generation_all(...)` without the seed, on every path,
+    and the global np.random state is neither read nor written.  With
+    variations=n, take k (0-based) uses seed s + k (s + n - 1 <= 2**32 - 1),
+    so a take can be regenerated alone with seed=s + k.  greedy=True
+    validates the seed and draws nothing.  Anything else raises ValueError
+    before the model or np.random is touched.  `stats` receives 'seeds', the
+    effective seed of every take (None unseeded)."""
     t, p = _check_tp(t, p)
+    n = None if variations is None else _check_variations(variations)
+    seeds = _check_seed(seed, None, n)
+    if stats is not None:
+        stats["seeds"] = seeds
     if variations is not None:
-        n = _check_variations(variations)
         if not use_kv_cache:
             raise ValueError("variations needs the KV-cached path (use_kv_cache=True)")
         with _Precision(model, precision):
@@ -523,7 +585,8 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
                 out, st = generation_batch(model, [(events, tracks_to_generate, bars_to_generate)],
                                            vocab, all_controls, greedy=greedy, logger=logger,
                                            return_stats=True, device_grammar=device_grammar, warm=warm,
-                                           t=t, p=p, variations=[n])
+                                           t=t, p=p, variations=[n],
+                                           seed=None if seeds is None else [seeds[0]])
                 if stats is not None:
                     stats["steps"] = st["steps"]
                 return out[0]
@@ -533,7 +596,7 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
     with _Precision(model, precision):
         return _generation_all(model, events, device, vocab, logger, all_controls,
                                tracks_to_generate, bars_to_generate, greedy, use_kv_cache, stats,
-                               warm, device_grammar, t, p)
+                               warm, device_grammar, t, p, None if seeds is None else seeds[0])
 
 
 _REJECT_CACHE = {}
@@ -555,19 +618,23 @@ def reject_table(vocab):
     return rej
 
 
-def _sampled_on_device(sess, st, vocab, all_controls, logger):
+def _sampled_on_device(sess, st, vocab, all_controls, logger, seed=None):
     """One request's sampled span loop on device (DecodeSession.
     sampled_decode), then the emitted ids replayed through the host span
     (event lists, the redraw-failure log lines).  Returns the steps, or None
     when a row's probabilities missed 1 by more than 1e-9 (np.random.choice
-    territory): the RNG is then rewound and the caller decodes on the host."""
+    territory): the RNG is then rewound and the caller decodes on the host
+    (a seeded call touches no global state: the caller starts a fresh
+    RandomState(seed))."""
     keep, cls = grammar_tables(vocab, all_controls)
-    rng0 = np.random.get_state()
+    rng0 = np.random.get_state() if seed is None else None
     seqs, steps, err, fails = sess.sampled_decode([st], keep, reject_table(vocab), cls,
                                                   eos=vocab.eos_index, m0=vocab.char2index('m_0'),
-                                                  t=st.t, p=st.p)
+                                                  t=st.t, p=st.p,
+                                                  seeds=None if seed is None else [seed])
     if err[0] & 2:
-        np.random.set_state(rng0)
+        if seed is None:
+            np.random.set_state(rng0)
         return None
     if err[0] & 1:
         raise ValueError("decoder prefix exceeds session max_tgt %d" % (sess.Tmax - 1))
@@ -582,11 +649,14 @@ def _sampled_on_device(sess, st, vocab, all_controls, logger):
 
 def _generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
                     bars_to_generate, greedy, use_kv_cache, stats, warm=True, device_grammar=True,
-                    t=1.0, p=None):
+                    t=1.0, p=None, seed=None):
+    def fresh_span():  # a seeded request starts its own stream (anew after a device redo)
+        rng = np.random if seed is None else np.random.RandomState(seed)
+        return _Span(vocab, src, target, all_controls, no_whole, greedy, logger, t, p, rng)
     try:
         src, mtn, mbn, target, no_whole = _prepare(events, vocab, tracks_to_generate,
                                                    bars_to_generate)
-        st = _Span(vocab, src, target, all_controls, no_whole, greedy, logger, t, p)
+        st = fresh_span()
         if st.n_masks == 0:
             return None
         model.eval()
@@ -600,11 +670,11 @@ def _generation_all(model, events, device, vocab, logger, all_controls, tracks_t
                                       warm=warm)
                 sess.prefill([0], [src])
                 if device_grammar and not greedy and vocab.vocab_size <= 512:
-                    n = _sampled_on_device(sess, st, vocab, all_controls, logger)
+                    n = _sampled_on_device(sess, st, vocab, all_controls, logger, seed)
                     if n is not None:
                         steps = n
                     else:  # fresh span, same RNG start: the host loop below
-                        st = _Span(vocab, src, target, all_controls, no_whole, greedy, logger, t, p)
+                        st = fresh_span()
                         sess.prefill([0], [src])
                 fed = 0
                 while not st.done:
@@ -705,7 +775,7 @@ def _batch_session(model, R, Smax, Tmax, precision, exact_tmax=False, warm=True,
 
 def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logger=None,
                      max_tgt=None, precision=None, return_stats=False, device_grammar=True,
-                     warm=True, t=1.0, p=None, variations=None):
+                     warm=True, t=1.0, p=None, variations=None, seed=None):
     """Decode many infill requests in lockstep on one KV-cached session.
 
     requests: list of (events, tracks_to_generate, bars_to_generate).
@@ -732,21 +802,37 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
     encoded ONCE and its takes share one cross-attention memory
     (DecodeSession.prefill_takes), and entry i of the result is the list of
     its takes' results (None where nothing was masked).
+    seed: None (default): every draw comes from the global np.random stream,
+    the requests in turn, so a request's tokens depend on the batch around
+    it.  An int in [0, 2**32 - 1] for all requests, or one per request (no
+    None among them): request i draws from its own stream
+    np.random.RandomState(seed[i]), so its tokens depend on its seed and its
+    logits alone -- the same in any batch, at any position, and (in fp32) as
+    generation_all(..., seed=seed[i]) -- and np.random is neither read nor
+    written.  With variations, take k (0-based) of request i uses seed[i] + k
+    (which must stay <= 2**32 - 1), so a take is regenerated alone with that
+    seed; derived seeds of different requests may coincide, which is the
+    caller's business.  On device the seeded sampler runs one block per
+    request (smer_grammar_sample_step_rows).  greedy=True validates the seed
+    and draws nothing.  Bad seeds raise ValueError before anything else.
     Returns a list of (restored, mask_track_names, mask_bar_names) (None
     where nothing was masked), and optionally {'tokens', 'steps', 'sources',
-    'prefill_rows', ..}."""
+    'prefill_rows', 'seeds' (the effective seed of every entry of 'generated',
+    None unseeded), ..}."""
     t0 = time.perf_counter()
     tps = _check_tp(t, p, len(requests))
     takes = None if variations is None else _check_variations(variations, len(requests))
+    seeds = _check_seed(seed, len(requests), takes)
     preps = [_prepare(list(ev), vocab, tr, br) for ev, tr, br in requests]
     srcs = [q[0] for q in preps]
     if takes is not None:  # the expanded list: take k of request i is a request of its own
         preps = [q for q, n in zip(preps, takes) for _ in range(n)]
         tps = [x for x, n in zip(tps, takes) for _ in range(n)]
 
-    def fresh_spans():
-        return [_Span(vocab, q[0], q[3], all_controls, q[4], greedy, logger, a, b)
-                for q, (a, b) in zip(preps, tps)]
+    def fresh_spans():  # seeded: every request's stream starts (again) at its seed
+        rngs = [np.random] * len(preps) if seeds is None else [np.random.RandomState(x) for x in seeds]
+        return [_Span(vocab, q[0], q[3], all_controls, q[4], greedy, logger, a, b, g)
+                for q, (a, b), g in zip(preps, tps, rngs)]
     spans = fresh_spans()
     R = len(preps)
     Smax = max(len(q[0]) for q in preps)
@@ -803,17 +889,20 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                 tokens += len(seq)
         elif device_grammar and vocab.vocab_size <= 512:
             keep, cls = grammar_tables(vocab, all_controls)
-            rng0 = np.random.get_state()
+            rng0 = np.random.get_state() if seeds is None else None
             ts = time.perf_counter()
             seqs, dsteps, err, fails = sess.sampled_decode(
                 spans, keep, reject_table(vocab), cls, eos=vocab.eos_index,
-                m0=vocab.char2index('m_0'), t=[a for a, _ in tps], p=[b for _, b in tps])
+                m0=vocab.char2index('m_0'), t=[a for a, _ in tps], p=[b for _, b in tps],
+                seeds=seeds)
             t_dev = time.perf_counter() - ts
             if np.any(err & 2):
                 # some row's probabilities missed 1 by more than 1e-9
                 # (np.random.choice territory): same RNG start, fresh spans,
                 # and the whole batch goes through the host loop below
-                np.random.set_state(rng0)
+                # (seeded: fresh_spans starts fresh RandomStates instead)
+                if seeds is None:
+                    np.random.set_state(rng0)
                 spans = fresh_spans()
                 prefill()
                 t_dev = 0.0
@@ -876,6 +965,6 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                      "prefill_s": t2 - t1, "decode_s": t3 - t2, "step_call_s": t_dev,
                      "request_latency_s": latency, "kv_row_reads": kv_reads,
                      "generated": [list(st.total) for st in spans],
-                     "sources": len(srcs), "prefill_rows": int(sess.prefill_rows),
+                     "seeds": seeds, "sources": len(srcs), "prefill_rows": int(sess.prefill_rows),
                      "decode_phases_s": dict(getattr(sess, "phase_s", {}))}
     return out

@@ -682,6 +682,40 @@ def grammar_sample_step(logits, state, targets, keep, reject, cls, src_len, ids,
     call("smer_grammar_sample_step_tp", *args, _p(tp), _stream())
 
 
+def grammar_sample_step_rows(logits, state, targets, keep, reject, cls, src_len, ids, meta, out_tok,
+                             mt, ctl, *, eos, m0, trash_pos, max_span=100, ring=None, tp=None):
+    """The sampled grammar step on one MT19937 stream per request
+    (smer_grammar_sample_step_rows): mt uint32 [R, ldmt >= 625], row r the
+    key + position of request r's stream (updated in place; a done request's
+    row is left alone), the requests drawn in parallel.  ctl int32 [3]; with
+    `ring` (pinned host int32 [n]) the live count lands in ring[step % n],
+    else in ctl[0] (zeroed by the call).  tp float64 [R, 2] on the device, or
+    None for t = 1, p = None throughout."""
+    R, nst = state.shape
+    V = keep.shape[1]
+    for t, dt in ((state, torch.int32), (targets, torch.int8), (keep, torch.uint8),
+                  (reject, torch.uint8), (cls, torch.uint8), (src_len, torch.int32),
+                  (ids, torch.int64), (meta, torch.int32), (out_tok, torch.int32),
+                  (mt, torch.int32), (ctl, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError("grammar_sample_step_rows: expected contiguous %s" % dt)
+    if logits.shape[0] < 2 * R or ids.shape[0] != 2 * R or meta.shape != (4, 2 * R) or \
+            targets.shape[0] != R or keep.shape[0] != 13 or reject.shape != keep.shape or \
+            cls.shape[0] != V or src_len.shape[0] != R or mt.dim() != 2 or mt.shape[0] != R or \
+            mt.shape[1] < 625 or ctl.numel() < 3 or out_tok.shape[0] != R:
+        raise RuntimeError("grammar_sample_step_rows: shape mismatch")
+    if ring is not None and (ring.dtype != torch.int32 or not ring.is_pinned()):
+        raise RuntimeError("grammar_sample_step_rows: ring must be pinned int32")
+    if tp is not None and (tp.dtype != torch.float64 or not tp.is_contiguous() or
+                           tuple(tp.shape) != (R, 2) or tp.device != state.device):
+        raise RuntimeError("grammar_sample_step_rows: tp must be contiguous float64 [R, 2] on the device")
+    call("smer_grammar_sample_step_rows", R, V, _p(logits), _ld(logits), _p(state), nst, _p(targets),
+         targets.shape[1], _p(keep), _p(reject), _p(cls), int(eos), int(m0), int(trash_pos),
+         int(max_span), _p(src_len), _p(ids), _p(meta), _p(out_tok), out_tok.shape[1], _p(mt),
+         mt.shape[1], _p(ctl), ring.data_ptr() if ring is not None else None,
+         ring.numel() if ring is not None else 0, _p(tp), _stream())
+
+
 # ---------------------------------------------------------------------------
 def layernorm(x, gamma, beta, y, mean, rstd, eps=1e-5):
     M, N = x.shape
