@@ -43,7 +43,10 @@
  *   smer_grammar_sample_step_rows  the same on one MT19937 stream per
  *                        request (a seed per request), the requests in
  *                        parallel
- *   smer_layernorm_*     residual LayerNorm, eps 1e-5 (transformer.py:392,395,
+ *   smer_logits_ban      per-request pitch constraints: banned tokens' logits
+ *                        become -100 ahead of any grammar step (sampling()'s
+ *                        masking, generation.py:41-95, with one more mask)
+ *   smer_layernorm_*   residual LayerNorm, eps 1e-5 (transformer.py:392,395,
  *                        462,466,469; final norms 274-275, 329-330)
  *   smer_embed_*         embedding gather x sqrt(d) + sinusoidal PE + dropout
  *                        (model.py:91-92,124-125) and its scatter backward
@@ -408,6 +411,21 @@ int smer_grammar_sample_step_rows(int R, int V, const float* logits, long ldl, i
                                   int32_t* meta, int32_t* out_tok, int cap, uint32_t* mt, long ldmt,
                                   int32_t* ctl, int32_t* ring, int ring_n, const double* tp,
                                   smer_stream_t stream);
+/* Per-request pitch constraints (not a reference operation: the reference
+ * masks token classes only, generation.py:41-95).  Run between the vocabulary
+ * projection and any smer_grammar_*_step entry on the same logits, state and
+ * max_masks: for request r it reads `done` and the mask index from the state
+ * row, looks up k = ban_of_mask[r * max_masks + mask index] (int8, -1 = none)
+ * and stores -100.f over logits[(2r+1) * ldl + v] for every v < V whose bit
+ * (word v / 32, bit v % 32) is set in ban_bits[(r * K + k) * 16 ..] (uint32
+ * [R, K, 16]).  Nothing else is written: done requests, k outside 0..K-1 and
+ * mask indices outside 0..max_masks-1 leave the row alone.  The grammar
+ * entries form keep ? logit : -100.f, so a banned token is drawn exactly as
+ * one their keep table masks.  V <= 512, K <= 127.  Status return, no
+ * allocation, no synchronisation. */
+int smer_logits_ban(int R, int V, float* logits, long ldl, const int32_t* state, int nst,
+                    int max_masks, const int8_t* ban_of_mask, const uint32_t* ban_bits, int K,
+                    smer_stream_t stream);
 
 int smer_layernorm_fwd(int dtype, int M, int N, const void* x, long ldx,
                        const float* gamma, const float* beta, float eps,

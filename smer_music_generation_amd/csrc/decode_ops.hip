@@ -1011,3 +1011,52 @@ extern "C" int smer_grammar_sample_step_rows(int R, int V, const float* logits, 
                                keep, reject, cls, eos, m0, trash_pos, max_span, src_len, ids, meta, out_tok, cap,
                                mt, ldmt, true, ctl, ring, ring_n, tp, stream);
 }
+
+// ---------------------------------------------------------------------------
+// Per-request pitch constraints: the logits of the tokens a request bans for
+// the mask it is about to draw become -100.f before the grammar kernel reads
+// them.  Both grammar kernels form x = keep[i] ? logit[i] : -100.f, so a kept
+// logit rewritten to exactly -100.f has the x, the sort key and the exp of a
+// masked one: the reference's `keep &= ~ban` in sampling().
+//   ban_of_mask int8 [R, max_masks]: the ban row of each mask, -1 for none;
+//   ban_bits uint32 [R, K, 16]: bit v of row k set = token v is banned.
+// One wave per request, 8 tokens per lane (V <= 512).  Done rows, masks with
+// no ban row and mask indices past the table leave the row alone; the lookups
+// are clamped, not guarded, and only the stores are predicated.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void logits_ban_kernel(
+    int R, int V, float* __restrict__ logits, long ldl, const int32_t* __restrict__ state, int nst,
+    int max_masks, const int8_t* __restrict__ ban_of_mask, const uint32_t* __restrict__ ban_bits,
+    int K) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int32_t* st = state + (long)r * nst;
+  const int done = st[ST_DONE], midx = st[ST_MIDX];
+  const int mc = min(max(midx, 0), max_masks - 1);
+  const int k = (int)ban_of_mask[(long)r * max_masks + mc];
+  const int kc = min(max(k, 0), K - 1);
+  // lane's 8 tokens are byte (lane & 3) of word lane / 4
+  const uint32_t w = ban_bits[((long)r * K + kc) * 16 + (lane >> 2)];
+  const bool on = !done && midx >= 0 && midx < max_masks && k >= 0 && k < K;
+  const uint32_t b = on ? (w >> (8 * (lane & 3))) & 0xffu : 0u;
+  float* lr = logits + (long)(2 * r + 1) * ldl;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int i = lane * 8 + j;
+    if (((b >> j) & 1u) && i < V) lr[i] = -100.f;
+  }
+}
+
+// Graph-capturable, no allocation, no synchronisation.  logits: the step's
+// fp32 logits, request r's row at (2r+1) * ldl (the grammar entries' rows).
+extern "C" int smer_logits_ban(int R, int V, float* logits, long ldl, const int32_t* state, int nst,
+                               int max_masks, const int8_t* ban_of_mask, const uint32_t* ban_bits,
+                               int K, smer_stream_t stream) {
+  SMER_REQUIRE(R > 0 && V > 0 && V <= 512 && nst >= 9 && max_masks > 0 && K > 0 && K <= 127,
+               "smer_logits_ban: sizes (V <= 512, K <= 127)");
+  SMER_REQUIRE(ldl >= V, "smer_logits_ban: logits row stride");
+  SMER_REQUIRE(logits && state && ban_of_mask && ban_bits, "smer_logits_ban: null pointer");
+  hipLaunchKernelGGL(logits_ban_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, R, V, logits, ldl,
+                     state, nst, max_masks, ban_of_mask, ban_bits, K);
+  SMER_CHECK_LAUNCH("smer_logits_ban");
+  return SMER_OK;
+}

@@ -535,6 +535,10 @@ class DecodeSession:
     # ------------------------------------------------------------------
     N_STATE = 12
     LDMT = 640  # words per request of g_mt_rows (625 used: rows start 256-byte aligned)
+    # ban rows per request of the '+ban' graphs (pitch constraints): one per
+    # constrained track, and a request masks at most the vocabulary's three
+    # tracks (track_0 .. track_2) -- rounded up to a power of two
+    BAN_K = 4
 
     def _bind_grammar(self, bufs):
         """Make one captured graph's buffers the session's g_* attributes."""
@@ -542,13 +546,15 @@ class DecodeSession:
             setattr(self, k, v)
 
     def _capture_greedy(self, st, tg, keep, cls, cap, nm, eos, m0, lookahead, max_span, use_ring,
-                        mode="greedy"):
+                        mode="greedy", ban=None):
         """Persistent grammar buffers + the captured (decoder step + grammar)
         graph, reused by later calls of the same mode and shapes.  mode:
         "greedy", "stream" (the sampler on the one shared MT19937 stream) or
         "rows" (the sampler on one stream per request).  The buffers a graph
         addresses belong to it (returned, and kept with it in self._graphs):
-        the graphs of the other modes keep theirs."""
+        the graphs of the other modes keep theirs.  ban ((ban_of_mask int8 [R,
+        nm], ban_bits uint32 [R, BAN_K, 16]) on the host): the graph runs
+        smer_logits_ban between the decoder step and the grammar kernel."""
         dev = self.dev
         bufs = dict(
             g_state=torch.from_numpy(st).to(dev),
@@ -564,6 +570,9 @@ class DecodeSession:
                 bufs["g_mt_rows"] = torch.zeros(self.R, self.LDMT, dtype=torch.int32, device=dev)
             else:
                 bufs["g_mt"] = torch.zeros(625, dtype=torch.int32, device=dev)
+        if ban is not None:
+            bufs["g_banmask"] = torch.from_numpy(ban[0]).to(dev)
+            bufs["g_banbits"] = torch.from_numpy(ban[1].view(np.int32)).to(dev)
         # live counts: the step's grammar kernel publishes its count into a
         # pinned host ring itself (no per-step memset / D2H copy between the
         # replays); SMER_GRAMMAR_RING=0: memset + copy per step (A/B)
@@ -575,6 +584,8 @@ class DecodeSession:
                      ring=ring if use_ring else None)
 
         def grammar():
+            if ban is not None:  # banned logits -> -100 ahead of the grammar kernel
+                ops.logits_ban(self.logits_t, self.g_state, self.g_banmask, self.g_banbits)
             if mode == "rows":
                 ops.grammar_sample_step_rows(self.logits_t, self.g_state, self.g_targets, self.g_keep,
                                              self.g_reject, self.g_cls, self.g_srclen, self.ids_t,
@@ -607,7 +618,7 @@ class DecodeSession:
         return g, ring, rv, t_a, t_b, t_c, bufs
 
     def sampled_decode(self, spans, keep, reject, cls, *, eos, m0, lookahead=3, max_span=100,
-                       t=1.0, p=None, seeds=None):
+                       t=1.0, p=None, seeds=None, bans=None):
         """The sampled infill loop (the reference's sampling(): softmax with
         temperature, then weighted_sampling or, with p, nucleus, and its
         redraws) on device: each step is one replay of the captured
@@ -623,7 +634,15 @@ class DecodeSession:
         and copied to the device; the step then ends in the one-block-per-
         request form of the kernel (smer_grammar_sample_step_rows), a second
         captured graph kept beside the unseeded one, and np.random is neither
-        read nor written.  Other seeds replay that graph.  Returns
+        read nor written.  Other seeds replay that graph.
+        bans (pitch constraints): per span None or (ban_of_mask row: the ban
+        row of each mask, -1 for none; bit rows uint32 [k <= BAN_K, 16]: bit v
+        of row j set = token v banned).  With any span constrained the call
+        replays the '+ban' graph of its mode, in which smer_logits_ban
+        rewrites the banned logits to -100 between the vocabulary projection
+        and the sampler; both tables are device data refreshed per call, so
+        other constraints replay that graph.  None (or all None): the graphs
+        without that node, as ever.  Returns
         (per-request emitted ids, steps, error flags, per-request redraw
         failure flags)."""
         if all(sp.done for sp in spans):  # nothing to draw: np.random stays untouched
@@ -653,7 +672,7 @@ class DecodeSession:
                 mt_h[r, :624] = s0[1]
                 mt_h[r, 624] = int(s0[2])
             res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
-                                       max_span=max_span, sample=(reject, mt_h, tp_h, True))
+                                       max_span=max_span, sample=(reject, mt_h, tp_h, True), bans=bans)
         else:
             st0 = np.random.get_state()
             if st0[0] != "MT19937":
@@ -662,18 +681,20 @@ class DecodeSession:
             mt_h[:624] = st0[1]
             mt_h[624] = int(st0[2])
             res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
-                                       max_span=max_span, sample=(reject, mt_h, tp_h, False))
+                                       max_span=max_span, sample=(reject, mt_h, tp_h, False), bans=bans)
             m = self.g_mt.cpu().numpy().view(np.uint32)
             np.random.set_state(("MT19937", m[:624].copy(), int(m[624]), st0[3], st0[4]))
         ids, steps, err, step_ms = res
         fails = [[(x >> 16) & 1 for x in q] for q in ids]
         return [[x & 0xFFFF for x in q] for q in ids], steps, err, fails
 
-    def greedy_decode(self, spans, keep, cls, *, eos, m0, lookahead=3, max_span=100):
+    def greedy_decode(self, spans, keep, cls, *, eos, m0, lookahead=3, max_span=100, bans=None):
+        """bans: pitch constraints, as sampled_decode's."""
         return self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
-                                    max_span=max_span)
+                                    max_span=max_span, bans=bans)
 
-    def _grammar_decode(self, spans, keep, cls, *, eos, m0, lookahead=3, max_span=100, sample=None):
+    def _grammar_decode(self, spans, keep, cls, *, eos, m0, lookahead=3, max_span=100, sample=None,
+                        bans=None):
         """Run the greedy infill loop of `spans` (generation._Span, one per
         request slot 0..len-1, freshly started, sources prefilled) entirely
         on device: each step is one replay of the captured decoder step +
@@ -717,8 +738,30 @@ class DecodeSession:
         mode = "greedy" if sample is None else "rows" if sample[3] else "stream"
         gkey = (nm, int(max_span), int(eos), int(m0), int(lookahead), use_ring, keep.shape, cls.shape,
                 mode)
+        # pitch constraints: a graph of its own per mode (mode + "+ban", the
+        # ban kernel in front of the grammar kernel); a call without any
+        # replays the graphs above, which never contain that node
+        ban = None
+        if bans is not None and any(b is not None for b in bans):
+            if len(bans) != R:
+                raise ValueError("one bans entry (or None) per span")
+            K = self.BAN_K
+            bm_h = np.full((self.R, nm), -1, dtype=np.int8)
+            bb_h = np.zeros((self.R, K, ops.BAN_WORDS), dtype=np.uint32)
+            for r, b in enumerate(bans):
+                if b is None:
+                    continue
+                row = np.asarray(b[0], dtype=np.int64)[:nm]
+                bits = np.asarray(b[1], dtype=np.uint32).reshape(-1, ops.BAN_WORDS)
+                if len(bits) > K or (len(row) and not -1 <= row.min() <= row.max() < len(bits)):
+                    raise ValueError("bans: at most %d ban rows per request, indices -1 .. rows - 1" % K)
+                bm_h[r, :len(row)] = row
+                bb_h[r, :len(bits)] = bits
+            ban = (bm_h, bb_h)
+            gkey += (K,)
+        gname = mode if ban is None else mode + "+ban"
         graphs = self.__dict__.setdefault("_graphs", {})
-        gc = graphs.get(mode)
+        gc = graphs.get(gname)
         if gc is not None and gc["key"] == gkey:
             # the captured step + grammar graph of an earlier call with the
             # same shapes: refresh its persistent inputs in place and replay
@@ -730,6 +773,9 @@ class DecodeSession:
             self.g_keep.copy_(torch.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8)))
             self.g_cls.copy_(torch.from_numpy(np.ascontiguousarray(cls, dtype=np.uint8)))
             self.g_srclen.copy_(torch.from_numpy(self.src_len.astype(np.int32)))
+            if ban is not None:
+                self.g_banmask.copy_(torch.from_numpy(ban[0]))
+                self.g_banbits.copy_(torch.from_numpy(ban[1].view(np.int32)))
             self.g_out.zero_()
             self.g_alive.zero_()
             g, ring = gc["graph"], gc["ring"]
@@ -738,10 +784,10 @@ class DecodeSession:
             torch.cuda.synchronize()
             t_c = time.perf_counter()
         else:
-            graphs.pop(mode, None)  # frees its buffers before the new ones are made
+            graphs.pop(gname, None)  # frees its buffers before the new ones are made
             g, ring, rv, t_a, t_b, t_c, bufs = self._capture_greedy(st, tg, keep, cls, cap, nm, eos, m0,
-                                                                   lookahead, max_span, use_ring, mode)
-            gc = graphs[mode] = {"key": gkey, "graph": g, "ring": ring, "bufs": bufs}
+                                                                   lookahead, max_span, use_ring, mode, ban)
+            gc = graphs[gname] = {"key": gkey, "graph": g, "ring": ring, "bufs": bufs}
         self._greedy = gc  # the graph of this call
         if sample is not None:
             self.g_reject.copy_(torch.from_numpy(np.ascontiguousarray(sample[0], dtype=np.uint8)))

@@ -23,6 +23,9 @@ Differences, all opt-in keywords with reference defaults:
     gives every request its own `np.random.RandomState(seed)` stream instead
     of the global `np.random` one, so its tokens depend on its seed and its
     logits alone (not on the batch around it), and `np.random` is left alone.
+  * `pitches=None` on the same three: the MIDI note numbers a request (or
+    each of its tracks) may use; the other pitch tokens are masked like a
+    banned token class (`pitch_set` builds ranges and scales).
 The grammar state machine, the -100 logit masking, the float64 softmax and
 the numpy RNG consumption are the reference's, so with the same
 `np.random` state the same token ids come out.
@@ -37,7 +40,7 @@ import torch
 from .decode import DecodeSession
 from .durations import durations_for_events
 from .wire import (change_controls, fill_empty_bars, mask_bar_and_track,  # noqa: F401
-                   mask_targets, restore_marked_input)
+                   mask_targets, restore_marked_input, track_names_of)
 
 
 # --------------------------------------------------------------------------
@@ -141,13 +144,17 @@ def allowed_ids(vocab, **flags):
     return keep
 
 
-def sampling(logit, vocab, p=None, t=1.0, greedy=False, rng=np.random, **flags):
+def sampling(logit, vocab, p=None, t=1.0, greedy=False, rng=np.random, ban=None, **flags):
     """`generation.py:41-95` with vectorised masking.  rng: the stream the
-    draw comes from (np.random: the global one, as the reference)."""
+    draw comes from (np.random: the global one, as the reference).  ban
+    (boolean [V], True = banned; None: nothing): `keep &= ~ban`, a banned
+    token's logit becomes -100.0 exactly as a masked class's does."""
     if isinstance(logit, torch.Tensor):
         logit = logit.squeeze().detach().cpu().numpy()
-    lg = np.where(allowed_ids(vocab, **flags), np.asarray(logit, dtype=np.float32).astype(np.float64),
-                  -100.0)
+    keep = allowed_ids(vocab, **flags)
+    if ban is not None:
+        keep = keep & ~np.asarray(ban, dtype=bool)
+    lg = np.where(keep, np.asarray(logit, dtype=np.float32).astype(np.float64), -100.0)
     probs = softmax_with_temperature(lg, t)
     if greedy:
         return int(np.argmax(probs))
@@ -241,6 +248,119 @@ def _check_seed(seed, n=None, takes=None):
         if s0 + k - 1 > SEED_MAX:
             raise ValueError("seed %d with %d variations: take seeds run past 2**32 - 1" % (s0, k))
     return [s0 + j for s0, k in zip(seeds, counts) for j in range(k)]
+
+
+PITCH_MIN, PITCH_MAX = 21, 108  # the MIDI numbers of the pitch tokens p_21 .. p_108
+
+
+def pitch_set(lo=None, hi=None, classes=None):
+    """The sorted tuple of MIDI note numbers in [max(lo, 21), min(hi, 108)]
+    whose pitch class n % 12 is in `classes` (None: all twelve), for
+    `pitches=`: pitch_set(28, 60) a bass range, pitch_set(classes=(0, 2, 4, 5,
+    7, 9, 11)) the C major scale.  An empty result raises ValueError."""
+    a = PITCH_MIN if lo is None else max(int(lo), PITCH_MIN)
+    b = PITCH_MAX if hi is None else min(int(hi), PITCH_MAX)
+    cl = None if classes is None else {int(c) % 12 for c in classes}
+    out = tuple(n for n in range(a, b + 1) if cl is None or n % 12 in cl)
+    if not out:
+        raise ValueError("pitch_set(%r, %r, %r) is empty" % (lo, hi, classes))
+    return out
+
+
+def _check_pitches(pitches, tracks, n=None):
+    """Validated pitch constraints of a call.  n None (the plugin call):
+    `tracks` is its tracks_to_generate and the result None (unconstrained) or
+    the effective {track number: sorted tuple of allowed MIDI numbers}: a
+    collection (list, tuple, set, frozenset, range or array) of ints
+    constrains every track of tracks_to_generate, a dict {track number:
+    collection} the listed tracks only (a key that is not in
+    tracks_to_generate is an error).  With n requests, `tracks` holds one
+    tracks_to_generate per request and the result one such value per request:
+    a list or tuple whose entries are all None, collections or dicts is the
+    per-request form and must have n entries; anything else (a collection of
+    ints, a dict) is one constraint applied to every request.  So a bare list
+    of ints is always one pitch set for all requests, whatever its length,
+    and [[60, 62, 64]] * n is that set spelled per request.  Every entry of a
+    set is an int in [21, 108] (no bool, no float) and every set is
+    non-empty.  Raises ValueError; touches neither the model nor np.random."""
+    def coll(x):
+        return isinstance(x, (list, tuple, set, frozenset, range, np.ndarray))
+
+    def one_set(x):
+        if not coll(x):
+            raise ValueError("pitches: a collection of MIDI note numbers, or a dict of them per "
+                             "track (got %r)" % (x,))
+        out = set()
+        for e in (x.tolist() if isinstance(x, np.ndarray) else x):
+            if isinstance(e, (bool, np.bool_)) or not isinstance(e, (int, np.integer)) or \
+                    not PITCH_MIN <= e <= PITCH_MAX:
+                raise ValueError("pitches: every entry is an int in [%d, %d] (got %r)"
+                                 % (PITCH_MIN, PITCH_MAX, e))
+            out.add(int(e))
+        if not out:
+            raise ValueError("pitches: an empty set allows no note")
+        return tuple(sorted(out))
+
+    def one_request(x, trk):
+        if x is None:
+            return None
+        trk = [int(t) for t in trk]
+        if isinstance(x, dict):
+            eff = {}
+            for k, val in x.items():
+                if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or \
+                        int(k) not in trk:
+                    raise ValueError("pitches: track %r is not in tracks_to_generate %r" % (k, trk))
+                eff[int(k)] = one_set(val)
+            return eff or None
+        s = one_set(x)
+        return {t: s for t in trk} or None
+
+    if n is None:
+        return one_request(pitches, tracks)
+    if pitches is None:
+        return [None] * n
+    if isinstance(pitches, (list, tuple)) and len(pitches) > 0 and \
+            all(x is None or isinstance(x, dict) or coll(x) for x in pitches):
+        if len(pitches) != n:
+            raise ValueError("pitches: one value, or one per request (%d)" % n)
+        return [one_request(x, trk) for x, trk in zip(pitches, tracks)]
+    return [one_request(pitches, trk) for trk in tracks]
+
+
+def _request_bans(vocab, events, tracks_to_generate, bars_to_generate, allowed):
+    """The ban rows of one request from its effective constraint `allowed`
+    ({track number: allowed MIDI numbers}, or None): (ban_of_mask, rows), or
+    None.  rows boolean [k, V], one per constrained track in ascending track
+    number, True on every pitch token outside the track's set; ban_of_mask:
+    per mask, in the order `mask_targets` builds (generation.py:488-492: for
+    each bar, for each track, r, d, o, p, and t after the last track), the row
+    of the mask's track or -1.  (Only an 'r' span can draw a pitch; the row
+    rides on the track's other spans too, which never admit one.)"""
+    if not allowed:
+        return None
+    order = sorted(allowed)
+    midi = {int(vocab.index2char(i)[2:]): i for i in vocab.pitch_indices}
+    rows = np.zeros((len(order), vocab.vocab_size), dtype=bool)
+    for k, trk in enumerate(order):
+        rows[k, vocab.pitch_indices] = True
+        rows[k, [midi[n] for n in allowed[trk]]] = False
+    names = track_names_of(events)
+    of_mask = []
+    for _ in bars_to_generate:
+        for t in tracks_to_generate:
+            k = order.index(int(t)) if int(t) in allowed else -1
+            of_mask += [k] * (5 if names.index('track_%d' % t) == len(names) - 1 else 4)
+    return of_mask, rows
+
+
+def ban_bits(rows):
+    """Boolean ban rows [k, V <= 512] as the device's bit rows uint32 [k, 16]:
+    token v is bit v % 32 of word v // 32."""
+    rows = np.asarray(rows, dtype=bool)
+    pad = np.zeros((rows.shape[0], 512), dtype=bool)
+    pad[:, :rows.shape[1]] = rows
+    return np.ascontiguousarray(np.packbits(pad, axis=1, bitorder='little')).view('<u4')
 
 
 def gen_nopeek_mask(length):
@@ -345,11 +465,14 @@ class _Span:
     """Decoding state of one request: mask index, span tokens, grammar flags."""
 
     def __init__(self, vocab, src, mask_target, all_controls, no_whole, greedy, logger, t=1.0,
-                 p=None, rng=np.random):
+                 p=None, rng=np.random, bans=None):
         self.v = vocab
         self.t = t
         self.p = p
         self.rng = rng  # the stream of this request's draws (np.random: the global one)
+        # pitch constraints (_request_bans): the ban row of each mask (-1:
+        # none) and the boolean rows; None: an unconstrained request
+        self.ban_of_mask, self.ban_rows = bans if bans is not None else (None, None)
         self.src = src
         self.mask_target = mask_target
         self.all_controls = set(int(c) for c in all_controls)
@@ -375,7 +498,24 @@ class _Span:
     def prefix(self):
         return self.tgt_inp + self.this_in
 
+    def ban(self):
+        """Boolean [V] ban of the mask being drawn, or None."""
+        if self.ban_of_mask is None or self.mask_idx >= len(self.ban_of_mask):
+            return None
+        k = self.ban_of_mask[self.mask_idx]
+        return None if k < 0 else self.ban_rows[k]
+
+    def device_bans(self):
+        """(ban_of_mask row, bit rows uint32 [k, 16]) for DecodeSession's
+        `bans=`, or None."""
+        if self.ban_of_mask is None:
+            return None
+        return self.ban_of_mask, ban_bits(self.ban_rows)
+
     def _draw(self, logit, check, failmsg, flags):
+        ban = self.ban()
+        if ban is not None:  # (an unconstrained draw is the call it always was)
+            flags = dict(flags, ban=ban)
         idx = sampling(logit, self.v, p=self.p, t=self.t, greedy=self.greedy, rng=self.rng, **flags)
         if check is None:
             return idx
@@ -526,7 +666,7 @@ class _Precision:
 def generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
                    bars_to_generate, *, greedy=False, use_kv_cache=True, stats=None,
                    precision="fp32", warm=True, device_grammar=True, t=1.0, p=None, variations=None,
-                   seed=None):
+                   seed=None, pitches=None):
     """`generation.py:468-696`.  Returns (restored '<U9' tokens,
     mask_track_names, mask_bar_names) or None (nothing masked / on error,
     after printing it, as the reference does).  `stats` (a dict, opt-in)
@@ -571,12 +711,32 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
     so a take can be regenerated alone with seed=s + k.  greedy=True
     validates the seed and draws nothing.  Anything else raises ValueError
     before the model or np.random is touched.  `stats` receives 'seeds', the
-    effective seed of every take (None unseeded)."""
+    effective seed of every take (None unseeded).
+    pitches: None (default): any of the pitch tokens p_21 .. p_108 may be
+    drawn, today's behaviour bit for bit.  A collection of ints (see
+    pitch_set): the MIDI note numbers every masked track of the request may
+    use; a dict {track number: collection}, keys among tracks_to_generate: the
+    listed tracks only, the others unconstrained.  For every draw of a span
+    of a constrained track the logits of the pitch tokens outside the set
+    become -100.0 -- after the float32 -> float64 widening, before the division
+    by t, exactly as a masked class's do (`keep &= ~ban` in sampling()); the
+    redraw checks do not change.  A banned pitch therefore has probability
+    about e^-100 relative to the best kept token: not a mathematical zero,
+    but never drawn in practice.  Since at least one pitch is kept, every
+    grammar state that demands a pitch can still be satisfied.  Every path --
+    device (greedy, shared stream, seeded), host loop, use_kv_cache=False --
+    draws the same tokens on the same stream; with variations all takes share
+    the constraint.  An empty set, an entry that is not an int in [21, 108]
+    (bool and float included) or an unknown track raises ValueError before
+    the model or np.random is touched.  `stats` receives 'pitches': None, or
+    the effective {track number: sorted tuple}."""
     t, p = _check_tp(t, p)
     n = None if variations is None else _check_variations(variations)
     seeds = _check_seed(seed, None, n)
+    allowed = _check_pitches(pitches, tracks_to_generate)
     if stats is not None:
         stats["seeds"] = seeds
+        stats["pitches"] = allowed
     if variations is not None:
         if not use_kv_cache:
             raise ValueError("variations needs the KV-cached path (use_kv_cache=True)")
@@ -586,7 +746,8 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
                                            vocab, all_controls, greedy=greedy, logger=logger,
                                            return_stats=True, device_grammar=device_grammar, warm=warm,
                                            t=t, p=p, variations=[n],
-                                           seed=None if seeds is None else [seeds[0]])
+                                           seed=None if seeds is None else [seeds[0]],
+                                           pitches=[allowed])
                 if stats is not None:
                     stats["steps"] = st["steps"]
                 return out[0]
@@ -596,7 +757,8 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
     with _Precision(model, precision):
         return _generation_all(model, events, device, vocab, logger, all_controls,
                                tracks_to_generate, bars_to_generate, greedy, use_kv_cache, stats,
-                               warm, device_grammar, t, p, None if seeds is None else seeds[0])
+                               warm, device_grammar, t, p, None if seeds is None else seeds[0],
+                               allowed)
 
 
 _REJECT_CACHE = {}
@@ -618,6 +780,14 @@ def reject_table(vocab):
     return rej
 
 
+def _device_bans(spans):
+    """`bans=` of DecodeSession.greedy_decode / sampled_decode: per span None
+    or (ban_of_mask row, bit rows); None when no span is constrained (the
+    call then replays the graphs without the ban kernel)."""
+    bans = [sp.device_bans() for sp in spans]
+    return bans if any(b is not None for b in bans) else None
+
+
 def _sampled_on_device(sess, st, vocab, all_controls, logger, seed=None):
     """One request's sampled span loop on device (DecodeSession.
     sampled_decode), then the emitted ids replayed through the host span
@@ -631,7 +801,8 @@ def _sampled_on_device(sess, st, vocab, all_controls, logger, seed=None):
     seqs, steps, err, fails = sess.sampled_decode([st], keep, reject_table(vocab), cls,
                                                   eos=vocab.eos_index, m0=vocab.char2index('m_0'),
                                                   t=st.t, p=st.p,
-                                                  seeds=None if seed is None else [seed])
+                                                  seeds=None if seed is None else [seed],
+                                                  bans=_device_bans([st]))
     if err[0] & 2:
         if seed is None:
             np.random.set_state(rng0)
@@ -649,11 +820,12 @@ def _sampled_on_device(sess, st, vocab, all_controls, logger, seed=None):
 
 def _generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
                     bars_to_generate, greedy, use_kv_cache, stats, warm=True, device_grammar=True,
-                    t=1.0, p=None, seed=None):
+                    t=1.0, p=None, seed=None, allowed=None):
     def fresh_span():  # a seeded request starts its own stream (anew after a device redo)
         rng = np.random if seed is None else np.random.RandomState(seed)
-        return _Span(vocab, src, target, all_controls, no_whole, greedy, logger, t, p, rng)
+        return _Span(vocab, src, target, all_controls, no_whole, greedy, logger, t, p, rng, bans)
     try:
+        bans = _request_bans(vocab, events, tracks_to_generate, bars_to_generate, allowed)
         src, mtn, mbn, target, no_whole = _prepare(events, vocab, tracks_to_generate,
                                                    bars_to_generate)
         st = fresh_span()
@@ -775,7 +947,7 @@ def _batch_session(model, R, Smax, Tmax, precision, exact_tmax=False, warm=True,
 
 def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logger=None,
                      max_tgt=None, precision=None, return_stats=False, device_grammar=True,
-                     warm=True, t=1.0, p=None, variations=None, seed=None):
+                     warm=True, t=1.0, p=None, variations=None, seed=None, pitches=None):
     """Decode many infill requests in lockstep on one KV-cached session.
 
     requests: list of (events, tracks_to_generate, bars_to_generate).
@@ -815,24 +987,41 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
     caller's business.  On device the seeded sampler runs one block per
     request (smer_grammar_sample_step_rows).  greedy=True validates the seed
     and draws nothing.  Bad seeds raise ValueError before anything else.
+    pitches: the allowed MIDI note numbers (see generation_all), one value
+    for all requests or one per request.  A bare collection of ints or a
+    dict applies to every request; a list or tuple with len(requests) entries
+    that are each None, a collection or a dict is per request (None: that
+    request is unconstrained).  The two are told apart by the entries, never
+    by the length: a list of ints is always ONE pitch set for all requests,
+    and a list whose entries are None / collections / dicts must have one
+    entry per request (ValueError otherwise).  With variations all takes of
+    a request share its constraint.  A call in which no request is
+    constrained replays the step graphs it always did; a constrained call
+    replays the '+ban' graph of its mode, whose extra kernel
+    (smer_logits_ban) rewrites the banned logits ahead of the grammar
+    kernel.  Validated before anything else is touched (ValueError).
     Returns a list of (restored, mask_track_names, mask_bar_names) (None
     where nothing was masked), and optionally {'tokens', 'steps', 'sources',
     'prefill_rows', 'seeds' (the effective seed of every entry of 'generated',
-    None unseeded), ..}."""
+    None unseeded), 'pitches' (per request, None or the effective {track
+    number: sorted tuple}), ..}."""
     t0 = time.perf_counter()
     tps = _check_tp(t, p, len(requests))
     takes = None if variations is None else _check_variations(variations, len(requests))
     seeds = _check_seed(seed, len(requests), takes)
+    allowed = _check_pitches(pitches, [tr for _, tr, _ in requests], len(requests))
+    bans = [_request_bans(vocab, list(ev), tr, br, a) for (ev, tr, br), a in zip(requests, allowed)]
     preps = [_prepare(list(ev), vocab, tr, br) for ev, tr, br in requests]
     srcs = [q[0] for q in preps]
     if takes is not None:  # the expanded list: take k of request i is a request of its own
         preps = [q for q, n in zip(preps, takes) for _ in range(n)]
         tps = [x for x, n in zip(tps, takes) for _ in range(n)]
+        bans = [x for x, n in zip(bans, takes) for _ in range(n)]
 
     def fresh_spans():  # seeded: every request's stream starts (again) at its seed
         rngs = [np.random] * len(preps) if seeds is None else [np.random.RandomState(x) for x in seeds]
-        return [_Span(vocab, q[0], q[3], all_controls, q[4], greedy, logger, a, b, g)
-                for q, (a, b), g in zip(preps, tps, rngs)]
+        return [_Span(vocab, q[0], q[3], all_controls, q[4], greedy, logger, a, b, g, bn)
+                for q, (a, b), g, bn in zip(preps, tps, rngs, bans)]
     spans = fresh_spans()
     R = len(preps)
     Smax = max(len(q[0]) for q in preps)
@@ -861,7 +1050,7 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
             m0 = vocab.char2index('m_0')
             ts = time.perf_counter()
             seqs, steps, err, step_ms = sess.greedy_decode(spans, keep, cls, eos=vocab.eos_index,
-                                                           m0=m0)
+                                                           m0=m0, bans=_device_bans(spans))
             t_dev = time.perf_counter() - ts
             # completion time of each request from the call's start: host
             # preparation + prefill, then the GPU end time of its last step
@@ -894,7 +1083,7 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
             seqs, dsteps, err, fails = sess.sampled_decode(
                 spans, keep, reject_table(vocab), cls, eos=vocab.eos_index,
                 m0=vocab.char2index('m_0'), t=[a for a, _ in tps], p=[b for _, b in tps],
-                seeds=seeds)
+                seeds=seeds, bans=_device_bans(spans))
             t_dev = time.perf_counter() - ts
             if np.any(err & 2):
                 # some row's probabilities missed 1 by more than 1e-9
@@ -939,6 +1128,10 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                 # per-row float64 softmax argmax: exp/normalise is monotone)
                 specs = [spans[i].spec() for i in live]
                 keep = np.stack([allowed_ids(vocab, **f) for f, _, _ in specs])
+                for k, i in enumerate(live):
+                    ban = spans[i].ban()
+                    if ban is not None:
+                        keep[k] &= ~ban
                 ids = np.argmax(np.where(keep, lg, np.float32(-100.0)), axis=1)
                 for k, i in enumerate(live):
                     spans[i].commit_greedy(ids[k], specs[k][1], specs[k][2])
@@ -965,6 +1158,6 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                      "prefill_s": t2 - t1, "decode_s": t3 - t2, "step_call_s": t_dev,
                      "request_latency_s": latency, "kv_row_reads": kv_reads,
                      "generated": [list(st.total) for st in spans],
-                     "seeds": seeds, "sources": len(srcs), "prefill_rows": int(sess.prefill_rows),
+                     "seeds": seeds, "pitches": allowed, "sources": len(srcs), "prefill_rows": int(sess.prefill_rows),
                      "decode_phases_s": dict(getattr(sess, "phase_s", {}))}
     return out

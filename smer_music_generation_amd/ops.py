@@ -716,6 +716,34 @@ def grammar_sample_step_rows(logits, state, targets, keep, reject, cls, src_len,
          ring.numel() if ring is not None else 0, _p(tp), _stream())
 
 
+BAN_WORDS = 16  # uint32 words of one ban row: one bit per token, V <= 512
+
+
+def logits_ban(logits, state, ban_of_mask, ban_bits):
+    """Per-request pitch constraints ahead of a grammar step (smer_logits_ban):
+    for every request r that is not done, the entries of logits row 2r + 1
+    whose bit is set in ban_bits[r, ban_of_mask[r, mask index]] become -100.
+    logits float32 [>= 2R, V <= 512] (rows contiguous), state int32 [R, nst]
+    (the grammar state), ban_of_mask int8 [R, max_masks] (-1: no ban),
+    ban_bits int32 [R, K, 16] (the bits of uint32 words: token v is bit v % 32
+    of word v // 32)."""
+    R, nst = state.shape
+    V = logits.shape[1]
+    for t, dt in ((logits, torch.float32), (state, torch.int32), (ban_of_mask, torch.int8),
+                  (ban_bits, torch.int32)):
+        if t.dtype != dt or t.device != logits.device:
+            raise RuntimeError("logits_ban: expected %s on the logits' device" % dt)
+    if not (state.is_contiguous() and ban_of_mask.is_contiguous() and ban_bits.is_contiguous()) or \
+            logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError("logits_ban: expected contiguous tables and logits rows")
+    if logits.shape[0] < 2 * R or ban_of_mask.dim() != 2 or ban_of_mask.shape[0] != R or \
+            ban_bits.dim() != 3 or ban_bits.shape[0] != R or ban_bits.shape[2] != BAN_WORDS or \
+            not 1 <= ban_bits.shape[1] <= 127 or ban_of_mask.shape[1] < 1 or V > 32 * BAN_WORDS:
+        raise RuntimeError("logits_ban: shape mismatch")
+    call("smer_logits_ban", R, V, _p(logits), _ld(logits), _p(state), nst, ban_of_mask.shape[1],
+         _p(ban_of_mask), _p(ban_bits), ban_bits.shape[1], _stream())
+
+
 # ---------------------------------------------------------------------------
 def layernorm(x, gamma, beta, y, mean, rstd, eps=1e-5):
     M, N = x.shape
