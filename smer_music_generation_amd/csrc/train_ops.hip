@@ -39,9 +39,10 @@ __global__ __launch_bounds__(256) void wce_kernel(int R, int V, const float* __r
   float se = 0.f;
   for (int v = lane; v < V; v += 64) se += expf(x[v] - mx);
   se = wave_sum(se);
-  const float lse = mx + logf(se);
   const float wy = yt == 0 ? 0.f : w[yt];
-  if (lane == 0) row_loss[r] = wy * (lse - x[yt]);
+  // -log_softmax(x)[y] = log(se) - (x[y] - mx): both terms are of the loss's
+  // own size (mx + log(se) - x[y] cancels at the logits' magnitude)
+  if (lane == 0) row_loss[r] = wy * (logf(se) - (x[yt] - mx));
   if (dlog) {
     const float coef = grad_scale * wy / *denom;
     const float inv = 1.f / se;
@@ -380,15 +381,18 @@ __global__ __launch_bounds__(256) void argmax_acc_kernel(int R, int V, const flo
   const float* x = logits + (long)r * ldl;
   float best = -INFINITY;
   int bi = V;  // V: no finite value seen yet (all -inf: index 0, as torch)
+  // a NaN beats any number and the first NaN wins, as torch.argmax orders them
   for (int v = lane; v < V; v += 64) {
     const float xv = x[v];
-    if (xv > best || bi == V) { best = xv; bi = v; }  // per lane: ascending v, first max kept
+    // per lane: ascending v, first max (or first NaN) kept
+    if (bi == V || (xv != xv ? best == best : xv > best)) { best = xv; bi = v; }
   }
 #pragma unroll
   for (int w = 1; w < 64; w <<= 1) {
     const float ob = __shfl_xor(best, w, 64);
     const int oi = __shfl_xor(bi, w, 64);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    const bool on = ob != ob, bn = best != best;
+    if (on ? (!bn || oi < bi) : (!bn && (ob > best || (ob == best && oi < bi)))) { best = ob; bi = oi; }
   }
   if (lane == 0) {
     const int c = (yt >= 0 && yt < V) ? cls[yt] : ncls;
