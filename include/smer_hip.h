@@ -46,6 +46,9 @@
  *   smer_logits_ban      per-request pitch constraints: banned tokens' logits
  *                        become -100 ahead of any grammar step (sampling()'s
  *                        masking, generation.py:41-95, with one more mask)
+ *   smer_logprob_stage / _commit  the log-probability of each drawn token (the
+ *                        log of sampling()'s distribution at t = 1), taken
+ *                        around any grammar step
  *   smer_layernorm_*   residual LayerNorm, eps 1e-5 (transformer.py:392,395,
  *                        462,466,469; final norms 274-275, 329-330)
  *   smer_embed_*         embedding gather x sqrt(d) + sinusoidal PE + dropout
@@ -426,6 +429,32 @@ int smer_grammar_sample_step_rows(int R, int V, const float* logits, long ldl, i
 int smer_logits_ban(int R, int V, float* logits, long ldl, const int32_t* state, int nst,
                     int max_masks, const int8_t* ban_of_mask, const uint32_t* ban_bits, int K,
                     smer_stream_t stream);
+
+/* Take scores (not a reference operation): the log-probability of each drawn
+ * token at t = 1 over the whole masked distribution, the log of what the
+ * reference's sampling() builds (generation.py:41-95) -- float32 -> float64
+ * widening, -100.0 for masked entries, softmax -- with the maximum subtracted
+ * first.  The pair brackets any smer_grammar_*_step entry on the same logits,
+ * state, targets, max_masks and keep (after smer_logits_ban, if any):
+ *   smer_logprob_stage   for a request that is not done: the grammar state
+ *     code of the state the step starts in, x_i = keep[code * V + i] ?
+ *     (double)logits[(2r+1) * ldl + i] : -100.0, lse = max + log(sum exp(x_i -
+ *     max)), scratch[r * ldp + i] = x_i - lse for i < V (float64 [R, ldp >=
+ *     V]) and stage[r] = the request's token count (state word 7); a done
+ *     request gets stage[r] = -1 and keeps its scratch row.  Logits and
+ *     state are only read.
+ *   smer_logprob_commit  for a request with 0 <= c = stage[r] < cap whose token
+ *     count is now c + 1: out_lp[r * cap + c] = scratch[r * ldp + (out_tok[r *
+ *     cap + c] & 0xFFFF)] (bit 16 of out_tok: the redraw-failure flag).
+ *     Nothing else is written; out_lp float64 [R, cap] lines up with out_tok.
+ * V <= 512, 9 <= nst <= 64.  Status return, no allocation, no
+ * synchronisation. */
+int smer_logprob_stage(int R, int V, const float* logits, long ldl, const int32_t* state, int nst,
+                       const int8_t* targets, int max_masks, const uint8_t* keep, double* scratch,
+                       long ldp, int32_t* stage, smer_stream_t stream);
+int smer_logprob_commit(int R, int V, const int32_t* state, int nst, const int32_t* stage,
+                        const int32_t* out_tok, int cap, const double* scratch, long ldp,
+                        double* out_lp, smer_stream_t stream);
 
 int smer_layernorm_fwd(int dtype, int M, int N, const void* x, long ldx,
                        const float* gamma, const float* beta, float eps,

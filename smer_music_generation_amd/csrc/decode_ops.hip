@@ -1060,3 +1060,108 @@ extern "C" int smer_logits_ban(int R, int V, float* logits, long ldl, const int3
   SMER_CHECK_LAUNCH("smer_logits_ban");
   return SMER_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Take scores: the log-probability of every drawn token under the model and
+// the grammar mask, at t = 1 over the whole distribution (the log of the
+// distribution the reference's sampling() builds from the same row:
+// generation.token_logprobs).  The logits row lives for one step only, so two
+// small kernels bracket the grammar kernel inside the captured step:
+//   stage  (after the ban kernel, before the grammar kernel): from the state
+//          the step starts in, x_i = keep[code][i] ? (double)logit_i : -100.0,
+//          m = max x, lse = m + log(sum exp(x_i - m)) in float64, x_i - lse for
+//          i < V into the request's scratch row, and the request's ST_COUNT
+//          into its stage slot (-1: the request is done and its scratch row is
+//          left alone).  One wave per request, 8 tokens per lane (V <= 512).
+//          It writes neither the logits nor the state.
+//   commit (after the grammar kernel): a request whose stage slot c is in
+//          [0, cap) and whose ST_COUNT is now c + 1 drew out_tok[r, c] in this
+//          step: out_lp[r, c] = scratch[r, out_tok[r, c] & 0xFFFF] (bit 16 is
+//          the redraw-failure flag).  Nothing else is written.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void logprob_stage_kernel(
+    int R, int V, const float* __restrict__ logits, long ldl, const int32_t* __restrict__ state, int nst,
+    const int8_t* __restrict__ targets, int max_masks, const uint8_t* __restrict__ keep,
+    double* __restrict__ scratch, long ldp, int32_t* __restrict__ stage) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int32_t* st = state + (long)r * nst;
+  const int sv = lane < nst ? st[lane] : 0;
+  if (__shfl(sv, ST_DONE, 64)) {  // wave-uniform
+    if (lane == 0) stage[r] = -1;
+    return;
+  }
+  const int flags = __shfl(sv, ST_FLAGS, 64), len = __shfl(sv, ST_LEN, 64),
+            midx = __shfl(sv, ST_MIDX, 64), nowhole = __shfl(sv, ST_NOWHOLE, 64),
+            cnt = __shfl(sv, ST_COUNT, 64);
+  // the lookups are clamped (a live request's mask index and state code are
+  // in range; a corrupt state must still read inside the tables)
+  const int tgt = (int)targets[(long)r * max_masks + min(max(midx, 0), max_masks - 1)];
+  const int code = min(max(grammar_state(flags, len, tgt, nowhole), 0), 12);
+  const uint8_t* kp = keep + (long)code * V;
+  const float* lr = logits + (long)(2 * r + 1) * ldl;
+  double x[8];
+  double m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int i = lane * 8 + j, ic = min(i, V - 1);
+    const float lg = lr[ic];
+    x[j] = kp[ic] ? (double)lg : -100.0;
+    if (i < V) m = fmax(m, x[j]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+  double s = 0.;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (lane * 8 + j < V) s += exp(x[j] - m);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);  // a + b = b + a: every lane ends on the same sum
+  const double lse = m + log(s);
+  double* pr = scratch + (long)r * ldp;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int i = lane * 8 + j;
+    if (i < V) pr[i] = x[j] - lse;
+  }
+  if (lane == 0) stage[r] = cnt;
+}
+
+__global__ __launch_bounds__(64) void logprob_commit_kernel(
+    int R, int V, const int32_t* __restrict__ state, int nst, const int32_t* __restrict__ stage,
+    const int32_t* __restrict__ out_tok, int cap, const double* __restrict__ scratch, long ldp,
+    double* __restrict__ out_lp) {
+  const int r = blockIdx.x * 64 + threadIdx.x;
+  if (r >= R) return;
+  const int c = stage[r];
+  if (c < 0 || c >= cap || state[(long)r * nst + ST_COUNT] != c + 1) return;
+  const int tok = out_tok[(long)r * cap + c] & 0xFFFF;
+  if (tok < V) out_lp[(long)r * cap + c] = scratch[(long)r * ldp + tok];
+}
+
+// Graph-capturable, no allocation, no synchronisation.  logits, state,
+// targets, max_masks and keep are the grammar entry's own arguments.
+extern "C" int smer_logprob_stage(int R, int V, const float* logits, long ldl, const int32_t* state, int nst,
+                                  const int8_t* targets, int max_masks, const uint8_t* keep, double* scratch,
+                                  long ldp, int32_t* stage, smer_stream_t stream) {
+  SMER_REQUIRE(R > 0 && V > 0 && V <= 512 && nst >= 9 && nst <= 64 && max_masks > 0,
+               "smer_logprob_stage: sizes (V <= 512, 9 <= nst <= 64)");
+  SMER_REQUIRE(ldl >= V, "smer_logprob_stage: logits row stride");
+  SMER_REQUIRE(ldp >= V, "smer_logprob_stage: scratch row stride");
+  SMER_REQUIRE(logits && state && targets && keep && scratch && stage, "smer_logprob_stage: null pointer");
+  hipLaunchKernelGGL(logprob_stage_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, R, V, logits, ldl,
+                     state, nst, targets, max_masks, keep, scratch, ldp, stage);
+  SMER_CHECK_LAUNCH("smer_logprob_stage");
+  return SMER_OK;
+}
+
+extern "C" int smer_logprob_commit(int R, int V, const int32_t* state, int nst, const int32_t* stage,
+                                   const int32_t* out_tok, int cap, const double* scratch, long ldp,
+                                   double* out_lp, smer_stream_t stream) {
+  SMER_REQUIRE(R > 0 && V > 0 && V <= 512 && nst >= 9 && cap > 0, "smer_logprob_commit: sizes (V <= 512)");
+  SMER_REQUIRE(ldp >= V, "smer_logprob_commit: scratch row stride");
+  SMER_REQUIRE(state && stage && out_tok && scratch && out_lp, "smer_logprob_commit: null pointer");
+  hipLaunchKernelGGL(logprob_commit_kernel, dim3((R + 63) / 64), dim3(64), 0, (hipStream_t)stream, R, V,
+                     state, nst, stage, out_tok, cap, scratch, ldp, out_lp);
+  SMER_CHECK_LAUNCH("smer_logprob_commit");
+  return SMER_OK;
+}

@@ -546,7 +546,7 @@ class DecodeSession:
             setattr(self, k, v)
 
     def _capture_greedy(self, st, tg, keep, cls, cap, nm, eos, m0, lookahead, max_span, use_ring,
-                        mode="greedy", ban=None):
+                        mode="greedy", ban=None, score=False):
         """Persistent grammar buffers + the captured (decoder step + grammar)
         graph, reused by later calls of the same mode and shapes.  mode:
         "greedy", "stream" (the sampler on the one shared MT19937 stream) or
@@ -554,7 +554,10 @@ class DecodeSession:
         addresses belong to it (returned, and kept with it in self._graphs):
         the graphs of the other modes keep theirs.  ban ((ban_of_mask int8 [R,
         nm], ban_bits uint32 [R, BAN_K, 16]) on the host): the graph runs
-        smer_logits_ban between the decoder step and the grammar kernel."""
+        smer_logits_ban between the decoder step and the grammar kernel.
+        score: the graph also takes the log-probability of every drawn token
+        (smer_logprob_stage before the grammar kernel, smer_logprob_commit
+        after it) into g_logp float64 [R, cap], entry for entry with g_out."""
         dev = self.dev
         bufs = dict(
             g_state=torch.from_numpy(st).to(dev),
@@ -573,6 +576,10 @@ class DecodeSession:
         if ban is not None:
             bufs["g_banmask"] = torch.from_numpy(ban[0]).to(dev)
             bufs["g_banbits"] = torch.from_numpy(ban[1].view(np.int32)).to(dev)
+        if score:
+            bufs["g_lp_row"] = torch.zeros(self.R, 512, dtype=torch.float64, device=dev)
+            bufs["g_lp_stage"] = torch.full((self.R,), -1, dtype=torch.int32, device=dev)
+            bufs["g_logp"] = torch.zeros(self.R, cap, dtype=torch.float64, device=dev)
         # live counts: the step's grammar kernel publishes its count into a
         # pinned host ring itself (no per-step memset / D2H copy between the
         # replays); SMER_GRAMMAR_RING=0: memset + copy per step (A/B)
@@ -586,6 +593,15 @@ class DecodeSession:
         def grammar():
             if ban is not None:  # banned logits -> -100 ahead of the grammar kernel
                 ops.logits_ban(self.logits_t, self.g_state, self.g_banmask, self.g_banbits)
+            if score:  # the row's log-softmax while the row exists, the drawn token's entry after
+                ops.logprob_stage(self.logits_t, self.g_state, self.g_targets, self.g_keep,
+                                  self.g_lp_row, self.g_lp_stage)
+            entry()
+            if score:
+                ops.logprob_commit(self.g_state, self.g_lp_stage, self.g_out, self.g_lp_row, self.g_logp,
+                                   V=self.g_keep.shape[1])
+
+        def entry():
             if mode == "rows":
                 ops.grammar_sample_step_rows(self.logits_t, self.g_state, self.g_targets, self.g_keep,
                                              self.g_reject, self.g_cls, self.g_srclen, self.ids_t,
@@ -618,7 +634,7 @@ class DecodeSession:
         return g, ring, rv, t_a, t_b, t_c, bufs
 
     def sampled_decode(self, spans, keep, reject, cls, *, eos, m0, lookahead=3, max_span=100,
-                       t=1.0, p=None, seeds=None, bans=None):
+                       t=1.0, p=None, seeds=None, bans=None, score=False):
         """The sampled infill loop (the reference's sampling(): softmax with
         temperature, then weighted_sampling or, with p, nucleus, and its
         redraws) on device: each step is one replay of the captured
@@ -642,11 +658,16 @@ class DecodeSession:
         rewrites the banned logits to -100 between the vocabulary projection
         and the sampler; both tables are device data refreshed per call, so
         other constraints replay that graph.  None (or all None): the graphs
-        without that node, as ever.  Returns
+        without that node, as ever.
+        score: replay the '+score' graph of the mode instead (_grammar_decode),
+        which also takes every drawn token's log-probability at t = 1 over the
+        whole masked distribution, whatever t and p are.  Returns
         (per-request emitted ids, steps, error flags, per-request redraw
-        failure flags)."""
+        failure flags), and with score a fifth value: per request the float64
+        log-probabilities of its ids."""
         if all(sp.done for sp in spans):  # nothing to draw: np.random stays untouched
-            return [[] for _ in spans], 0, np.zeros(len(spans), dtype=np.int32), [[] for _ in spans]
+            res = [[] for _ in spans], 0, np.zeros(len(spans), dtype=np.int32), [[] for _ in spans]
+            return res + ([np.zeros(0) for _ in spans],) if score else res
         n = len(spans)
         ts = list(t) if isinstance(t, (list, tuple, np.ndarray)) else [t] * n
         ps = list(p) if isinstance(p, (list, tuple, np.ndarray)) else [p] * n
@@ -672,7 +693,8 @@ class DecodeSession:
                 mt_h[r, :624] = s0[1]
                 mt_h[r, 624] = int(s0[2])
             res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
-                                       max_span=max_span, sample=(reject, mt_h, tp_h, True), bans=bans)
+                                       max_span=max_span, sample=(reject, mt_h, tp_h, True), bans=bans,
+                                       score=score)
         else:
             st0 = np.random.get_state()
             if st0[0] != "MT19937":
@@ -681,26 +703,35 @@ class DecodeSession:
             mt_h[:624] = st0[1]
             mt_h[624] = int(st0[2])
             res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
-                                       max_span=max_span, sample=(reject, mt_h, tp_h, False), bans=bans)
+                                       max_span=max_span, sample=(reject, mt_h, tp_h, False), bans=bans,
+                                       score=score)
             m = self.g_mt.cpu().numpy().view(np.uint32)
             np.random.set_state(("MT19937", m[:624].copy(), int(m[624]), st0[3], st0[4]))
-        ids, steps, err, step_ms = res
+        ids, steps, err = res[:3]
         fails = [[(x >> 16) & 1 for x in q] for q in ids]
-        return [[x & 0xFFFF for x in q] for q in ids], steps, err, fails
+        return ([[x & 0xFFFF for x in q] for q in ids], steps, err, fails) + tuple(res[4:])
 
-    def greedy_decode(self, spans, keep, cls, *, eos, m0, lookahead=3, max_span=100, bans=None):
-        """bans: pitch constraints, as sampled_decode's."""
+    def greedy_decode(self, spans, keep, cls, *, eos, m0, lookahead=3, max_span=100, bans=None,
+                      score=False):
+        """bans: pitch constraints, as sampled_decode's.  score: the '+score'
+        graph and a fifth return value, as _grammar_decode's."""
         return self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
-                                    max_span=max_span, bans=bans)
+                                    max_span=max_span, bans=bans, score=score)
 
     def _grammar_decode(self, spans, keep, cls, *, eos, m0, lookahead=3, max_span=100, sample=None,
-                        bans=None):
+                        bans=None, score=False):
         """Run the greedy infill loop of `spans` (generation._Span, one per
         request slot 0..len-1, freshly started, sources prefilled) entirely
         on device: each step is one replay of the captured decoder step +
         grammar kernel; the host only polls the live count, `lookahead`
-        steps behind.  Returns (per-request emitted ids, steps, error flags);
-        the caller replays the ids through its host spans."""
+        steps behind.  Returns (per-request emitted ids, steps, error flags,
+        step times); the caller replays the ids through its host spans.
+        score: the call replays the '+score' graph of its mode (after '+ban',
+        if constrained), in which smer_logprob_stage / smer_logprob_commit
+        bracket the grammar kernel, and returns a fifth value: per request the
+        float64 log-probabilities of its emitted ids (generation.
+        token_logprobs at each id, t = 1, the whole masked distribution).
+        Without it: the graphs without those nodes, as ever."""
         R = len(spans)
         if R > self.R:
             raise ValueError("more spans than session slots")
@@ -731,7 +762,8 @@ class DecodeSession:
                 feeds.append((r, [m0], 0))
         st[R:, 5] = 1
         if not feeds:
-            return [[] for _ in range(R)], 0, np.zeros(R, dtype=np.int32), []
+            res = [[] for _ in range(R)], 0, np.zeros(R, dtype=np.int32), []
+            return res + ([np.zeros(0) for _ in range(R)],) if score else res
         use_ring = os.environ.get("SMER_GRAMMAR_RING", "1") != "0" or sample is not None
         # one captured graph per mode, side by side: a process that alternates
         # between greedy, unseeded and seeded calls replays, never recaptures
@@ -760,6 +792,11 @@ class DecodeSession:
             ban = (bm_h, bb_h)
             gkey += (K,)
         gname = mode if ban is None else mode + "+ban"
+        if score:  # take scores: again a graph of its own, with buffers of its own
+            if keep.shape[1] > 512:
+                raise ValueError("score: the device path scores vocabularies up to 512 tokens")
+            gname += "+score"
+            gkey += ("score",)
         graphs = self.__dict__.setdefault("_graphs", {})
         gc = graphs.get(gname)
         if gc is not None and gc["key"] == gkey:
@@ -777,6 +814,8 @@ class DecodeSession:
                 self.g_banmask.copy_(torch.from_numpy(ban[0]))
                 self.g_banbits.copy_(torch.from_numpy(ban[1].view(np.int32)))
             self.g_out.zero_()
+            if score:
+                self.g_logp.zero_()
             self.g_alive.zero_()
             g, ring = gc["graph"], gc["ring"]
             ring.zero_()
@@ -786,7 +825,8 @@ class DecodeSession:
         else:
             graphs.pop(gname, None)  # frees its buffers before the new ones are made
             g, ring, rv, t_a, t_b, t_c, bufs = self._capture_greedy(st, tg, keep, cls, cap, nm, eos, m0,
-                                                                   lookahead, max_span, use_ring, mode, ban)
+                                                                   lookahead, max_span, use_ring, mode, ban,
+                                                                   score)
             gc = graphs[gname] = {"key": gkey, "graph": g, "ring": ring, "bufs": bufs}
         self._greedy = gc  # the graph of this call
         if sample is not None:
@@ -829,4 +869,7 @@ class DecodeSession:
         out = self.g_out.cpu().numpy()
         ids = [out[r, :min(int(st[r, 7]), cap)].tolist() for r in range(R)]
         step_ms = [ev_start.elapsed_time(e) for e in events[:steps]]
+        if score:
+            lp = self.g_logp.cpu().numpy()
+            return ids, steps, st[:R, 8].copy(), step_ms, [lp[r, :len(ids[r])].copy() for r in range(R)]
         return ids, steps, st[:R, 8].copy(), step_ms

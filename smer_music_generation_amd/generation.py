@@ -26,6 +26,10 @@ Differences, all opt-in keywords with reference defaults:
   * `pitches=None` on the same three: the MIDI note numbers a request (or
     each of its tracks) may use; the other pitch tokens are masked like a
     banned token class (`pitch_set` builds ranges and scales).
+  * `logprobs=False, rank=False` on the same three: the log-probability of
+    every drawn token (`token_logprobs`: t = 1, the whole masked
+    distribution) and each take's sum in `stats`; `rank=True` orders the
+    takes of `variations=` by their mean log-probability per token.
 The grammar state machine, the -100 logit masking, the float64 softmax and
 the numpy RNG consumption are the reference's, so with the same
 `np.random` state the same token ids come out.
@@ -161,6 +165,39 @@ def sampling(logit, vocab, p=None, t=1.0, greedy=False, rng=np.random, ban=None,
     if p is not None:
         return nucleus(probs, p, rng)
     return weighted_sampling(probs, rng)
+
+
+def token_logprobs(logit, keep):
+    """float64 [V]: the log of the distribution `sampling()` builds from the
+    float32 row `logit` at t = 1, before any nucleus cut or redraw: x =
+    where(keep, float64(float32(logit)), -100.0), x - logsumexp(x).  keep
+    (boolean [V]) is what the draw used: `allowed_ids` of the grammar state,
+    `& ~ban` under a pitch constraint.  The maximum is subtracted before the
+    exp, so a row of large logits stays finite where the softmax itself
+    overflows.  A masked entry scores from its -100 like any other."""
+    x = np.where(np.asarray(keep, dtype=bool), np.asarray(logit, dtype=np.float32).astype(np.float64),
+                 -100.0)
+    m = np.max(x)
+    return x - (m + np.log(np.sum(np.exp(x - m))))
+
+
+def _check_score(logprobs, rank, variations):
+    """Validated `logprobs` / `rank` of a call: both bools, rank only with
+    variations.  Returns whether the call takes scores.  Raises ValueError;
+    touches neither the model nor np.random."""
+    for name, x in (("logprobs", logprobs), ("rank", rank)):
+        if not isinstance(x, (bool, np.bool_)):
+            raise ValueError("%s must be True or False (got %r)" % (name, x))
+    if rank and variations is None:
+        raise ValueError("rank=True orders the takes of a request: it needs variations")
+    return bool(logprobs) or bool(rank)
+
+
+def _rank_order(logps):
+    """Take indices in descending mean log-probability per drawn token (sum /
+    count; a take that drew nothing goes last), ties to the lower index."""
+    mean = [float(np.sum(a)) / len(a) if len(a) else -np.inf for a in logps]
+    return sorted(range(len(logps)), key=lambda k: (-mean[k], k))
 
 
 def _check_tp(t, p, n=None):
@@ -465,7 +502,7 @@ class _Span:
     """Decoding state of one request: mask index, span tokens, grammar flags."""
 
     def __init__(self, vocab, src, mask_target, all_controls, no_whole, greedy, logger, t=1.0,
-                 p=None, rng=np.random, bans=None):
+                 p=None, rng=np.random, bans=None, score=False):
         self.v = vocab
         self.t = t
         self.p = p
@@ -473,6 +510,11 @@ class _Span:
         # pitch constraints (_request_bans): the ban row of each mask (-1:
         # none) and the boolean rows; None: an unconstrained request
         self.ban_of_mask, self.ban_rows = bans if bans is not None else (None, None)
+        # take scores: with `score`, logp receives token_logprobs(..)[id] of
+        # every emitted id, in draw order (the host draws append it, a device
+        # path assigns its own); without, nothing is computed
+        self.score = bool(score)
+        self.logp = []
         self.src = src
         self.mask_target = mask_target
         self.all_controls = set(int(c) for c in all_controls)
@@ -512,7 +554,23 @@ class _Span:
             return None
         return self.ban_of_mask, ban_bits(self.ban_rows)
 
+    def _score(self, logit, flags, ban, idx):
+        """The emitted id's log-probability (t = 1, the whole distribution,
+        the redraws not counted) from the draw's own keep; draws nothing."""
+        if isinstance(logit, torch.Tensor):
+            logit = logit.squeeze().detach().cpu().numpy()
+        keep = allowed_ids(self.v, **flags)
+        if ban is not None:
+            keep = keep & ~np.asarray(ban, dtype=bool)
+        self.logp.append(token_logprobs(logit, keep)[int(idx)])
+
     def _draw(self, logit, check, failmsg, flags):
+        idx = self._draw_id(logit, check, failmsg, flags)
+        if self.score:
+            self._score(logit, flags, self.ban(), idx)
+        return idx
+
+    def _draw_id(self, logit, check, failmsg, flags):
         ban = self.ban()
         if ban is not None:  # (an unconstrained draw is the call it always was)
             flags = dict(flags, ban=ban)
@@ -666,7 +724,7 @@ class _Precision:
 def generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
                    bars_to_generate, *, greedy=False, use_kv_cache=True, stats=None,
                    precision="fp32", warm=True, device_grammar=True, t=1.0, p=None, variations=None,
-                   seed=None, pitches=None):
+                   seed=None, pitches=None, logprobs=False, rank=False):
     """`generation.py:468-696`.  Returns (restored '<U9' tokens,
     mask_track_names, mask_bar_names) or None (nothing masked / on error,
     after printing it, as the reference does).  `stats` (a dict, opt-in)
@@ -729,11 +787,36 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
     the constraint.  An empty set, an entry that is not an int in [21, 108]
     (bool and float included) or an unknown track raises ValueError before
     the model or np.random is touched.  `stats` receives 'pitches': None, or
-    the effective {track number: sorted tuple}."""
+    the effective {track number: sorted tuple}.
+    logprobs: False (default): today's call, and today's `stats`.  True: the
+    call also scores what it draws.  `stats` receives 'logprobs', a list with
+    one float64 array per take (one take without variations): entry j is the
+    log-probability of the take's j-th drawn token, token_logprobs(logit,
+    keep)[id] -- the log of the distribution sampling() builds from that
+    step's masked (and, under `pitches`, banned) logits at t = 1, over the
+    whole distribution -- so len(stats['logprobs'][k]) is take k's step count;
+    and 'scores', float(np.sum(..)) of each array.  Both are in take order,
+    as 'seeds' is.  The score never depends on the call's t and p and takes no
+    account of the redraw loop, so takes drawn with different settings
+    compare: it is the log-likelihood of the tokens under the model and the
+    grammar mask.  Tokens, redraw log lines, steps and the np.random state
+    afterwards are those of the call without logprobs, on every path; on the
+    device the step graphs named '+score' take the numbers between the
+    vocabulary projection and the next replay (smer_logprob_stage /
+    smer_logprob_commit), and a call without logprobs replays the graphs it
+    always did.
+    rank: True (implies scoring; needs variations) returns the takes in
+    descending mean log-probability per drawn token, scores[k] /
+    len(logprobs[k]) -- the mean, so that a short take is not favoured for
+    being short -- ties to the lower take index; `stats` receives 'order', the
+    take indices in returned order, while 'seeds', 'logprobs' and 'scores'
+    stay in take order.  Anything but a bool for either, or rank without
+    variations, raises ValueError before the model or np.random is touched."""
     t, p = _check_tp(t, p)
     n = None if variations is None else _check_variations(variations)
     seeds = _check_seed(seed, None, n)
     allowed = _check_pitches(pitches, tracks_to_generate)
+    score = _check_score(logprobs, rank, variations)
     if stats is not None:
         stats["seeds"] = seeds
         stats["pitches"] = allowed
@@ -747,9 +830,13 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
                                            return_stats=True, device_grammar=device_grammar, warm=warm,
                                            t=t, p=p, variations=[n],
                                            seed=None if seeds is None else [seeds[0]],
-                                           pitches=[allowed])
+                                           pitches=[allowed], logprobs=score, rank=bool(rank))
                 if stats is not None:
                     stats["steps"] = st["steps"]
+                    if score:
+                        stats["logprobs"], stats["scores"] = st["logprobs"], st["scores"]
+                    if rank:
+                        stats["order"] = st["order"][0]
                 return out[0]
             except Exception as e:  # reference behaviour (generation.py:695-696)
                 print(e)
@@ -758,7 +845,7 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
         return _generation_all(model, events, device, vocab, logger, all_controls,
                                tracks_to_generate, bars_to_generate, greedy, use_kv_cache, stats,
                                warm, device_grammar, t, p, None if seeds is None else seeds[0],
-                               allowed)
+                               allowed, score)
 
 
 _REJECT_CACHE = {}
@@ -798,11 +885,11 @@ def _sampled_on_device(sess, st, vocab, all_controls, logger, seed=None):
     RandomState(seed))."""
     keep, cls = grammar_tables(vocab, all_controls)
     rng0 = np.random.get_state() if seed is None else None
-    seqs, steps, err, fails = sess.sampled_decode([st], keep, reject_table(vocab), cls,
-                                                  eos=vocab.eos_index, m0=vocab.char2index('m_0'),
-                                                  t=st.t, p=st.p,
-                                                  seeds=None if seed is None else [seed],
-                                                  bans=_device_bans([st]))
+    seqs, steps, err, fails, *lps = sess.sampled_decode([st], keep, reject_table(vocab), cls,
+                                                        eos=vocab.eos_index, m0=vocab.char2index('m_0'),
+                                                        t=st.t, p=st.p,
+                                                        seeds=None if seed is None else [seed],
+                                                        bans=_device_bans([st]), score=st.score)
     if err[0] & 2:
         if seed is None:
             np.random.set_state(rng0)
@@ -815,15 +902,17 @@ def _sampled_on_device(sess, st, vocab, all_controls, logger, seed=None):
         st.commit(idx)
     if not st.done:
         raise RuntimeError("device grammar and host replay disagree")
+    if st.score:  # the device's own numbers, entry for entry with the ids
+        st.logp = list(lps[0][0])
     return len(seqs[0])
 
 
 def _generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
                     bars_to_generate, greedy, use_kv_cache, stats, warm=True, device_grammar=True,
-                    t=1.0, p=None, seed=None, allowed=None):
+                    t=1.0, p=None, seed=None, allowed=None, score=False):
     def fresh_span():  # a seeded request starts its own stream (anew after a device redo)
         rng = np.random if seed is None else np.random.RandomState(seed)
-        return _Span(vocab, src, target, all_controls, no_whole, greedy, logger, t, p, rng, bans)
+        return _Span(vocab, src, target, all_controls, no_whole, greedy, logger, t, p, rng, bans, score)
     try:
         bans = _request_bans(vocab, events, tracks_to_generate, bars_to_generate, allowed)
         src, mtn, mbn, target, no_whole = _prepare(events, vocab, tracks_to_generate,
@@ -863,6 +952,9 @@ def _generation_all(model, events, device, vocab, logger, all_controls, tracks_t
                     steps += 1
             if stats is not None:
                 stats["steps"] = steps
+                if score:
+                    stats["logprobs"] = [np.asarray(st.logp, dtype=np.float64)]
+                    stats["scores"] = [float(np.sum(stats["logprobs"][0]))]
         return restore_marked_input(_src_tokens(vocab, src), st.total), mtn, mbn
     except Exception as e:  # reference behaviour (generation.py:695-696)
         print(e)
@@ -947,7 +1039,8 @@ def _batch_session(model, R, Smax, Tmax, precision, exact_tmax=False, warm=True,
 
 def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logger=None,
                      max_tgt=None, precision=None, return_stats=False, device_grammar=True,
-                     warm=True, t=1.0, p=None, variations=None, seed=None, pitches=None):
+                     warm=True, t=1.0, p=None, variations=None, seed=None, pitches=None,
+                     logprobs=False, rank=False):
     """Decode many infill requests in lockstep on one KV-cached session.
 
     requests: list of (events, tracks_to_generate, bars_to_generate).
@@ -1000,6 +1093,18 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
     replays the '+ban' graph of its mode, whose extra kernel
     (smer_logits_ban) rewrites the banned logits ahead of the grammar
     kernel.  Validated before anything else is touched (ValueError).
+    logprobs, rank: take scores (see generation_all).  logprobs=True: the
+    stats dict receives 'logprobs' (one float64 array per entry of
+    'generated': the log-probability of each of its drawn tokens, in draw
+    order) and 'scores' (their sums); absent otherwise.  A scored call replays
+    the '+score' graph of its mode ('greedy+score', 'stream+ban+score', ..)
+    and emits the tokens of the unscored call; its host loops compute the same
+    numbers from their own logits.  rank=True (needs variations; implies
+    scoring) returns every request's takes in descending mean log-probability
+    per drawn token, ties to the lower take index, and 'order' holds one list
+    of take indices per request; 'generated', 'seeds', 'logprobs' and 'scores'
+    stay in take order.  Both are validated as bools before anything else is
+    touched (ValueError).
     Returns a list of (restored, mask_track_names, mask_bar_names) (None
     where nothing was masked), and optionally {'tokens', 'steps', 'sources',
     'prefill_rows', 'seeds' (the effective seed of every entry of 'generated',
@@ -1010,6 +1115,7 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
     takes = None if variations is None else _check_variations(variations, len(requests))
     seeds = _check_seed(seed, len(requests), takes)
     allowed = _check_pitches(pitches, [tr for _, tr, _ in requests], len(requests))
+    score = _check_score(logprobs, rank, variations)
     bans = [_request_bans(vocab, list(ev), tr, br, a) for (ev, tr, br), a in zip(requests, allowed)]
     preps = [_prepare(list(ev), vocab, tr, br) for ev, tr, br in requests]
     srcs = [q[0] for q in preps]
@@ -1020,7 +1126,7 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
 
     def fresh_spans():  # seeded: every request's stream starts (again) at its seed
         rngs = [np.random] * len(preps) if seeds is None else [np.random.RandomState(x) for x in seeds]
-        return [_Span(vocab, q[0], q[3], all_controls, q[4], greedy, logger, a, b, g, bn)
+        return [_Span(vocab, q[0], q[3], all_controls, q[4], greedy, logger, a, b, g, bn, score)
                 for q, (a, b), g, bn in zip(preps, tps, rngs, bans)]
     spans = fresh_spans()
     R = len(preps)
@@ -1049,8 +1155,9 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
             keep, cls = grammar_tables(vocab, all_controls)
             m0 = vocab.char2index('m_0')
             ts = time.perf_counter()
-            seqs, steps, err, step_ms = sess.greedy_decode(spans, keep, cls, eos=vocab.eos_index,
-                                                           m0=m0, bans=_device_bans(spans))
+            seqs, steps, err, step_ms, *lps = sess.greedy_decode(spans, keep, cls, eos=vocab.eos_index,
+                                                                 m0=m0, bans=_device_bans(spans),
+                                                                 score=score)
             t_dev = time.perf_counter() - ts
             # completion time of each request from the call's start: host
             # preparation + prefill, then the GPU end time of its last step
@@ -1076,14 +1183,17 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                 if not sp.done:
                     raise RuntimeError("device grammar and host replay disagree")
                 tokens += len(seq)
+            if score:
+                for sp, lp in zip(spans, lps[0]):
+                    sp.logp = list(lp)
         elif device_grammar and vocab.vocab_size <= 512:
             keep, cls = grammar_tables(vocab, all_controls)
             rng0 = np.random.get_state() if seeds is None else None
             ts = time.perf_counter()
-            seqs, dsteps, err, fails = sess.sampled_decode(
+            seqs, dsteps, err, fails, *lps = sess.sampled_decode(
                 spans, keep, reject_table(vocab), cls, eos=vocab.eos_index,
                 m0=vocab.char2index('m_0'), t=[a for a, _ in tps], p=[b for _, b in tps],
-                seeds=seeds, bans=_device_bans(spans))
+                seeds=seeds, bans=_device_bans(spans), score=score)
             t_dev = time.perf_counter() - ts
             if np.any(err & 2):
                 # some row's probabilities missed 1 by more than 1e-9
@@ -1111,6 +1221,9 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                     if not sp.done:
                         raise RuntimeError("device grammar and host replay disagree")
                     tokens += len(seq)
+                if score:
+                    for sp, lp in zip(spans, lps[0]):
+                        sp.logp = list(lp)
         while True:
             live = [i for i in range(R) if not spans[i].done]
             if not live:
@@ -1134,6 +1247,8 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                         keep[k] &= ~ban
                 ids = np.argmax(np.where(keep, lg, np.float32(-100.0)), axis=1)
                 for k, i in enumerate(live):
+                    if score:  # the argmax is taken outside _draw: score it from the same keep row
+                        spans[i].logp.append(token_logprobs(lg[k], keep[k])[ids[k]])
                     spans[i].commit_greedy(ids[k], specs[k][1], specs[k][2])
             else:
                 for k, i in enumerate(live):
@@ -1146,15 +1261,24 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
             out.append(None)
             continue
         out.append((restore_marked_input(_src_tokens(vocab, q[0]), st.total), q[1], q[2]))
+    lp_all = [np.asarray(st.logp, dtype=np.float64) for st in spans] if score else None
+    order = None
     if takes is not None:  # entry i: the list of request i's takes
-        nested, k0 = [], 0
+        nested, order, k0 = [], [], 0
         for n in takes:
-            nested.append(None if out[k0] is None else out[k0:k0 + n])
+            ks = _rank_order(lp_all[k0:k0 + n]) if rank else list(range(n))
+            order.append(ks)
+            nested.append(None if out[k0] is None else [out[k0 + k] for k in ks])
             k0 += n
         out = nested
     if return_stats:
         t3 = time.perf_counter()
-        return out, {"tokens": tokens, "steps": steps, "prepare_s": t1 - t0,
+        extra = {}
+        if score:
+            extra = {"logprobs": lp_all, "scores": [float(np.sum(a)) for a in lp_all]}
+        if rank:
+            extra["order"] = order
+        return out, {**extra, "tokens": tokens, "steps": steps, "prepare_s": t1 - t0,
                      "prefill_s": t2 - t1, "decode_s": t3 - t2, "step_call_s": t_dev,
                      "request_latency_s": latency, "kv_row_reads": kv_reads,
                      "generated": [list(st.total) for st in spans],

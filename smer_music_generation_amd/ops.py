@@ -744,6 +744,58 @@ def logits_ban(logits, state, ban_of_mask, ban_bits):
          _p(ban_of_mask), _p(ban_bits), ban_bits.shape[1], _stream())
 
 
+def logprob_stage(logits, state, targets, keep, scratch, stage):
+    """Take scores, ahead of a grammar step (smer_logprob_stage; after
+    logits_ban, if any): for every request r that is not done, the float64
+    log-softmax of where(keep[state code], float64(logits row 2r + 1), -100.0)
+    lands in scratch[r, :V] and the request's token count in stage[r]; a done
+    request gets stage[r] = -1.  logits float32 [>= 2R, V <= 512] (rows
+    contiguous), state int32 [R, nst], targets int8 [R, max_masks], keep
+    uint8 [13, V] (the grammar step's own tables), scratch float64 [R, >= V]
+    (rows contiguous), stage int32 [R].  Logits and state are only read."""
+    R, nst = state.shape
+    V = logits.shape[1]
+    for t, dt in ((logits, torch.float32), (state, torch.int32), (targets, torch.int8),
+                  (keep, torch.uint8), (scratch, torch.float64), (stage, torch.int32)):
+        if t.dtype != dt or t.device != logits.device:
+            raise RuntimeError("logprob_stage: expected %s on the logits' device" % dt)
+    if not (state.is_contiguous() and targets.is_contiguous() and keep.is_contiguous() and
+            stage.is_contiguous()) or logits.dim() != 2 or logits.stride(1) != 1 or \
+            scratch.dim() != 2 or scratch.stride(1) != 1:
+        raise RuntimeError("logprob_stage: expected contiguous tables, logits rows and scratch rows")
+    if logits.shape[0] < 2 * R or targets.dim() != 2 or targets.shape[0] != R or targets.shape[1] < 1 or \
+            tuple(keep.shape) != (13, V) or scratch.shape[0] != R or scratch.shape[1] < V or \
+            stage.numel() != R or not 9 <= nst <= 64 or V > 512:
+        raise RuntimeError("logprob_stage: shape mismatch")
+    call("smer_logprob_stage", R, V, _p(logits), _ld(logits), _p(state), nst, _p(targets),
+         targets.shape[1], _p(keep), _p(scratch), _ld(scratch), _p(stage), _stream())
+
+
+def logprob_commit(state, stage, out_tok, scratch, out_lp, *, V):
+    """Take scores, after the grammar step (smer_logprob_commit): a request
+    whose stage slot c is in [0, cap) and whose token count is now c + 1 drew
+    out_tok[r, c] in this step; out_lp[r, c] = scratch[r, out_tok[r, c] &
+    0xFFFF].  Nothing else is written.  state int32 [R, nst], stage int32 [R],
+    out_tok int32 [R, cap], scratch float64 [R, >= V] (rows contiguous),
+    out_lp float64 [R, cap]; V <= 512: the vocabulary size logprob_stage ran
+    with."""
+    R, nst = state.shape
+    V = int(V)
+    for t, dt in ((state, torch.int32), (stage, torch.int32), (out_tok, torch.int32),
+                  (scratch, torch.float64), (out_lp, torch.float64)):
+        if t.dtype != dt or t.device != state.device:
+            raise RuntimeError("logprob_commit: expected %s on the state's device" % dt)
+    if not (state.is_contiguous() and stage.is_contiguous() and out_tok.is_contiguous() and
+            out_lp.is_contiguous()) or scratch.dim() != 2 or scratch.stride(1) != 1:
+        raise RuntimeError("logprob_commit: expected contiguous tables and scratch rows")
+    if stage.numel() != R or out_tok.dim() != 2 or out_tok.shape[0] != R or \
+            tuple(out_lp.shape) != tuple(out_tok.shape) or scratch.shape[0] != R or \
+            scratch.shape[1] < V or not 1 <= V <= 512 or nst < 9:
+        raise RuntimeError("logprob_commit: shape mismatch")
+    call("smer_logprob_commit", R, V, _p(state), nst, _p(stage), _p(out_tok), out_tok.shape[1],
+         _p(scratch), _ld(scratch), _p(out_lp), _stream())
+
+
 # ---------------------------------------------------------------------------
 def layernorm(x, gamma, beta, y, mean, rstd, eps=1e-5):
     M, N = x.shape
