@@ -1,0 +1,259 @@
+"""smer_attn_fwd / smer_attn_bwd / smer_attn_weights (csrc/attention.hip)
+against the float64 reference of tests/attnref.py, element by element, at the
+shapes where their dispatch changes (attnref.SHAPES: single query / key, the
+16-row and 64-key edges, Lq != Lk with and without causal, the two-group
+QG = 2 / KG = 2 kernels with ragged and empty second groups, D = 128) and
+under every padding pattern of attnref.MASK_KINDS, one per sequence.
+
+Bounds (attnref's docstring has the rule and the term magnitudes T):
+ * bf16: ATTN_REL_x * T + 2**-8 |ref| per element with ATTN_REL_O 0.0232,
+   ATTN_REL_DQ 0.01016, ATTN_REL_DK 0.01792, ATTN_REL_DV 0.02752, lse to
+   ATTN_ABS_LSE 0.02848: four times the worst error of the CPU emulation of
+   the kernels' bf16 roundings (tests/test_attention_ref_cpu.py), never tuned
+   against the kernels;
+ * fp32: (k + 2) * 2**-24 * T, k = Lk + D (O, dQ) or Lq + D (dK, dV);
+ * the mask test (Q = 0, integer V): one bf16 rounding, 2**-8 |ref| (2**-7
+   with dropout), lse = ln n to 1e-6: one wrongly visible or hidden key moves
+   an element by |v| / n;
+ * exact: O = 0, lse = +inf, dQ = 0 for a query without a visible key; zero
+   bits in the dK / dV rows of a padded key; every sentinel around the
+   outputs (pad columns, rows after B*L, lse tail) untouched.
+Q, K and V are column slices of one fused buffer, the gradients slices of a
+sentinel-filled one.  Dropout runs are checked through the reference against
+tests/hashref.attn_keep_mask for each way the kernels obtain the keep bits.
+"""
+import math
+
+import pytest
+import torch
+
+from tests import attnref as A
+from tests.hashref import attn_scale
+from tests.test_train_ops_gpu import assert_within, bits, pads_intact
+
+pytestmark = pytest.mark.gpu
+
+dev = "cuda"
+F32, BF16 = torch.float32, torch.bfloat16
+SENT = 123.0  # sentinel (exact in bf16)
+SEED = A.DROP_SEED
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _lib():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from smer_music_generation_amd import _lib as L
+    L.load()
+
+
+def ops():
+    from smer_music_generation_amd import ops as O
+    return O
+
+
+def sentinel_intact(t, what):
+    t = t.cpu()
+    assert torch.equal(bits(t), bits(torch.full_like(t, SENT))), what + ": sentinel overwritten"
+
+
+class Call:
+    """Device buffers of one (shape, dtype, masks) call: Q / K / V as column
+    slices of one fused [rows, 3*H*D] buffer."""
+
+    def __init__(self, shape, dtype, kinds, exact=False):
+        self.shape, self.dtype, self.kinds = shape, dtype, tuple(kinds)
+        B, H, Lq, Lk, D, causal = shape
+        self.HD = HD = H * D
+        self.cpu = A.inputs(shape, dtype, exact)
+        q, k, v, do = self.cpu
+        fused = torch.full((B * max(Lq, Lk), 3 * HD), SENT, dtype=dtype)
+        fused[:B * Lq, :HD], fused[:B * Lk, HD:2 * HD], fused[:B * Lk, 2 * HD:] = q, k, v
+        fused = fused.to(dev)
+        self.q, self.k, self.v = fused[:B * Lq, :HD], fused[:B * Lk, HD:2 * HD], fused[:B * Lk, 2 * HD:]
+        self.do = do.to(dev)
+        self.kpm_cpu = A.make_kpm(kinds, Lk)
+        self.kpm = self.kpm_cpu.to(dev)
+        self.kw = dict(B=B, H=H, Lq=Lq, Lk=Lk, D=D, kpm=self.kpm, causal=causal, scale=A.scale_of(D))
+        self.what = "%s %s %s" % (A.shape_id(shape), str(dtype)[6:], "/".join(kinds))
+
+    def fwd(self, what, **kw):
+        """O [B*Lq, H*D] and lse [B, H, Lq] of a forward, written into
+        sentinel-framed buffers that are checked afterwards."""
+        B, H, Lq, Lk, D, causal = self.shape
+        obuf = torch.full((B * Lq + 2, self.HD + 16), SENT, dtype=self.dtype, device=dev)
+        lbuf = torch.full((B * H * Lq + 16,), SENT, dtype=F32, device=dev)
+        o, lse = obuf[:B * Lq, :self.HD], lbuf[:B * H * Lq].view(B, H, Lq)
+        ops().attn_fwd(self.q, self.k, self.v, o, lse, **self.kw, **kw)
+        torch.cuda.synchronize()
+        pads_intact(obuf[:B * Lq], self.HD, SENT, what + " O")
+        sentinel_intact(obuf[B * Lq:], what + " rows after O")
+        sentinel_intact(lbuf[B * H * Lq:], what + " lse tail")
+        return o, lse
+
+    def bwd(self, o, lse, what, **kw):
+        B, H, Lq, Lk, D, causal = self.shape
+        HD = self.HD
+        g = torch.full((B * max(Lq, Lk) + 3, 3 * HD + 8), SENT, dtype=self.dtype, device=dev)
+        dq, dk, dv = g[:B * Lq, :HD], g[:B * Lk, HD:2 * HD], g[:B * Lk, 2 * HD:3 * HD]
+        ops().attn_bwd(self.q, self.k, self.v, o, self.do, lse, dq, dk, dv, **self.kw, **kw)
+        torch.cuda.synchronize()
+        pads_intact(g, 3 * HD, SENT, what + " gradients")
+        sentinel_intact(g[B * Lq:, :HD], what + " rows after dQ")
+        sentinel_intact(g[B * Lk:, HD:3 * HD], what + " rows after dK / dV")
+        return dq, dk, dv
+
+    def check_lse(self, lse, ref, bound, what):
+        lse = lse.cpu()
+        assert torch.equal(lse == math.inf, ~ref.has), what + ": lse = +inf iff no visible key"
+        z = torch.zeros_like(ref.lse)
+        assert_within(torch.where(ref.has, lse.double(), z), torch.where(ref.has, ref.lse, z), bound, what + " lse")
+
+    def check_fwd(self, o, lse, ref, bounds, lse_bound, what):
+        assert torch.isfinite(o).all(), what + ": O not finite"
+        assert_within(o, ref.O, bounds["O"], what + " O")  # (a zero bound: rows without a visible key)
+        self.check_lse(lse, ref, lse_bound, what)
+
+    def check_bwd(self, grads, ref, bounds, what):
+        B, H, Lq, Lk, D, causal = self.shape
+        dq, dk, dv = grads
+        for name, g in (("dQ", dq), ("dK", dk), ("dV", dv)):
+            assert torch.isfinite(g).all(), "%s: %s not finite" % (what, name)
+            assert_within(g, getattr(ref, name), bounds[name], "%s %s" % (what, name))
+        padded = self.kpm_cpu.bool().view(B * Lk)
+        assert not bits(dk)[padded].any() and not bits(dv)[padded].any(), what + ": padded keys' dK / dV bits"
+        blind = ~ref.has.permute(0, 2, 1).reshape(B * Lq, H)  # [row, head]
+        assert (dq.cpu().view(B * Lq, H, D)[blind] == 0).all(), what + ": dQ of queries without a visible key"
+
+
+def mask_sets(shape):
+    return A.mask_sets(shape[0], shape[3])
+
+
+# ------------------------------------------------------- 3a. exact mask test
+def _exact_expected(c, p):
+    B, H, Lq, Lk, D, causal = c.shape
+    vis = A.visible(B, Lq, Lk, c.kpm_cpu, causal).expand(B, H, Lq, Lk)
+    n = vis.sum(-1).double()
+    kept = vis & A.keep_mask(c.shape, p) if p else vis
+    v = A._heads(c.cpu[2], B, Lk, H, D)
+    o = (kept.double() @ v) * A.f32r(attn_scale(p)) / n.clamp_min(1).unsqueeze(-1)
+    return A._rows(o), n
+
+
+@pytest.mark.parametrize("shape", A.SHAPES, ids=A.shape_id)
+def test_mask_exact(shape):
+    """Q = 0 and integer V: O = (survivor scale) * sum of the visible, kept
+    V rows / n, lse = ln n, exactly up to the stores' rounding."""
+    B, H, Lq, Lk, D, causal = shape
+    O = ops()
+    for kinds in mask_sets(shape):
+        c = Call(shape, BF16, kinds, exact=True)
+        runs = [(0.0, "plain", {})]
+        for p in A.drop_rates(*shape):
+            gen = O.attn_drop_mask(B, H, Lq, Lk, dev)
+            O.attn_drop_mask_gen(gen, B=B, H=H, Lq=Lq, Lk=Lk, drop_p=p, seed=SEED)
+            runs += [(p, "hashing", dict(drop_p=p, seed=SEED)),
+                     (p, "filling a buffer", dict(drop_p=p, seed=SEED, drop_mask=O.attn_drop_mask(B, H, Lq, Lk, dev))),
+                     (p, "drop_mask_in", dict(drop_p=p, seed=SEED, drop_mask=gen, drop_mask_in=True))]
+        for p, mode, kw in runs:
+            what = "%s p=%g %s" % (c.what, p, mode)
+            o, lse = c.fwd(what, **kw)
+            want, n = _exact_expected(c, p)
+            assert_within(o, want, (2.0 ** -7 if p else 2.0 ** -8) * want.abs(), what + " O")
+            lse = lse.cpu()
+            assert torch.equal(lse == math.inf, n == 0), what + ": lse = +inf iff n = 0"
+            assert_within(torch.where(n > 0, lse.double(), n), torch.log(n.clamp_min(1)), 1e-6, what + " lse")
+            blind = (n == 0).permute(0, 2, 1).reshape(B * Lq, H)
+            assert not bits(o).view(B * Lq, H, D)[blind].any(), what + ": O bits of queries with n = 0"
+
+
+# ------------------------------------------------------ 3b. float64 parity
+def _parity(c, p, monkeypatch=None):
+    B, H, Lq, Lk, D, causal = c.shape
+    O = ops()
+    ref = A.reference(c.shape, c.kinds, c.dtype, p)
+    drop = dict(drop_p=p, seed=SEED) if p else {}
+    if c.dtype == BF16:
+        bounds, lse_bound = A.bf16_bounds(ref), A.ATTN_ABS_LSE
+    else:
+        bounds = A.f32_bounds(ref, Lq, Lk, D)
+        lse_bound = A.f32_lse_bound(c.cpu[0], c.cpu[1], ref, B, H, Lq, Lk, D, A.scale_of(D))
+    what = "%s p=%g" % (c.what, p)
+    if c.dtype == F32:
+        for mfma in ("1", "0"):  # (dropout and D != 64 stay on attn_fwd_f32 either way)
+            monkeypatch.setenv("SMER_ATTN_F32_MFMA", mfma)
+            o, lse = c.fwd(what, **drop)
+            c.check_fwd(o, lse, ref, bounds, lse_bound, "%s fwd(MFMA=%s)" % (what, mfma))
+        c.check_bwd(c.bwd(o, lse, what, **drop), ref, bounds, what + " bwd")
+        return
+    if not p:
+        o, lse = c.fwd(what)
+        c.check_fwd(o, lse, ref, bounds, lse_bound, what + " fwd")
+        c.check_bwd(c.bwd(o, lse, what), ref, bounds, what + " bwd")
+        return
+    # dropout, each way of obtaining the keep bits, each against the reference
+    o, lse = c.fwd(what, **drop)
+    c.check_fwd(o, lse, ref, bounds, lse_bound, what + " fwd hashing")
+    c.check_bwd(c.bwd(o, lse, what, **drop), ref, bounds, what + " bwd hashing")
+    mask = O.attn_drop_mask(B, H, Lq, Lk, dev)
+    o, lse = c.fwd(what, drop_mask=mask, **drop)
+    c.check_fwd(o, lse, ref, bounds, lse_bound, what + " fwd filling a buffer")
+    c.check_bwd(c.bwd(o, lse, what, drop_mask=mask, **drop), ref, bounds, what + " bwd reading the buffer")
+    gen = O.attn_drop_mask(B, H, Lq, Lk, dev)
+    O.attn_drop_mask_gen(gen, B=B, H=H, Lq=Lq, Lk=Lk, drop_p=p, seed=SEED)
+    o, lse = c.fwd(what, drop_mask=gen, drop_mask_in=True, **drop)
+    c.check_fwd(o, lse, ref, bounds, lse_bound, what + " fwd drop_mask_in")
+    c.check_bwd(c.bwd(o, lse, what, drop_mask=gen, **drop), ref, bounds, what + " bwd reading the generated buffer")
+
+
+@pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("shape", A.SHAPES, ids=A.shape_id)
+def test_parity(monkeypatch, shape, dtype):
+    for kinds in mask_sets(shape):
+        _parity(Call(shape, dtype, kinds), 0.0, monkeypatch)
+
+
+DROP_SHAPES = [s for s in A.SHAPES if A.drop_rates(*s)]
+
+
+@pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("shape", DROP_SHAPES, ids=A.shape_id)
+def test_parity_dropout(monkeypatch, shape, dtype):
+    for kinds in mask_sets(shape):
+        for p in A.drop_rates(*shape):
+            _parity(Call(shape, dtype, kinds), p, monkeypatch)
+
+
+# ------------------------------------------------- 3c. smer_attn_weights
+@pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])
+@pytest.mark.parametrize("Lq,Lk", [(17, 65), (70, 130), (130, 70)])
+def test_weights(Lq, Lk, causal, dtype):
+    """Head-averaged probabilities from the forward's own lse against the
+    float64 softmax.  attn_weights_kernel adds exp(s - lse) only for a visible
+    key, so a query without a visible key (lse = +inf, never read) gets a row
+    of zero bits.  fp32: Lk * 2**-24 plus the lse bound (p <= 1, so an lse
+    error moves p by at most as much); bf16: the scores are exact fp32 sums of
+    the bf16 inputs, the lse is the bf16 forward's, within ATTN_ABS_LSE:
+    p * expm1(ATTN_ABS_LSE), plus the fp32 part."""
+    B, H, D = 2, 3, 64
+    shape = (B, H, Lq, Lk, D, causal)
+    for kinds in mask_sets(shape):
+        c = Call(shape, dtype, kinds)
+        ref = A.reference(shape, c.kinds, dtype, 0.0)
+        o, lse = c.fwd(c.what)
+        wbuf = torch.full((B * Lq * Lk + 16,), SENT, dtype=F32, device=dev)
+        w = wbuf[:B * Lq * Lk].view(B, Lq, Lk)
+        ops().attn_weights(c.q, c.k, lse, w, **c.kw)
+        torch.cuda.synchronize()
+        sentinel_intact(wbuf[B * Lq * Lk:], c.what + " weights tail")
+        want, psabs = A.weights_ref64(c.cpu[0], c.cpu[1], ref.lse, B, H, Lq, Lk, D, c.kpm_cpu, causal, A.scale_of(D))
+        lse_b = A.f32_lse_bound(c.cpu[0], c.cpu[1], ref, B, H, Lq, Lk, D, A.scale_of(D)).max(1).values.unsqueeze(-1)
+        bound = Lk * A.U + lse_b
+        if dtype == BF16:
+            bound = bound + want * math.expm1(A.ATTN_ABS_LSE)
+        assert_within(w, want, bound.expand_as(want), c.what + " weights")
+        blind = ~ref.has.all(1)  # [B, Lq] (visibility does not depend on the head)
+        assert torch.equal(ref.has.all(1), ref.has.any(1))
+        assert not bits(w)[blind].any(), c.what + ": weights of queries without a visible key"
