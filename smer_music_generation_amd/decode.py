@@ -26,6 +26,7 @@ from __future__ import annotations
 import math
 import os
 import time
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -48,6 +49,169 @@ def _capture(stream, fn):
         finally:
             g.capture_end()
     return g
+
+
+class _StepPlan(NamedTuple):
+    """How a session's decoder step runs (DecodeSession._plan): every field
+    follows from the precision, the shapes and the SMER_DECODE_* switches."""
+    # post-norm LayerNorms in the prologue of the Linear that consumes them
+    # (ops.linear_decode_ln: LN3 -> next QKV, LN1 -> cross Q, LN2 -> FFN1, final
+    # norm -> vocab head; the LN output also stored as the next residual, the
+    # LayerNorm kernel's bits) and the new K/V appended by the QKV epilogue:
+    # bf16 7-8 launches per layer (11 in round 1), fp32 8 instead of 12.
+    # False: one kernel per LayerNorm, kv_scatter after the QKV Linear.
+    fused: bool
+    # LN1 + the cross query projection inside the cross-attention blocks.
+    # bf16: re-reads the head's Wq slice per (row, head) block: 329 vs 342 us
+    # per replayed step at R = 32, 484 vs 480 at R = 64
+    # (tools/decode_host_probe.py).  It rounds q in a different order than the
+    # Linear, so the choice must not depend on the batch (a request's tokens
+    # may not depend on its batch-mates): on whenever the shape allows it.
+    # fp32: inside the split attention blocks, few rows only (batch 1-2: one
+    # launch fewer per layer; each block re-reads its head's 128 KB of Wq from
+    # L2, so not for many rows).
+    qln: bool
+    # cross attention reads the row's SOURCE slot: takes that share a source
+    # share one prefill and one memory, and the per-row kernels read it through
+    # the indirection.  shared (SMER_DECODE_SHARED=1, fewer sources than
+    # requests, bf16): the grouped kernels instead, which load each K / V key
+    # step once per chunk of a group's rows and write the per-row kernels'
+    # bits.  Off by default: measured slower (C2 shapes, 4 sources x 8 takes:
+    # 426 vs 289 us per replayed step, tools/variations_probe.py, DESIGN 5j) --
+    # the repeated reads of the per-row blocks hit in the caches, and the
+    # grouped form leaves 64 walking blocks for 256 CUs.  Never with two
+    # chains: a half's group table would be another one.  (fp32 has no grouped
+    # kernel: takes run the per-row kernels on the source's slot.)
+    shared: bool
+    # fp32 cross attention as flash-decoding (8 key slices per (row, head),
+    # merged in the out-projection's prologue): the unsplit form runs
+    # 2 * R * H blocks, 16 at batch 1.  (The self attention stays unsplit: its
+    # <= ~400-key caches measured 0.306 vs 0.296 ms per step split.)
+    split_f32: bool
+    # request chains per step.  SMER_DECODE_CHAINS=2 (bf16) splits the requests
+    # into two halves on two graph branches; measured slower (C2 364 vs 326 us
+    # per replay, C5 888 vs 871: tools/decode_chain_probe.py), so one chain is
+    # the default.
+    chains: int
+
+
+class _Sampler(NamedTuple):
+    """The sampler's inputs of one call (host arrays)."""
+    reject: np.ndarray   # uint8 [13, V]: generation.reject_table
+    mt: np.ndarray       # uint32 MT19937 key + position: [625], per_request [R, LDMT]
+    tp: np.ndarray       # float64 [R, 2]: temperature, nucleus p (-1 = none)
+    per_request: bool    # one stream per request (the "rows" graphs)
+
+
+class DecodeResult(NamedTuple):
+    """What greedy_decode / sampled_decode return; None where a field does not
+    apply to the call."""
+    ids: list       # per request the emitted token ids
+    steps: int
+    err: np.ndarray  # per request: bit 0 prefix exceeds max_tgt, bit 1 probabilities missed 1
+    step_ms: list   # GPU end time of each step from the loop's start
+    fails: list = None  # sampled: per request, per id, 1 = the redraws ran out
+    logp: list = None   # score: per request the float64 log-probabilities of its ids
+
+    @classmethod
+    def empty(cls, n, sampled, score):
+        return cls([[] for _ in range(n)], 0, np.zeros(n, dtype=np.int32), [],
+                   [[] for _ in range(n)] if sampled else None,
+                   [np.zeros(0) for _ in range(n)] if score else None)
+
+
+class _GrammarGraph:
+    """One captured (decoder step + grammar) graph of a session and the
+    buffers it addresses, which are its own: the graphs of the other modes
+    keep theirs.  mode: "greedy", "stream" (the sampler on the one shared
+    MT19937 stream) or "rows" (the sampler on one stream per request).
+    ban: the graph runs smer_logits_ban between the decoder step and the
+    grammar kernel.  score: it also takes the log-probability of every drawn
+    token (smer_logprob_stage before the grammar kernel, smer_logprob_commit
+    after it) into g_logp float64 [R, cap], entry for entry with g_out.
+    Construction allocates; load() writes a call's inputs, before the capture
+    and before every later call alike."""
+
+    def __init__(self, sess, key, mode, nm, keep_shape, cls_shape, *, eos, m0, lookahead, max_span,
+                 use_ring, ban, score):
+        self.key, self.mode, self.ban, self.score = key, mode, ban, score
+        self.graph = None
+        R, cap, dev = sess.R, sess.Tmax, sess.dev
+
+        def zeros(*shape, dtype=torch.int32):
+            return torch.zeros(*shape, dtype=dtype, device=dev)
+        b = self.bufs = dict(
+            g_state=zeros(R, sess.N_STATE), g_targets=zeros(R, nm, dtype=torch.int8),
+            g_keep=zeros(keep_shape, dtype=torch.uint8), g_cls=zeros(cls_shape, dtype=torch.uint8),
+            g_srclen=zeros(R), g_out=zeros(R, cap))
+        if mode != "greedy":
+            b["g_reject"] = zeros(keep_shape, dtype=torch.uint8)
+            b["g_tp"] = zeros(R, 2, dtype=torch.float64)
+            if mode == "rows":
+                b["g_mt_rows"] = zeros(R, sess.LDMT)
+            else:
+                b["g_mt"] = zeros(625)
+        if ban:
+            b["g_banmask"] = zeros(R, nm, dtype=torch.int8)
+            b["g_banbits"] = zeros(R, sess.BAN_K, ops.BAN_WORDS)
+        if score:
+            b["g_lp_row"] = zeros(R, 512, dtype=torch.float64)
+            b["g_lp_stage"] = torch.full((R,), -1, dtype=torch.int32, device=dev)
+            b["g_logp"] = zeros(R, cap, dtype=torch.float64)
+        # live counts: the step's grammar kernel publishes its count into a
+        # pinned host ring itself (no per-step memset / D2H copy between the
+        # replays); SMER_GRAMMAR_RING=0: memset + copy per step (A/B)
+        self.ring = torch.zeros(2 * lookahead + 2, dtype=torch.int32).pin_memory()
+        self.rv = self.ring.numpy()
+        b["g_alive"] = zeros(3 if use_ring else 1)
+        self.gargs = dict(eos=eos, m0=m0, trash_pos=sess.Tmax - 1, max_span=max_span,
+                          ring=self.ring if use_ring else None)
+
+    def load(self, st, tg, keep, cls, src_len, ban=None, sampler=None):
+        """Write one call's inputs (host arrays) and clear its outputs."""
+        b = self.bufs
+
+        def up(name, a):
+            b[name].copy_(torch.from_numpy(a))
+        up("g_state", st)
+        up("g_targets", tg)
+        up("g_keep", np.ascontiguousarray(keep, dtype=np.uint8))
+        up("g_cls", np.ascontiguousarray(cls, dtype=np.uint8))
+        up("g_srclen", src_len.astype(np.int32))
+        if self.ban:
+            up("g_banmask", ban[0])
+            up("g_banbits", ban[1].view(np.int32))
+        if self.mode != "greedy":
+            up("g_reject", np.ascontiguousarray(sampler.reject, dtype=np.uint8))
+            up("g_mt_rows" if self.mode == "rows" else "g_mt", sampler.mt.view(np.int32))
+            up("g_tp", sampler.tp)
+        b["g_out"].zero_()
+        if self.score:
+            b["g_logp"].zero_()
+        b["g_alive"].zero_()
+        self.ring.zero_()
+
+    def step(self, logits, ids, meta):
+        """The launches that follow the decoder step inside the graph: they
+        pick every request's token from `logits` and write the next step's
+        feed into the session's row tables `ids` and `meta`."""
+        b = self.bufs
+        state, targets, keep = b["g_state"], b["g_targets"], b["g_keep"]
+        if self.ban:  # banned logits -> -100 ahead of the grammar kernel
+            ops.logits_ban(logits, state, b["g_banmask"], b["g_banbits"])
+        if self.score:  # the row's log-softmax while the row exists, the drawn token's entry after
+            ops.logprob_stage(logits, state, targets, keep, b["g_lp_row"], b["g_lp_stage"])
+        if self.mode == "greedy":
+            ops.grammar_greedy_step(logits, state, targets, keep, b["g_cls"], b["g_srclen"], ids, meta,
+                                    b["g_out"], b["g_alive"], **self.gargs)
+        else:
+            rows = self.mode == "rows"
+            (ops.grammar_sample_step_rows if rows else ops.grammar_sample_step)(
+                logits, state, targets, keep, b["g_reject"], b["g_cls"], b["g_srclen"], ids, meta,
+                b["g_out"], b["g_mt_rows" if rows else "g_mt"], b["g_alive"], tp=b["g_tp"], **self.gargs)
+        if self.score:
+            ops.logprob_commit(state, b["g_lp_stage"], b["g_out"], b["g_lp_row"], b["g_logp"],
+                               V=keep.shape[1])
 
 
 class DecodeSession:
@@ -106,10 +270,15 @@ class DecodeSession:
         self.graph = None
         # step(): the row-table H2D and logits D2H copies inside the step graph
         self._graph_copies = os.environ.get("SMER_DECODE_GRAPH_COPY", "1") == "1"
-        self.logits_t = None
+        self.logits_t = torch.empty(M, eng.V, device=dev)
         # the positional table the captured graphs address (pos_enc.extend()
         # by a later session reallocates it: _pe_guard drops stale graphs)
         self._pe_ptr = model.pos_enc.pe.data_ptr()
+        self.plan = None      # the _StepPlan of the last _run (None: no step has run yet)
+        self._side = None     # the second chain's stream, made on first use
+        self._graphs = {}     # name ("greedy", "stream+ban", "rows+ban+score", ..) -> _GrammarGraph
+        self._greedy = None   # the _GrammarGraph of the last call
+        self.phase_s = {}     # host seconds of the last device loop's phases (bench / probes)
 
     def _pe_guard(self):
         """Drop the captured step / greedy graphs when the model's
@@ -117,10 +286,7 @@ class DecodeSession:
         pos_enc.extend() freed the buffer they read)."""
         ptr = self.model.pos_enc.pe.data_ptr()
         if ptr != self._pe_ptr:
-            self.graph = None
-            self._graphs = {}
-            self._greedy = None
-            self._pe_ptr = ptr
+            self.graph, self._graphs, self._greedy, self._pe_ptr = None, {}, None, ptr
 
     def refresh_weights(self):
         self.W = self.eng.weights(self.dt)
@@ -227,232 +393,139 @@ class DecodeSession:
         return lens
 
     # ------------------------------------------------------------------
+    def _plan(self):
+        """The step plan of this session under the current switches."""
+        d, M, D = self.d, self.M, self.eng.D
+        if self.dt == torch.float32:
+            # the fused fp32 layers need the LayerNorm-prologue Linear's limits
+            # (K = d_model a multiple of 8, at most 2048); other widths unfused
+            fused = (M <= 64 and d % 8 == 0 and d <= 2048
+                     and os.environ.get("SMER_DECODE_F32_FUSED", "1") == "1")
+            split = fused and D == 64 and os.environ.get("SMER_DECODE_SPLIT_F32", "1") == "1"
+            qln = split and d == 512 and M <= 4 and os.environ.get("SMER_DECODE_QLN_F32", "1") == "1"
+            return _StepPlan(fused, qln, False, split, 1)
+        if self.dt != torch.bfloat16:
+            return _StepPlan(False, False, False, False, 1)
+        chains = 2 if self.R >= 2 and os.environ.get("SMER_DECODE_CHAINS", "1") == "2" else 1
+        qln = D == 64 and d in (512, 768, 1024) and os.environ.get("SMER_DECODE_QLN", "1") == "1"
+        shared = (self.NS < self.R and D in (32, 64) and chains == 1
+                  and os.environ.get("SMER_DECODE_SHARED", "0") == "1")
+        return _StepPlan(True, qln, shared, False, chains)
+
     def _run(self):
         """The fixed-shape decoder step on the static buffers."""
-        eng, W, dt, dev, d = self.eng, self.W, self.dt, self.dev, self.d
-        H, D, M = eng.H, eng.D, self.M
-        pos_t, req_t, nks_t, nkc_t = self.meta_t[0], self.meta_t[1], self.meta_t[2], self.meta_t[3]
-        src_t = self.src_t  # cross attention: the row's SOURCE slot
+        eng, W, d, M = self.eng, self.W, self.d, self.M
+        plan = self.plan = self._plan()
         pe = self.model.pos_enc.pe
         pe2 = pe.view(pe.shape[0], pe.shape[2])
-        x = torch.empty(M, d, dtype=dt, device=dev)
-        ops.embed(self.ids_t, W.emb, pe2, x, positions=pos_t, scale=math.sqrt(d))
-        scale = 1.0 / math.sqrt(D)
-        sstride = self.Tmax * 2 * d
-        cstride = 2 * H * self.Smax * D
-        # the fused fp32 layers need the LayerNorm-prologue Linear's limits
-        # (K = d_model a multiple of 8, at most 2048); other widths unfused
-        if (dt == torch.float32 and M <= 64 and d % 8 == 0 and d <= 2048
-                and os.environ.get("SMER_DECODE_F32_FUSED", "1") == "1"):
-            if self.logits_t is None:
-                self.logits_t = torch.empty(M, eng.V, device=dev)
-            self._run_fused_layers_f32(x, scale, sstride, cstride)
+        x = torch.empty(M, d, dtype=self.dt, device=self.dev)
+        ops.embed(self.ids_t, W.emb, pe2, x, positions=self.meta_t[0], scale=math.sqrt(d))
+        if plan.chains == 1:
+            self._run_layers(plan, x, 0, M)
             return
-        fused = dt == torch.bfloat16
-        if fused:
-            if self.logits_t is None:
-                self.logits_t = torch.empty(M, eng.V, device=dev)
-            chains = self._chains()
-            if chains == 1:
-                self._run_fused_layers(x, scale, sstride, cstride, 0, M)
-                return
-            # Two independent request halves on two streams (graph branches),
-            # meant to overlap one half's HBM-bound cross attention with the
-            # other half's latency-bound Linears.  Every kernel computes a row
-            # the same way whatever rows share its launch (logits bit-identical
-            # either way).
-            h = 2 * (self.R // 2)
-            main = torch.cuda.current_stream(dev)
-            side = self._side_stream()
-            side.wait_stream(main)
-            self._run_fused_layers(x, scale, sstride, cstride, 0, h)
-            with torch.cuda.stream(side):
-                self._run_fused_layers(x, scale, sstride, cstride, h, M)
-            main.wait_stream(side)
-            return
-        for li, L in enumerate(W.dec):
-            cache = self.self_kv[li]
-            qkv = ops.linear(x, L.sa_w, L.sa_b)
-            ops.kv_scatter(qkv[:, d:], cache, req_t, pos_t, row_stride=2 * d, req_stride=sstride)
-            o = torch.empty(M, d, dtype=dt, device=dev)
-            ops.attn_decode(qkv[:, :d], cache, cache.view(-1)[d:], req_t, nks_t, o, H=H, D=D,
-                            row_stride=2 * d, req_stride=sstride, scale=scale)
-            y1 = ops.linear(o, L.sa_ow, L.sa_ob, residual=x)
-            x1, _, _ = eng._ln(y1, L.n1, dt)
-            qc = ops.linear(x1, L.cq_w, L.cq_b)
-            cc = self.cross_kv[li]
-            oc = torch.empty(M, d, dtype=dt, device=dev)
-            ops.attn_decode(qc, cc, cc.view(-1)[H * self.Smax * D:], src_t, nkc_t, oc, H=H, D=D,
-                            row_stride=D, req_stride=cstride, head_stride=self.Smax * D,
-                            scale=scale)
-            y2 = ops.linear(oc, L.ca_ow, L.ca_ob, residual=x1)
-            x2, _, _ = eng._ln(y2, L.n2, dt)
-            h = ops.linear(x2, L.l1_w, L.l1_b, relu=True)
-            y3 = ops.linear(h, L.l2_w, L.l2_b, residual=x2)
-            x, _, _ = eng._ln(y3, L.n3, dt)
-        out, _, _ = eng._ln(x, W.dec_norm, dt)
-        logits = torch.empty(M, eng.V, device=dev) if self.logits_t is None else self.logits_t
-        ops.gemm(out, W.fc_w, M=M, N=eng.V, K=d, out_f32=logits, bias=W.fc_b, dtype=dt)
-        self.logits_t = logits
-
-    def _chains(self):
-        """Request chains per decode step.  SMER_DECODE_CHAINS=2 splits the
-        requests into two halves on two graph branches; measured slower
-        (C2 364 vs 326 us per replay, C5 888 vs 871: tools/decode_chain_probe.py),
-        so one chain is the default."""
-        if self.R < 2:
-            return 1
-        return 2 if os.environ.get("SMER_DECODE_CHAINS", "1") == "2" else 1
-
-    def _side_stream(self):
-        if getattr(self, "_side", None) is None:
+        # Two independent request halves on two streams (graph branches),
+        # meant to overlap one half's HBM-bound cross attention with the
+        # other half's latency-bound Linears.  Every kernel computes a row
+        # the same way whatever rows share its launch (logits bit-identical
+        # either way).
+        h = 2 * (self.R // 2)
+        if self._side is None:
             self._side = torch.cuda.Stream(device=self.dev)
-        return self._side
+        main = torch.cuda.current_stream(self.dev)
+        self._side.wait_stream(main)
+        self._run_layers(plan, x, 0, h)
+        with torch.cuda.stream(self._side):
+            self._run_layers(plan, x, h, M)
+        main.wait_stream(self._side)
 
-    def _run_fused_layers(self, x, scale, sstride, cstride, r0, r1):
-        """bf16 decoder step with every post-norm LayerNorm fused into the
-        prologue of the Linear that consumes it (ops.linear_decode_ln: LN1 ->
-        cross Q, LN2 -> FFN1, LN3 -> next layer's QKV, final norm -> vocab
-        head; the LN output is also stored as the next residual), the cross
-        query projection computed inside the cross-attention blocks, and the
-        new K/V appended by the QKV epilogue: 7 launches per layer (11 in
-        round 1)."""
+    def _run_layers(self, plan, x, r0, r1):
+        """The decoder layers and the vocabulary head on step rows r0..r1 (all
+        of them, or one chain's half) as `plan` says; logits into
+        self.logits_t[r0:r1].  The launches of a configuration, their operands
+        and the order of the allocations are fixed: they make its logits bits
+        and the size of a captured step's private pool."""
         eng, W, dt, dev, d = self.eng, self.W, self.dt, self.dev, self.d
         H, D, M = eng.H, eng.D, r1 - r0
         pos_t, req_t, nks_t, nkc_t = (self.meta_t[0, r0:r1], self.meta_t[1, r0:r1],
                                       self.meta_t[2, r0:r1], self.meta_t[3, r0:r1])
+        src_t = self.src_t[r0:r1]  # cross attention: the row's SOURCE slot
         x = x[r0:r1]
-        # The in-attention query projection re-reads the head's Wq slice per
-        # (row, head) block: 329 vs 342 us per replayed step at R = 32, 484
-        # vs 480 at R = 64 (tools/decode_host_probe.py).  It rounds q in a
-        # different order than the Linear, so the choice must not depend on
-        # the batch (a request's tokens may not depend on its batch-mates):
-        # on whenever the shape allows it.
-        self._qln = D == 64 and d in (512, 768, 1024) and os.environ.get("SMER_DECODE_QLN", "1") == "1"
-        # cross attention reads the row's SOURCE slot: takes that share a
-        # source share one prefill and one memory, and the per-row kernels
-        # read it through the indirection.  SMER_DECODE_SHARED=1 (fewer
-        # sources than requests): the grouped kernels instead, which load
-        # each K / V key step once per chunk of a group's rows and write the
-        # per-row kernels' bits.  Off by default: measured slower (C2 shapes,
-        # 4 sources x 8 takes: 426 vs 289 us per replayed step,
-        # tools/variations_probe.py, DESIGN 5j) -- the repeated reads of the
-        # per-row blocks hit in the caches, and the grouped form leaves 64
-        # walking blocks for 256 CUs.  (Never for a half of the rows, whose
-        # group table would be another one.)
-        src_t = self.src_t[r0:r1]
-        shared = (self.NS < self.R and D in (32, 64) and (r0, r1) == (0, self.M)
-                  and os.environ.get("SMER_DECODE_SHARED", "0") == "1")
-        self._shared = shared
-        ckw = dict(H=H, D=D, row_stride=D, req_stride=cstride, head_stride=self.Smax * D, scale=scale)
-        y_prev = n_prev = None
-        for li, L in enumerate(W.dec):
-            cache = self.self_kv[li]
-            kv = dict(kv=cache, kv_req=req_t, kv_pos=pos_t, kv_row_stride=2 * d,
-                      kv_req_stride=sstride, kv_col0=d)
-            if y_prev is None:  # layer 0: x is the embedding (no norm in front)
-                qkv = ops.linear_decode(x, L.sa_w, L.sa_b, **kv)
-            else:
-                x = torch.empty(M, d, dtype=dt, device=dev)
-                qkv = ops.linear_decode_ln(y_prev, n_prev[0], n_prev[1], L.sa_w, L.sa_b, x_out=x, **kv)
-            o = torch.empty(M, d, dtype=dt, device=dev)
-            ops.attn_decode(qkv[:, :d], cache, cache.view(-1)[d:], req_t, nks_t, o, H=H, D=D,
-                            row_stride=2 * d, req_stride=sstride, scale=scale)
-            y1 = ops.linear(o, L.sa_ow, L.sa_ob, residual=x)
-            x1 = torch.empty(M, d, dtype=dt, device=dev)
-            cc = self.cross_kv[li]
-            oc = torch.empty(M, d, dtype=dt, device=dev)
-            vc = cc.view(-1)[H * self.Smax * D:]
-            if self._qln:  # LN1 + cross Q inside the cross-attention blocks
-                if shared:
-                    ops.attn_decode_shared_qln(y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b, cc, vc, src_t, nkc_t,
-                                               self.grp_t, oc, x_out=x1, **ckw)
-                else:
-                    ops.attn_decode_qln(y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b, cc, vc, src_t, nkc_t, oc,
-                                        x_out=x1, **ckw)
-            else:
-                qc = ops.linear_decode_ln(y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b, x_out=x1)
-                if shared:
-                    ops.attn_decode_shared(qc, cc, vc, src_t, nkc_t, self.grp_t, oc, **ckw)
-                else:
-                    ops.attn_decode(qc, cc, vc, src_t, nkc_t, oc, **ckw)
-            y2 = ops.linear(oc, L.ca_ow, L.ca_ob, residual=x1)
-            x2 = torch.empty(M, d, dtype=dt, device=dev)
-            h = ops.linear_decode_ln(y2, L.n2[0], L.n2[1], L.l1_w, L.l1_b, relu=True, x_out=x2)
-            y_prev = ops.linear(h, L.l2_w, L.l2_b, residual=x2)
-            n_prev = L.n3
-        x, _, _ = eng._ln(y_prev, n_prev, dt)  # last LN3; the final norm feeds the head below
-        ops.linear_decode_ln(x, W.dec_norm[0], W.dec_norm[1], W.fc_w, W.fc_b,
-                             out_f32=self.logits_t[r0:r1])
+        scale = 1.0 / math.sqrt(D)
+        sstride = self.Tmax * 2 * d
+        fused, bf16 = plan.fused, dt == torch.bfloat16
+        skw = dict(H=H, D=D, row_stride=2 * d, req_stride=sstride, scale=scale)
+        ckw = dict(H=H, D=D, row_stride=D, req_stride=2 * H * self.Smax * D, head_stride=self.Smax * D,
+                   scale=scale)
 
-    def _run_fused_layers_f32(self, x, scale, sstride, cstride):
-        """fp32 (parity-mode) decoder step, 8 launches per layer instead of 12:
-        the post-norm LayerNorms run in the prologue of the Linear that
-        consumes them (ops.linear_decode_ln: LN3 -> next QKV, LN1 -> cross Q,
-        LN2 -> FFN1, final norm -> vocab head; the LN output also stored as
-        the next residual, the LayerNorm kernel's bits) and the QKV epilogue
-        appends the new K/V to the cache (no kv_scatter launch).  Every
-        operand fp32; the attention and the plain Linears as in _run."""
-        eng, W, dt, dev, d = self.eng, self.W, self.dt, self.dev, self.d
-        H, D, M = eng.H, eng.D, self.M
-        pos_t, req_t, nks_t, nkc_t = self.meta_t[0], self.meta_t[1], self.meta_t[2], self.meta_t[3]
-        # cross attention as flash-decoding (8 key slices per (row, head),
-        # merged in the out-projection's prologue): the unsplit form runs
-        # 2 * R * H blocks, 16 at batch 1
-        self._split_f32 = D == 64 and d <= 2048 and os.environ.get("SMER_DECODE_SPLIT_F32", "1") == "1"
-        # few rows (batch 1-2): LN1 + the cross-attention query projection
-        # computed inside the split attention blocks (one launch fewer per
-        # layer; each block re-reads its head's 128 KB of Wq from L2, so not
-        # for many rows)
-        qln = self._split_f32 and d == 512 and M <= 4 and os.environ.get("SMER_DECODE_QLN_F32", "1") == "1"
-        # (fp32 has no grouped cross-attention kernel: takes that share a
-        # source run these kernels on the source's slot -- one prefill and one
-        # cache, the loads not shared)
-        src_t = self.src_t
-        y_prev = n_prev = None
+        def new():
+            return torch.empty(M, d, dtype=dt, device=dev)
+        y = n = None  # the layer below's FFN output and its LN3, which the next Linear in line applies
         for li, L in enumerate(W.dec):
-            cache = self.self_kv[li]
-            kv = dict(kv=cache, kv_req=req_t, kv_pos=pos_t, kv_row_stride=2 * d,
-                      kv_req_stride=sstride, kv_col0=d)
-            if y_prev is None:  # layer 0: x is the embedding (no norm in front)
-                qkv = ops.linear_decode(x, L.sa_w, L.sa_b, **kv)
+            cache, cc = self.self_kv[li], self.cross_kv[li]
+            # QKV projection (of LN3 of the layer below), the new K/V appended
+            if not fused:
+                if y is not None:
+                    x, _, _ = eng._ln(y, n, dt)
+                qkv = ops.linear(x, L.sa_w, L.sa_b)
+                ops.kv_scatter(qkv[:, d:], cache, req_t, pos_t, row_stride=2 * d, req_stride=sstride)
             else:
-                x = torch.empty(M, d, dtype=dt, device=dev)
-                qkv = ops.linear_decode_ln(y_prev, n_prev[0], n_prev[1], L.sa_w, L.sa_b, x_out=x, **kv)
-            # (the self attention stays unsplit: its <= ~400-key caches
-            # measured 0.306 vs 0.296 ms per step split)
-            o = torch.empty(M, d, dtype=dt, device=dev)
-            ops.attn_decode(qkv[:, :d], cache, cache.view(-1)[d:], req_t, nks_t, o, H=H, D=D,
-                            row_stride=2 * d, req_stride=sstride, scale=scale)
+                kv = dict(kv=cache, kv_req=req_t, kv_pos=pos_t, kv_row_stride=2 * d,
+                          kv_req_stride=sstride, kv_col0=d)
+                if y is None:  # layer 0: x is the embedding (no norm in front)
+                    qkv = ops.linear_decode(x, L.sa_w, L.sa_b, **kv)
+                else:
+                    x = new()
+                    qkv = ops.linear_decode_ln(y, n[0], n[1], L.sa_w, L.sa_b, x_out=x, **kv)
+            o = new()
+            ops.attn_decode(qkv[:, :d], cache, cache.view(-1)[d:], req_t, nks_t, o, **skw)
             y1 = ops.linear(o, L.sa_ow, L.sa_ob, residual=x)
-            x1 = torch.empty(M, d, dtype=dt, device=dev)
-            cc = self.cross_kv[li]
-            if qln:
+            # x1 = LN1(y1); cross attention of x1 . Wq over the source's memory; out-projection + x1
+            lnq = (y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b)
+            mem = (cc, cc.view(-1)[H * self.Smax * D:], src_t, nkc_t)  # K half, V half, row -> slot, keys
+            if fused:
+                x1 = new()
+            else:
+                x1, _, _ = eng._ln(y1, L.n1, dt)
+            if plan.split_f32:  # 8 key slices per (row, head), merged by the out-projection
+                if not plan.qln:
+                    qc = ops.linear_decode_ln(*lnq, x_out=x1)
                 part = torch.empty(M, H, ops.DEC_SPLITS, 68, device=dev)
-                ops.attn_decode_split_qln_f32(y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b, cc,
-                                              cc.view(-1)[H * self.Smax * D:], src_t, nkc_t, part, H=H, D=D,
-                                              row_stride=D, req_stride=cstride, head_stride=self.Smax * D,
-                                              scale=scale, x_out=x1)
-                y2 = ops.linear_decode_merge_f32(part, L.ca_ow, L.ca_ob, M=M, residual=x1)
-            elif self._split_f32:  # 8 key slices per (row, head), merged by the out-projection
-                qc = ops.linear_decode_ln(y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b, x_out=x1)
-                part = torch.empty(M, H, ops.DEC_SPLITS, 68, device=dev)
-                ops.attn_decode_split_f32(qc, cc, cc.view(-1)[H * self.Smax * D:], src_t, nkc_t, part, H=H,
-                                          D=D, row_stride=D, req_stride=cstride, head_stride=self.Smax * D,
-                                          scale=scale)
+                if plan.qln:
+                    ops.attn_decode_split_qln_f32(*lnq, *mem, part, x_out=x1, **ckw)
+                else:
+                    ops.attn_decode_split_f32(qc, *mem, part, **ckw)
                 y2 = ops.linear_decode_merge_f32(part, L.ca_ow, L.ca_ob, M=M, residual=x1)
             else:
-                qc = ops.linear_decode_ln(y1, L.n1[0], L.n1[1], L.cq_w, L.cq_b, x_out=x1)
-                oc = torch.empty(M, d, dtype=dt, device=dev)
-                ops.attn_decode(qc, cc, cc.view(-1)[H * self.Smax * D:], src_t, nkc_t, oc, H=H, D=D,
-                                row_stride=D, req_stride=cstride, head_stride=self.Smax * D, scale=scale)
+                if bf16:  # (the bf16 step takes oc ahead of the projection, the fp32 ones after it)
+                    oc = new()
+                if not plan.qln:
+                    qc = ops.linear_decode_ln(*lnq, x_out=x1) if fused else ops.linear(x1, L.cq_w, L.cq_b)
+                if not bf16:
+                    oc = new()
+                if plan.qln and plan.shared:
+                    ops.attn_decode_shared_qln(*lnq, *mem, self.grp_t, oc, x_out=x1, **ckw)
+                elif plan.qln:
+                    ops.attn_decode_qln(*lnq, *mem, oc, x_out=x1, **ckw)
+                elif plan.shared:
+                    ops.attn_decode_shared(qc, *mem, self.grp_t, oc, **ckw)
+                else:
+                    ops.attn_decode(qc, *mem, oc, **ckw)
                 y2 = ops.linear(oc, L.ca_ow, L.ca_ob, residual=x1)
-            x2 = torch.empty(M, d, dtype=dt, device=dev)
-            h = ops.linear_decode_ln(y2, L.n2[0], L.n2[1], L.l1_w, L.l1_b, relu=True, x_out=x2)
-            y_prev = ops.linear(h, L.l2_w, L.l2_b, residual=x2)
-            n_prev = L.n3
-        x, _, _ = eng._ln(y_prev, n_prev, dt)  # last LN3; the final norm feeds the head below
-        ops.linear_decode_ln(x, W.dec_norm[0], W.dec_norm[1], W.fc_w, W.fc_b, out_f32=self.logits_t)
+            # x2 = LN2(y2); FFN + x2
+            if fused:
+                x2 = new()
+                h = ops.linear_decode_ln(y2, L.n2[0], L.n2[1], L.l1_w, L.l1_b, relu=True, x_out=x2)
+            else:
+                x2, _, _ = eng._ln(y2, L.n2, dt)
+                h = ops.linear(x2, L.l1_w, L.l1_b, relu=True)
+            y, n = ops.linear(h, L.l2_w, L.l2_b, residual=x2), L.n3
+        x, _, _ = eng._ln(y, n, dt)  # the last LN3, then the final norm into the vocabulary head
+        if fused:
+            ops.linear_decode_ln(x, W.dec_norm[0], W.dec_norm[1], W.fc_w, W.fc_b,
+                                 out_f32=self.logits_t[r0:r1])
+        else:
+            out, _, _ = eng._ln(x, W.dec_norm, dt)
+            ops.gemm(out, W.fc_w, M=M, N=eng.V, K=d, out_f32=self.logits_t[r0:r1], bias=W.fc_b, dtype=dt)
 
     def _ensure_graph(self):
         if self.graph is not None or not self.use_graph:
@@ -464,10 +537,7 @@ class DecodeSession:
         torch.cuda.synchronize()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        if self._graph_copies:
-            self.graph = _capture(s, self._run_with_copies)
-        else:
-            self.graph = _capture(s, self._run)
+        self.graph = _capture(s, self._run_with_copies if self._graph_copies else self._run)
         torch.cuda.current_stream().wait_stream(s)
 
     def _run_with_copies(self):
@@ -534,92 +604,16 @@ class DecodeSession:
     # greedy decode with the grammar on device (csrc/decode_ops.hip)
     # ------------------------------------------------------------------
     N_STATE = 12
-    LDMT = 640  # words per request of g_mt_rows (625 used: rows start 256-byte aligned)
+    LDMT = 640  # words per request of a rows graph's g_mt_rows (625 used: rows start 256-byte aligned)
     # ban rows per request of the '+ban' graphs (pitch constraints): one per
     # constrained track, and a request masks at most the vocabulary's three
     # tracks (track_0 .. track_2) -- rounded up to a power of two
     BAN_K = 4
 
-    def _bind_grammar(self, bufs):
-        """Make one captured graph's buffers the session's g_* attributes."""
-        for k, v in bufs.items():
-            setattr(self, k, v)
-
-    def _capture_greedy(self, st, tg, keep, cls, cap, nm, eos, m0, lookahead, max_span, use_ring,
-                        mode="greedy", ban=None, score=False):
-        """Persistent grammar buffers + the captured (decoder step + grammar)
-        graph, reused by later calls of the same mode and shapes.  mode:
-        "greedy", "stream" (the sampler on the one shared MT19937 stream) or
-        "rows" (the sampler on one stream per request).  The buffers a graph
-        addresses belong to it (returned, and kept with it in self._graphs):
-        the graphs of the other modes keep theirs.  ban ((ban_of_mask int8 [R,
-        nm], ban_bits uint32 [R, BAN_K, 16]) on the host): the graph runs
-        smer_logits_ban between the decoder step and the grammar kernel.
-        score: the graph also takes the log-probability of every drawn token
-        (smer_logprob_stage before the grammar kernel, smer_logprob_commit
-        after it) into g_logp float64 [R, cap], entry for entry with g_out."""
-        dev = self.dev
-        bufs = dict(
-            g_state=torch.from_numpy(st).to(dev),
-            g_targets=torch.from_numpy(tg).to(dev),
-            g_keep=torch.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8)).to(dev),
-            g_cls=torch.from_numpy(np.ascontiguousarray(cls, dtype=np.uint8)).to(dev),
-            g_srclen=torch.from_numpy(self.src_len.astype(np.int32)).to(dev),
-            g_out=torch.zeros(self.R, cap, dtype=torch.int32, device=dev))
-        if mode != "greedy":
-            bufs["g_reject"] = torch.zeros(keep.shape, dtype=torch.uint8, device=dev)
-            bufs["g_tp"] = torch.zeros(self.R, 2, dtype=torch.float64, device=dev)
-            if mode == "rows":
-                bufs["g_mt_rows"] = torch.zeros(self.R, self.LDMT, dtype=torch.int32, device=dev)
-            else:
-                bufs["g_mt"] = torch.zeros(625, dtype=torch.int32, device=dev)
-        if ban is not None:
-            bufs["g_banmask"] = torch.from_numpy(ban[0]).to(dev)
-            bufs["g_banbits"] = torch.from_numpy(ban[1].view(np.int32)).to(dev)
-        if score:
-            bufs["g_lp_row"] = torch.zeros(self.R, 512, dtype=torch.float64, device=dev)
-            bufs["g_lp_stage"] = torch.full((self.R,), -1, dtype=torch.int32, device=dev)
-            bufs["g_logp"] = torch.zeros(self.R, cap, dtype=torch.float64, device=dev)
-        # live counts: the step's grammar kernel publishes its count into a
-        # pinned host ring itself (no per-step memset / D2H copy between the
-        # replays); SMER_GRAMMAR_RING=0: memset + copy per step (A/B)
-        ring = torch.zeros(2 * lookahead + 2, dtype=torch.int32).pin_memory()
-        rv = ring.numpy()
-        bufs["g_alive"] = torch.zeros(3 if use_ring else 1, dtype=torch.int32, device=dev)
-        self._bind_grammar(bufs)
-        gargs = dict(eos=eos, m0=m0, trash_pos=self.Tmax - 1, max_span=max_span,
-                     ring=ring if use_ring else None)
-
-        def grammar():
-            if ban is not None:  # banned logits -> -100 ahead of the grammar kernel
-                ops.logits_ban(self.logits_t, self.g_state, self.g_banmask, self.g_banbits)
-            if score:  # the row's log-softmax while the row exists, the drawn token's entry after
-                ops.logprob_stage(self.logits_t, self.g_state, self.g_targets, self.g_keep,
-                                  self.g_lp_row, self.g_lp_stage)
-            entry()
-            if score:
-                ops.logprob_commit(self.g_state, self.g_lp_stage, self.g_out, self.g_lp_row, self.g_logp,
-                                   V=self.g_keep.shape[1])
-
-        def entry():
-            if mode == "rows":
-                ops.grammar_sample_step_rows(self.logits_t, self.g_state, self.g_targets, self.g_keep,
-                                             self.g_reject, self.g_cls, self.g_srclen, self.ids_t,
-                                             self.meta_t, self.g_out, self.g_mt_rows, self.g_alive,
-                                             tp=self.g_tp, **gargs)
-                return
-            if mode == "stream":
-                ops.grammar_sample_step(self.logits_t, self.g_state, self.g_targets, self.g_keep,
-                                        self.g_reject, self.g_cls, self.g_srclen, self.ids_t,
-                                        self.meta_t, self.g_out, self.g_mt, self.g_alive, tp=self.g_tp,
-                                        **gargs)
-                return
-            ops.grammar_greedy_step(self.logits_t, self.g_state, self.g_targets, self.g_keep,
-                                    self.g_cls, self.g_srclen, self.ids_t, self.meta_t, self.g_out,
-                                    self.g_alive, **gargs)
-
-        # warm the decoder step eagerly (dummy rows only), then capture
-        # step + grammar; the grammar kernel never runs outside the graph
+    def _capture_grammar(self, gg):
+        """Capture (decoder step + gg.step) into gg.graph.  The decoder step
+        is warmed eagerly first (dummy rows only); the grammar kernel never
+        runs outside the graph.  Returns the host seconds of the two phases."""
         t_a = time.perf_counter()
         self._load_feeds([])
         self._run()
@@ -627,11 +621,10 @@ class DecodeSession:
         t_b = time.perf_counter()
         gs = torch.cuda.Stream()
         gs.wait_stream(torch.cuda.current_stream())
-        g = _capture(gs, lambda: (self._run(), grammar()))
+        gg.graph = _capture(gs, lambda: (self._run(), gg.step(self.logits_t, self.ids_t, self.meta_t)))
         torch.cuda.current_stream().wait_stream(gs)
         torch.cuda.synchronize()
-        t_c = time.perf_counter()
-        return g, ring, rv, t_a, t_b, t_c, bufs
+        return t_b - t_a, time.perf_counter() - t_b
 
     def sampled_decode(self, spans, keep, reject, cls, *, eos, m0, lookahead=3, max_span=100,
                        t=1.0, p=None, seeds=None, bans=None, score=False):
@@ -648,26 +641,15 @@ class DecodeSession:
         seeds (one int in [0, 2**32) per span): span r draws from its own
         stream np.random.RandomState(seeds[r]) instead, built here on the host
         and copied to the device; the step then ends in the one-block-per-
-        request form of the kernel (smer_grammar_sample_step_rows), a second
-        captured graph kept beside the unseeded one, and np.random is neither
+        request form of the kernel (smer_grammar_sample_step_rows), the "rows"
+        graph kept beside the unseeded "stream" one, and np.random is neither
         read nor written.  Other seeds replay that graph.
-        bans (pitch constraints): per span None or (ban_of_mask row: the ban
-        row of each mask, -1 for none; bit rows uint32 [k <= BAN_K, 16]: bit v
-        of row j set = token v banned).  With any span constrained the call
-        replays the '+ban' graph of its mode, in which smer_logits_ban
-        rewrites the banned logits to -100 between the vocabulary projection
-        and the sampler; both tables are device data refreshed per call, so
-        other constraints replay that graph.  None (or all None): the graphs
-        without that node, as ever.
-        score: replay the '+score' graph of the mode instead (_grammar_decode),
-        which also takes every drawn token's log-probability at t = 1 over the
-        whole masked distribution, whatever t and p are.  Returns
-        (per-request emitted ids, steps, error flags, per-request redraw
-        failure flags), and with score a fifth value: per request the float64
-        log-probabilities of its ids."""
+        bans, score: as greedy_decode's; the scores are taken at t = 1 over
+        the whole masked distribution, whatever t and p are.
+        Returns a DecodeResult whose `fails` flag the ids whose redraws ran
+        out."""
         if all(sp.done for sp in spans):  # nothing to draw: np.random stays untouched
-            res = [[] for _ in spans], 0, np.zeros(len(spans), dtype=np.int32), [[] for _ in spans]
-            return res + ([np.zeros(0) for _ in spans],) if score else res
+            return DecodeResult.empty(len(spans), True, score)
         n = len(spans)
         ts = list(t) if isinstance(t, (list, tuple, np.ndarray)) else [t] * n
         ps = list(p) if isinstance(p, (list, tuple, np.ndarray)) else [p] * n
@@ -692,9 +674,6 @@ class DecodeSession:
                 s0 = np.random.RandomState(int(seeds[r]) if r < n else 0).get_state()
                 mt_h[r, :624] = s0[1]
                 mt_h[r, 624] = int(s0[2])
-            res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
-                                       max_span=max_span, sample=(reject, mt_h, tp_h, True), bans=bans,
-                                       score=score)
         else:
             st0 = np.random.get_state()
             if st0[0] != "MT19937":
@@ -702,41 +681,44 @@ class DecodeSession:
             mt_h = np.empty(625, dtype=np.uint32)
             mt_h[:624] = st0[1]
             mt_h[624] = int(st0[2])
-            res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
-                                       max_span=max_span, sample=(reject, mt_h, tp_h, False), bans=bans,
-                                       score=score)
-            m = self.g_mt.cpu().numpy().view(np.uint32)
+        res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead, max_span=max_span,
+                                   sampler=_Sampler(reject, mt_h, tp_h, seeds is not None), bans=bans,
+                                   score=score)
+        if seeds is None:  # the stream goes on where the device left it
+            m = self._greedy.bufs["g_mt"].cpu().numpy().view(np.uint32)
             np.random.set_state(("MT19937", m[:624].copy(), int(m[624]), st0[3], st0[4]))
-        ids, steps, err = res[:3]
-        fails = [[(x >> 16) & 1 for x in q] for q in ids]
-        return ([[x & 0xFFFF for x in q] for q in ids], steps, err, fails) + tuple(res[4:])
+        return res._replace(ids=[[x & 0xFFFF for x in q] for q in res.ids],
+                            fails=[[(x >> 16) & 1 for x in q] for q in res.ids])
 
     def greedy_decode(self, spans, keep, cls, *, eos, m0, lookahead=3, max_span=100, bans=None,
                       score=False):
-        """bans: pitch constraints, as sampled_decode's.  score: the '+score'
-        graph and a fifth return value, as _grammar_decode's."""
-        return self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
-                                    max_span=max_span, bans=bans, score=score)
-
-    def _grammar_decode(self, spans, keep, cls, *, eos, m0, lookahead=3, max_span=100, sample=None,
-                        bans=None, score=False):
         """Run the greedy infill loop of `spans` (generation._Span, one per
         request slot 0..len-1, freshly started, sources prefilled) entirely
         on device: each step is one replay of the captured decoder step +
         grammar kernel; the host only polls the live count, `lookahead`
-        steps behind.  Returns (per-request emitted ids, steps, error flags,
-        step times); the caller replays the ids through its host spans.
+        steps behind.  Returns a DecodeResult; the caller replays the ids
+        through its host spans.
+        bans (pitch constraints): per span None or (ban_of_mask row: the ban
+        row of each mask, -1 for none; bit rows uint32 [k <= BAN_K, 16]: bit v
+        of row j set = token v banned).  With any span constrained the call
+        replays the '+ban' graph of its mode (_GrammarGraph); both tables are
+        device data refreshed per call, so other constraints replay that
+        graph.  None (or all None): the graphs without that node, as ever.
         score: the call replays the '+score' graph of its mode (after '+ban',
-        if constrained), in which smer_logprob_stage / smer_logprob_commit
-        bracket the grammar kernel, and returns a fifth value: per request the
-        float64 log-probabilities of its emitted ids (generation.
-        token_logprobs at each id, t = 1, the whole masked distribution).
-        Without it: the graphs without those nodes, as ever."""
+        if constrained) and the result's `logp` holds, per request, the float64
+        log-probabilities of its emitted ids (generation.token_logprobs at each
+        id, t = 1, the whole masked distribution).  Without it: the graphs
+        without those nodes, as ever."""
+        return self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
+                                    max_span=max_span, bans=bans, score=score)
+
+    def _grammar_decode(self, spans, keep, cls, *, eos, m0, lookahead, max_span, sampler=None, bans=None,
+                        score=False):
+        """greedy_decode, or with `sampler` (a _Sampler) sampled_decode."""
         R = len(spans)
         if R > self.R:
             raise ValueError("more spans than session slots")
         self._pe_guard()
-        dev = self.dev
         # mask-target table capacity: a power of two >= 16, so calls whose
         # requests have different mask counts replay the same captured graph
         # (a capture costs ~10 ms; the kernels read the table by its row
@@ -762,12 +744,11 @@ class DecodeSession:
                 feeds.append((r, [m0], 0))
         st[R:, 5] = 1
         if not feeds:
-            res = [[] for _ in range(R)], 0, np.zeros(R, dtype=np.int32), []
-            return res + ([np.zeros(0) for _ in range(R)],) if score else res
-        use_ring = os.environ.get("SMER_GRAMMAR_RING", "1") != "0" or sample is not None
+            return DecodeResult.empty(R, sampler is not None, score)
+        use_ring = os.environ.get("SMER_GRAMMAR_RING", "1") != "0" or sampler is not None
         # one captured graph per mode, side by side: a process that alternates
         # between greedy, unseeded and seeded calls replays, never recaptures
-        mode = "greedy" if sample is None else "rows" if sample[3] else "stream"
+        mode = "greedy" if sampler is None else "rows" if sampler.per_request else "stream"
         gkey = (nm, int(max_span), int(eos), int(m0), int(lookahead), use_ring, keep.shape, cls.shape,
                 mode)
         # pitch constraints: a graph of its own per mode (mode + "+ban", the
@@ -797,45 +778,30 @@ class DecodeSession:
                 raise ValueError("score: the device path scores vocabularies up to 512 tokens")
             gname += "+score"
             gkey += ("score",)
-        graphs = self.__dict__.setdefault("_graphs", {})
-        gc = graphs.get(gname)
-        if gc is not None and gc["key"] == gkey:
+        inputs = (st, tg, keep, cls, self.src_len, ban, sampler)
+        gg = self._graphs.get(gname)
+        if gg is not None and gg.key == gkey:
             # the captured step + grammar graph of an earlier call with the
-            # same shapes: refresh its persistent inputs in place and replay
-            t_a = t_b = time.perf_counter()
-            self._bind_grammar(gc["bufs"])
+            # same shapes: refresh its inputs in place and replay
+            t_b = time.perf_counter()
             self.eng.weights(self.dt)  # re-casts the bf16 weights in place if they moved
-            self.g_state.copy_(torch.from_numpy(st))
-            self.g_targets.copy_(torch.from_numpy(tg))
-            self.g_keep.copy_(torch.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8)))
-            self.g_cls.copy_(torch.from_numpy(np.ascontiguousarray(cls, dtype=np.uint8)))
-            self.g_srclen.copy_(torch.from_numpy(self.src_len.astype(np.int32)))
-            if ban is not None:
-                self.g_banmask.copy_(torch.from_numpy(ban[0]))
-                self.g_banbits.copy_(torch.from_numpy(ban[1].view(np.int32)))
-            self.g_out.zero_()
-            if score:
-                self.g_logp.zero_()
-            self.g_alive.zero_()
-            g, ring = gc["graph"], gc["ring"]
-            ring.zero_()
-            rv = ring.numpy()
+            gg.load(*inputs)
             torch.cuda.synchronize()
-            t_c = time.perf_counter()
+            warm_s, capture_s = 0.0, time.perf_counter() - t_b
         else:
-            graphs.pop(gname, None)  # frees its buffers before the new ones are made
-            g, ring, rv, t_a, t_b, t_c, bufs = self._capture_greedy(st, tg, keep, cls, cap, nm, eos, m0,
-                                                                   lookahead, max_span, use_ring, mode, ban,
-                                                                   score)
-            gc = graphs[gname] = {"key": gkey, "graph": g, "ring": ring, "bufs": bufs}
-        self._greedy = gc  # the graph of this call
-        if sample is not None:
-            self.g_reject.copy_(torch.from_numpy(np.ascontiguousarray(sample[0], dtype=np.uint8)))
-            mt_dst = self.g_mt_rows if mode == "rows" else self.g_mt
-            mt_dst.copy_(torch.from_numpy(sample[1].view(np.int32)))
-            self.g_tp.copy_(torch.from_numpy(sample[2]))
+            gg = self._greedy = None
+            self._graphs.pop(gname, None)  # a stale graph's buffers go before the new ones are made
+            gg = _GrammarGraph(self, gkey, mode, nm, keep.shape, cls.shape, eos=eos, m0=m0,
+                               lookahead=lookahead, max_span=max_span, use_ring=use_ring,
+                               ban=ban is not None, score=score)
+            gg.load(*inputs)
+            warm_s, capture_s = self._capture_grammar(gg)
+            self._graphs[gname] = gg
+        self._greedy = gg  # the graph of this call
+        t_c = time.perf_counter()
         self._load_feeds(feeds)
         max_steps = max([s.n_masks for s in spans] + [0]) * (max_span + 1) + 2
+        graph, rv = gg.graph, gg.rv
         inflight = []
         events = []
         steps = None
@@ -852,24 +818,23 @@ class DecodeSession:
                 continue
             if issued >= max_steps:
                 raise RuntimeError("greedy_decode: no convergence within %d steps" % max_steps)
-            g.replay()
+            graph.replay()
             slot = issued % len(rv)
             if not use_ring:
-                ring[slot:slot + 1].copy_(self.g_alive, non_blocking=True)
+                gg.ring[slot:slot + 1].copy_(gg.bufs["g_alive"], non_blocking=True)
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
             events.append(ev)
             inflight.append((issued, ev, slot))
             issued += 1
         torch.cuda.synchronize()
-        t_d = time.perf_counter()
-        # host seconds of this call's phases (bench / probes)
-        self.phase_s = {"warm_s": t_b - t_a, "capture_s": t_c - t_b, "loop_s": t_d - t_c}
-        st = self.g_state.cpu().numpy()
-        out = self.g_out.cpu().numpy()
+        self.phase_s = {"warm_s": warm_s, "capture_s": capture_s, "loop_s": time.perf_counter() - t_c}
+        st = gg.bufs["g_state"].cpu().numpy()
+        out = gg.bufs["g_out"].cpu().numpy()
         ids = [out[r, :min(int(st[r, 7]), cap)].tolist() for r in range(R)]
-        step_ms = [ev_start.elapsed_time(e) for e in events[:steps]]
+        logp = None
         if score:
-            lp = self.g_logp.cpu().numpy()
-            return ids, steps, st[:R, 8].copy(), step_ms, [lp[r, :len(ids[r])].copy() for r in range(R)]
-        return ids, steps, st[:R, 8].copy(), step_ms
+            lp = gg.bufs["g_logp"].cpu().numpy()
+            logp = [lp[r, :len(ids[r])].copy() for r in range(R)]
+        return DecodeResult(ids, steps, st[:R, 8].copy(), [ev_start.elapsed_time(e) for e in events[:steps]],
+                            None, logp)

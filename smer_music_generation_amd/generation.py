@@ -875,6 +875,37 @@ def _device_bans(spans):
     return bans if any(b is not None for b in bans) else None
 
 
+def _replay(spans, res, logger, sampled=True):
+    """Replay the ids a device loop emitted (a DecodeResult) through the host
+    spans, which rebuild exactly the reference's event lists.  sampled: step
+    by step, the requests in order -- the host loop's order, so the
+    redraw-failure lines come out in its order too.  Greedy: commit_all
+    without a logger (no redraw report to log), commit_greedy with one.
+    With score the spans take the device's own log-probabilities, entry for
+    entry with the ids.  Returns the number of tokens."""
+    if sampled:
+        for k in range(max([len(q) for q in res.ids] + [0])):
+            for sp, seq, fl in zip(spans, res.ids, res.fails):
+                if k < len(seq):
+                    if fl[k] and logger is not None:
+                        logger.info(sp.spec()[2])
+                    sp.commit(seq[k])
+    else:
+        for sp, seq in zip(spans, res.ids):
+            if logger is None:
+                sp.commit_all(seq)
+            else:
+                for idx in seq:
+                    _, chk, msg = sp.spec()
+                    sp.commit_greedy(idx, chk, msg)
+    if not all(sp.done for sp in spans):
+        raise RuntimeError("device grammar and host replay disagree")
+    if res.logp is not None:
+        for sp, lp in zip(spans, res.logp):
+            sp.logp = list(lp)
+    return sum(len(seq) for seq in res.ids)
+
+
 def _sampled_on_device(sess, st, vocab, all_controls, logger, seed=None):
     """One request's sampled span loop on device (DecodeSession.
     sampled_decode), then the emitted ids replayed through the host span
@@ -885,26 +916,17 @@ def _sampled_on_device(sess, st, vocab, all_controls, logger, seed=None):
     RandomState(seed))."""
     keep, cls = grammar_tables(vocab, all_controls)
     rng0 = np.random.get_state() if seed is None else None
-    seqs, steps, err, fails, *lps = sess.sampled_decode([st], keep, reject_table(vocab), cls,
-                                                        eos=vocab.eos_index, m0=vocab.char2index('m_0'),
-                                                        t=st.t, p=st.p,
-                                                        seeds=None if seed is None else [seed],
-                                                        bans=_device_bans([st]), score=st.score)
-    if err[0] & 2:
+    res = sess.sampled_decode([st], keep, reject_table(vocab), cls, eos=vocab.eos_index,
+                              m0=vocab.char2index('m_0'), t=st.t, p=st.p,
+                              seeds=None if seed is None else [seed], bans=_device_bans([st]),
+                              score=st.score)
+    if res.err[0] & 2:
         if seed is None:
             np.random.set_state(rng0)
         return None
-    if err[0] & 1:
+    if res.err[0] & 1:
         raise ValueError("decoder prefix exceeds session max_tgt %d" % (sess.Tmax - 1))
-    for idx, fail in zip(seqs[0], fails[0]):
-        if fail and logger is not None:
-            logger.info(st.spec()[2])
-        st.commit(idx)
-    if not st.done:
-        raise RuntimeError("device grammar and host replay disagree")
-    if st.score:  # the device's own numbers, entry for entry with the ids
-        st.logp = list(lps[0][0])
-    return len(seqs[0])
+    return _replay([st], res, logger)
 
 
 def _generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
@@ -1155,14 +1177,14 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
             keep, cls = grammar_tables(vocab, all_controls)
             m0 = vocab.char2index('m_0')
             ts = time.perf_counter()
-            seqs, steps, err, step_ms, *lps = sess.greedy_decode(spans, keep, cls, eos=vocab.eos_index,
-                                                                 m0=m0, bans=_device_bans(spans),
-                                                                 score=score)
+            res = sess.greedy_decode(spans, keep, cls, eos=vocab.eos_index, m0=m0,
+                                     bans=_device_bans(spans), score=score)
             t_dev = time.perf_counter() - ts
+            seqs, steps = res.ids, res.steps
             # completion time of each request from the call's start: host
             # preparation + prefill, then the GPU end time of its last step
-            latency = [(ts - t0) + (step_ms[len(q) - 1] / 1000.0 if q else 0.0) for q in seqs]
-            if np.any(err):
+            latency = [(ts - t0) + (res.step_ms[len(q) - 1] / 1000.0 if q else 0.0) for q in seqs]
+            if np.any(res.err):
                 raise ValueError("decoder prefix exceeds session max_tgt %d" % (sess.Tmax - 1))
             # key rows the decode steps attended to (SURVEY §8d infill bytes):
             # request r's i-th step reads its S_r memory rows and i+1 prefix rows
@@ -1173,29 +1195,17 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
             for src, n in zip(srcs, takes or [1] * R):
                 kv_reads += max(len(q) for q in seqs[k0:k0 + n]) * len(src)
                 k0 += n
-            for sp, seq in zip(spans, seqs):
-                if logger is None:  # no redraw report to log: commit only
-                    sp.commit_all(seq)
-                else:
-                    for idx in seq:
-                        _, chk, msg = sp.spec()
-                        sp.commit_greedy(idx, chk, msg)
-                if not sp.done:
-                    raise RuntimeError("device grammar and host replay disagree")
-                tokens += len(seq)
-            if score:
-                for sp, lp in zip(spans, lps[0]):
-                    sp.logp = list(lp)
+            tokens += _replay(spans, res, logger, sampled=False)
         elif device_grammar and vocab.vocab_size <= 512:
             keep, cls = grammar_tables(vocab, all_controls)
             rng0 = np.random.get_state() if seeds is None else None
             ts = time.perf_counter()
-            seqs, dsteps, err, fails, *lps = sess.sampled_decode(
+            res = sess.sampled_decode(
                 spans, keep, reject_table(vocab), cls, eos=vocab.eos_index,
                 m0=vocab.char2index('m_0'), t=[a for a, _ in tps], p=[b for _, b in tps],
                 seeds=seeds, bans=_device_bans(spans), score=score)
             t_dev = time.perf_counter() - ts
-            if np.any(err & 2):
+            if np.any(res.err & 2):
                 # some row's probabilities missed 1 by more than 1e-9
                 # (np.random.choice territory): same RNG start, fresh spans,
                 # and the whole batch goes through the host loop below
@@ -1206,24 +1216,10 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                 prefill()
                 t_dev = 0.0
             else:
-                if np.any(err & 1):
+                if np.any(res.err & 1):
                     raise ValueError("decoder prefix exceeds session max_tgt %d" % (sess.Tmax - 1))
-                steps = dsteps
-                # replay in the host loop's order (step by step, requests in
-                # order): the redraw-failure lines come out in its order too
-                for k in range(max([len(q) for q in seqs] + [0])):
-                    for sp, seq, fl in zip(spans, seqs, fails):
-                        if k < len(seq):
-                            if fl[k] and logger is not None:
-                                logger.info(sp.spec()[2])
-                            sp.commit(seq[k])
-                for sp, seq in zip(spans, seqs):
-                    if not sp.done:
-                        raise RuntimeError("device grammar and host replay disagree")
-                    tokens += len(seq)
-                if score:
-                    for sp, lp in zip(spans, lps[0]):
-                        sp.logp = list(lp)
+                steps = res.steps
+                tokens += _replay(spans, res, logger)
         while True:
             live = [i for i in range(R) if not spans[i].done]
             if not live:
@@ -1283,5 +1279,5 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                      "request_latency_s": latency, "kv_row_reads": kv_reads,
                      "generated": [list(st.total) for st in spans],
                      "seeds": seeds, "pitches": allowed, "sources": len(srcs), "prefill_rows": int(sess.prefill_rows),
-                     "decode_phases_s": dict(getattr(sess, "phase_s", {}))}
+                     "decode_phases_s": dict(sess.phase_s)}
     return out

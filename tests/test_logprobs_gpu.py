@@ -449,19 +449,19 @@ def test_unscored_calls_keep_their_graph_and_their_tokens(micro, spans):  # noqa
     before = _plugin(G, m, v, reqs, ctl, spans, seed=11)
     sess = _sessions(G, m, 1)[0]
     plain = sess._graphs["rows"]
-    graph, bufs = plain["graph"], dict(plain["bufs"])
+    graph, bufs = plain.graph, dict(plain.bufs)
     assert set(sess._graphs) == {"rows"}
     assert not any(k in bufs for k in ("g_lp_row", "g_lp_stage", "g_logp"))
     a = _plugin(G, m, v, reqs, ctl, spans, seed=11, logprobs=True)
     entry = sess._graphs["rows+score"]
-    assert sess._greedy is entry and {"g_lp_row", "g_lp_stage", "g_logp"} <= set(entry["bufs"])
+    assert sess._greedy is entry and {"g_lp_row", "g_lp_stage", "g_logp"} <= set(entry.bufs)
     b = _plugin(G, m, v, reqs, ctl, spans, seed=12, logprobs=True)
     assert sess._graphs["rows+score"] is entry  # another seed replays it
     assert a[0] == before[0] and b[0] != a[0]
     after = _plugin(G, m, v, reqs, ctl, spans, seed=11)
     assert _sessions(G, m, 1)[0] is sess and sess._graphs["rows"] is plain and sess._greedy is plain
-    assert plain["graph"] is graph and set(plain["bufs"]) == set(bufs)
-    assert all(plain["bufs"][k] is bufs[k] for k in bufs)
+    assert plain.graph is graph and set(plain.bufs) == set(bufs)
+    assert all(plain.bufs[k] is bufs[k] for k in bufs)
     assert after[0] == before[0] and after[1] == before[1] and _str(after[3]) == _str(before[3])
 
 

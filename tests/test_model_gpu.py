@@ -332,9 +332,9 @@ def test_warm_session_graph_reuse_and_ring_match_fresh(golden_dir, precision, mo
     G._BATCH_SESSIONS.clear()
     G.generation_batch(m, big, v, ctl, greedy=True)
     sess = next(iter(G._BATCH_SESSIONS.values()))
-    graph = sess._greedy["graph"]
+    graph = sess._greedy.graph
     warm = run()
-    assert next(iter(G._BATCH_SESSIONS.values())) is sess and sess._greedy["graph"] is graph
+    assert next(iter(G._BATCH_SESSIONS.values())) is sess and sess._greedy.graph is graph
     monkeypatch.setenv("SMER_GRAMMAR_RING", "0")
     noring = run()
     for x, y, w in zip(fresh, warm, noring):

@@ -290,7 +290,7 @@ def test_batch_sampled_on_device_matches_host_loop(golden_dir):
     assert _same(res[True][2], res[False][2])
     assert res[True][3:] == res[False][3:] and res[True][3] > 0
     sess = [s for s in G._BATCH_SESSIONS.values() if s.R == 3 and s.model is m]
-    assert sess and getattr(sess[0], "g_tp", None) is not None  # the device sampler ran
+    assert sess and sess[0]._graphs["stream"].bufs["g_tp"] is not None  # the device sampler ran
 
 
 def test_other_t_and_p_replay_the_same_captured_graph(golden_dir):
@@ -319,7 +319,7 @@ def test_other_t_and_p_replay_the_same_captured_graph(golden_dir):
         assert _same(_rng_state(), st_want)
         sess = [s for s in G._BATCH_SESSIONS.values() if s.R == 1 and s.model is m]
         assert len(sess) == 1
-        graphs.append(sess[0]._greedy["graph"])
+        graphs.append(sess[0]._greedy.graph)
     assert graphs[1] is graphs[0] and graphs[2] is graphs[0]
 
 

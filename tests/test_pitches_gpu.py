@@ -513,11 +513,11 @@ def test_another_set_replays_and_unconstrained_calls_keep_their_tokens(micro, sp
         plain = sess._graphs[mode]
         a, sp_a = call(pitches=A)
         entry = sess._graphs[mode + "+ban"]
-        graph = entry["graph"]
+        graph = entry.graph
         assert sess._greedy is entry
         b, sp_b = call(pitches=B)
         assert _sessions(G, m, 1)[0] is sess
-        assert sess._graphs[mode + "+ban"] is entry and entry["graph"] is graph  # replayed
+        assert sess._graphs[mode + "+ban"] is entry and entry.graph is graph  # replayed
         assert _inside(v, sp_a, a, {0: _ok_ids(v, A)}) > 0
         assert _inside(v, sp_b, b, {0: _ok_ids(v, B)}) > 0
         assert a != b and a != before

@@ -217,8 +217,8 @@ def test_seeded_batch_on_device_matches_host_loop(micro):
     assert res[True] == res[False]
     assert res[True][2] > 0 and res[True][4] == [5, 6, 7]
     sess = _sessions(G, m, 3)
-    assert sess and getattr(sess[0], "g_mt_rows", None) is not None  # the rows kernel ran
-    assert getattr(sess[0], "g_mt", None) is None  # and the shared-stream one did not
+    assert sess and "g_mt_rows" in sess[0]._graphs["rows"].bufs  # the rows kernel ran
+    assert not any(k.startswith("stream") for k in sess[0]._graphs)  # and the shared-stream one did not
 
 
 @pytest.mark.parametrize("tp", [dict(), dict(t=0.8, p=0.9)], ids=["default", "t0.8p0.9"])
@@ -332,12 +332,13 @@ def test_seeded_and_unseeded_graphs_live_side_by_side(micro):
         assert len(sess) == 1
         mode = "rows" if "seed" in kw else "stream"
         assert sess[0]._greedy is sess[0]._graphs[mode]
-        seen.append((sess[0], {k: e["graph"] for k, e in sess[0]._graphs.items()}))
+        seen.append((sess[0], {k: e.graph for k, e in sess[0]._graphs.items()}))
     assert set(seen[0][1]) == {"rows"} and set(seen[1][1]) == {"rows", "stream"}
     for s, graphs in seen[2:]:
         assert s is seen[1][0]
         assert all(graphs[k] is seen[1][1][k] for k in ("rows", "stream")) and len(graphs) == 2
-    assert sess[0].g_mt is not None and sess[0].g_mt_rows is not None
+    assert sess[0]._graphs["stream"].bufs["g_mt"] is not None
+    assert sess[0]._graphs["rows"].bufs["g_mt_rows"] is not None
 
 
 def test_seed_none_spelled_out_equals_omitted(micro):
@@ -356,6 +357,46 @@ def test_seed_none_spelled_out_equals_omitted(micro):
         assert stats["seeds"] is None
         res[bool(kw)] = (outs, _rng_state())
         sess = _sessions(G, m, 3)  # the shared-stream sampler, as before
-        assert sess and sess[0].g_mt is not None and getattr(sess[0], "g_mt_rows", None) is None
+        assert sess and sess[0]._graphs["stream"].bufs["g_mt"] is not None
+        assert not any(k.startswith("rows") for k in sess[0]._graphs)
+        assert "g_mt_rows" not in sess[0]._graphs["stream"].bufs
     assert res[True][0] == res[False][0]
     assert _same(res[True][1], res[False][1])
+
+
+def test_grammar_graphs_are_recaptured_after_the_positional_table_moved(micro):
+    """A second session whose capacity exceeds the model's positional table
+    reallocates it (pos_enc.extend), and the warm session's captured step +
+    grammar graphs address the freed one.  The next calls run on the same
+    warm session with newly captured graphs and return what they returned
+    before: tokens equal, log-probabilities bit for bit."""
+    from smer_music_generation_amd import generation as G
+    from smer_music_generation_amd.decode import DecodeSession
+    m, v, reqs, ctl = micro
+    G.clear_decode_sessions(m)
+
+    def calls():
+        res = []
+        for kw in (dict(greedy=True), dict(greedy=False, seed=[5, 6, 7], t=[1.0, 0.7, 1.3], p=[None, 0.9, 0.5])):
+            out, st = G.generation_batch(m, [(list(e), t, b) for e, t, b in reqs], v, ctl, precision="fp32",
+                                         logprobs=True, return_stats=True, **kw)
+            res.append(([_str(o) for o in out], st["generated"], st["steps"],
+                        [a.tobytes() for a in st["logprobs"]]))
+        (sess,) = _sessions(G, m, 3)
+        return res, sess, {k: e.graph for k, e in sess._graphs.items()}
+    calls()
+    want, sess, graphs = calls()  # warm: the session and both graphs of the first round
+    assert set(graphs) == {"greedy+score", "rows+score"}
+    assert all(sum(len(g) for g in r[1]) > 0 and r[2] > 0 for r in want)
+    pe = m.pos_enc.pe
+    old_ptr, rows = pe.data_ptr(), pe.shape[0]
+    other = DecodeSession(m, 1, rows + 8, 8)  # extends the table
+    assert m.pos_enc.pe.data_ptr() != old_ptr and m.pos_enc.pe.shape[0] >= rows + 8
+    del pe
+    junk = [torch.full((rows, 1, m.pos_enc.pe.shape[2]), 1e4, device=dev) for _ in range(8)]
+    got, sess2, graphs2 = calls()
+    del junk, other
+    assert sess2 is sess and set(graphs2) == set(graphs)
+    assert all(graphs2[k] is not graphs[k] for k in graphs)
+    assert sess._greedy is sess._graphs["rows+score"]
+    assert got == want

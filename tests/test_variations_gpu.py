@@ -268,7 +268,7 @@ def test_batch_variations_equal_the_expanded_list(golden_dir, name, kw, monkeypa
         assert len(sess) == 1
         assert sess[0].cross_kv[0].shape[0] == 3 and sess[0].self_kv[0].shape[0] == 6
         if kw.get("precision") is None and kw.get("device_grammar", True):
-            assert sess[0]._shared  # the grouped kernels ran
+            assert sess[0].plan.shared  # the grouped kernels ran
     finally:
         G.clear_decode_sessions(m)
         m.set_precision("bf16")
@@ -338,8 +338,8 @@ def test_other_splits_replay_the_same_captured_graph(golden_dir, switch, monkeyp
             got = _batch(m, v, reqs, ctl, takes, expanded=False, greedy=False)
             _assert_same_run(got, want)
             sess = [s for s in G._BATCH_SESSIONS.values() if s.model is m and s.R == 6 and s.NS == 3]
-            assert len(sess) == 1 and sess[0]._shared == (switch == "1")
-            graphs.append(sess[0]._greedy["graph"])
+            assert len(sess) == 1 and sess[0].plan.shared == (switch == "1")
+            graphs.append(sess[0]._greedy.graph)
     finally:
         G.clear_decode_sessions(m)
     assert graphs[1] is graphs[0]
@@ -364,7 +364,7 @@ def test_default_and_switch_off_run_the_per_row_kernels(golden_dir, name, switch
     try:
         got = _batch(m, v, reqs, ctl, TAKES, expanded=False, greedy=False)
         sess = [s for s in G._BATCH_SESSIONS.values() if s.model is m and s.NS == 3]
-        assert len(sess) == 1 and not sess[0]._shared
+        assert len(sess) == 1 and not sess[0].plan.shared
         assert sess[0].cross_kv[0].shape[0] == 3
     finally:
         G.clear_decode_sessions(m)

@@ -94,7 +94,7 @@ def breakdown():
             T[name + "_n"] = T.get(name + "_n", 0) + 1
             return r
         setattr(cls, name, g)
-    for n in ("__init__", "prefill", "_capture_greedy", "sampled_decode"):
+    for n in ("__init__", "prefill", "_capture_grammar", "sampled_decode"):
         wrap(decode.DecodeSession, n)
     args = bench.parse_args([])
     dev = torch.device("cuda:0")

@@ -1,6 +1,6 @@
 """Where the first (cold) generation_batch call's capture time goes: the
 greedy decode graph (decoder step + grammar kernel) captured for three fresh
-sessions in one process, with the phases of DecodeSession._capture_greedy
+sessions in one process, with the phases of DecodeSession._capture_grammar
 timed separately (eager warm step, stream capture, instantiate = first
 replay), C2 model, R = 32 requests -- with the caching allocator first
 filled the way a training step leaves it (torch.cuda.graph's __enter__
