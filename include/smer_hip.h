@@ -49,6 +49,8 @@
  *   smer_logprob_stage / _commit  the log-probability of each drawn token (the
  *                        log of sampling()'s distribution at t = 1), taken
  *                        around any grammar step
+ *   smer_logprob_rows    the same number for given tokens at many rows of one
+ *                        full forward, each at its own grammar state
  *   smer_layernorm_*   residual LayerNorm, eps 1e-5 (transformer.py:392,395,
  *                        462,466,469; final norms 274-275, 329-330)
  *   smer_embed_*         embedding gather x sqrt(d) + sinusoidal PE + dropout
@@ -455,6 +457,23 @@ int smer_logprob_stage(int R, int V, const float* logits, long ldl, const int32_
 int smer_logprob_commit(int R, int V, const int32_t* state, int nst, const int32_t* stage,
                         const int32_t* out_tok, int cap, const double* scratch, long ldp,
                         double* out_lp, smer_stream_t stream);
+/* Scores of given content (not a reference operation): the same number for a
+ * known token at many rows of one full forward, each at its own grammar
+ * state.  For entry n < N: r = row[n] (a row of logits float32 [nrows, ldl]),
+ * c = code[n] (0..12), k = ban_idx[n] (int8, -1 = none), t = id[n];
+ *   x_i = keep[c * V + i] && !(bit i % 32 of ban_bits[k * 16 + i / 32]) ?
+ *         (double)logits[r * ldl + i] : -100.0,  lse = max + log(sum exp(x_i -
+ *   max)) in float64;  out_lp[n] = x_t - lse;  out_arg[n] = the first index
+ *   of the maximum of x (the masked argmax, smer_grammar_greedy_step's rule).
+ * row may name the rows in any order and repeat them.  ban_bits uint32 [K,
+ * 16] may be null when K = 0.  Every lookup is clamped into its table; an
+ * entry whose id is outside [0, V) or whose row is outside [0, nrows) writes
+ * neither output.  Nothing but out_lp / out_arg is written.  1 <= V <= 512,
+ * 0 <= K <= 127, N > 0.  Status return, no allocation, no synchronisation. */
+int smer_logprob_rows(int N, int V, int nrows, const float* logits, long ldl, const int32_t* row,
+                      const uint8_t* code, const uint8_t* keep, const int8_t* ban_idx,
+                      const uint32_t* ban_bits, int K, const int32_t* id, double* out_lp,
+                      int32_t* out_arg, smer_stream_t stream);
 
 int smer_layernorm_fwd(int dtype, int M, int N, const void* x, long ldx,
                        const float* gamma, const float* beta, float eps,

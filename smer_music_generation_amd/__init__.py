@@ -8,7 +8,7 @@ all running hand-written gfx950 kernels from libsmer_hip.so (include/smer_hip.h)
 from .vocab import WordVocab  # noqa: F401
 
 __all__ = ["WordVocab", "ScoreTransformer", "Trainer", "generation_all", "infill",
-           "model_generate", "generation_batch"]
+           "model_generate", "generation_batch", "score_infill", "score_batch", "InfillScore"]
 
 
 def __getattr__(name):  # lazy: importing torch-heavy modules only when used
@@ -18,7 +18,8 @@ def __getattr__(name):  # lazy: importing torch-heavy modules only when used
     if name == "Trainer":
         from .train import Trainer
         return Trainer
-    if name in ("generation_all", "infill", "model_generate", "generation_batch"):
+    if name in ("generation_all", "infill", "model_generate", "generation_batch", "score_infill",
+                "score_batch", "InfillScore"):
         from . import generation
         return getattr(generation, name)
     raise AttributeError(name)

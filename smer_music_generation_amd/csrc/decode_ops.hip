@@ -1165,3 +1165,87 @@ extern "C" int smer_logprob_commit(int R, int V, const int32_t* state, int nst, 
   SMER_CHECK_LAUNCH("smer_logprob_commit");
   return SMER_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Scores of given content: the log-probability of a known token at many rows
+// of ONE full (teacher-forced) forward, each row at its own grammar state --
+// the number logprob_stage_kernel forms for one live row per request, without
+// a step loop or a state vector: the host plan (generation._forced_plan) names
+// every scored entry's logits row, state code, ban row and token.
+//   x_i = (keep[code][i] && !banned_i) ? (double)logit_i : -100.0,
+//   m = max x, lse = m + log(sum exp(x_i - m)) in float64,
+//   out_lp[n] = x[id] - lse, out_arg[n] = the first index of the maximum of x
+//   (the greedy kernel's rule on the same masked row).
+// One wave per entry, 8 tokens per lane (V <= 512); lane l owns tokens 8l ..
+// 8l + 7, which are byte l & 3 of ban word l / 4.  x[id] comes from its
+// owning lane by shuffle.  Every lookup is clamped (row, code, ban row,
+// token), only the two stores are predicated: an entry whose id is outside
+// [0, V) or whose row is outside [0, nrows) writes nothing.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void logprob_rows_kernel(
+    int N, int V, int nrows, const float* __restrict__ logits, long ldl, const int32_t* __restrict__ row,
+    const uint8_t* __restrict__ code, const uint8_t* __restrict__ keep, const int8_t* __restrict__ ban_idx,
+    const uint32_t* __restrict__ ban_bits, int K, const int32_t* __restrict__ id,
+    double* __restrict__ out_lp, int32_t* __restrict__ out_arg) {
+  const int n = blockIdx.x, lane = threadIdx.x;
+  const int rw = row[n], tok = id[n], bk = (int)ban_idx[n];
+  const int rc = min(max(rw, 0), nrows - 1);
+  const int cc = min((int)code[n], 12);
+  uint32_t b = 0u;
+  if (K > 0) {  // kernel-uniform: with K = 0 the table may be null
+    const uint32_t w = ban_bits[(long)min(max(bk, 0), K - 1) * 16 + (lane >> 2)];
+    if (bk >= 0 && bk < K) b = (w >> (8 * (lane & 3))) & 0xffu;
+  }
+  const uint8_t* kp = keep + (long)cc * V;
+  const float* lr = logits + (long)rc * ldl;
+  double x[8];
+  double m = -INFINITY;
+  int bi = 0x7fffffff;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int i = lane * 8 + j, ic = min(i, V - 1);
+    const float lg = lr[ic];
+    x[j] = (kp[ic] && !((b >> j) & 1u)) ? (double)lg : -100.0;
+    if (i < V && (x[j] > m || bi == 0x7fffffff)) { m = x[j]; bi = i; }  // ascending i: first max kept
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double om = __shfl_xor(m, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (om > m || (om == m && oi < bi)) { m = om; bi = oi; }  // both partners keep the same pair
+  }
+  double s = 0.;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (lane * 8 + j < V) s += exp(x[j] - m);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);  // a + b = b + a: every lane ends on the same sum
+  const double lse = m + log(s);
+  const int tc = min(max(tok, 0), V - 1);
+  double xt = x[0];
+#pragma unroll
+  for (int j = 1; j < 8; ++j) xt = (tc & 7) == j ? x[j] : xt;  // selects, no indexed register array
+  xt = __shfl(xt, tc >> 3, 64);
+  if (lane == 0 && tok >= 0 && tok < V && rw >= 0 && rw < nrows) {
+    out_lp[n] = xt - lse;
+    out_arg[n] = bi;
+  }
+}
+
+// Graph-capturable, no allocation, no synchronisation.  logits float32
+// [nrows, ldl]; row / code / ban_idx / id / out_lp / out_arg have N entries;
+// keep uint8 [13, V]; ban_bits uint32 [K, 16], null allowed when K = 0.
+extern "C" int smer_logprob_rows(int N, int V, int nrows, const float* logits, long ldl, const int32_t* row,
+                                 const uint8_t* code, const uint8_t* keep, const int8_t* ban_idx,
+                                 const uint32_t* ban_bits, int K, const int32_t* id, double* out_lp,
+                                 int32_t* out_arg, smer_stream_t stream) {
+  SMER_REQUIRE(N > 0 && V > 0 && V <= 512 && nrows > 0 && K >= 0 && K <= 127,
+               "smer_logprob_rows: sizes (1 <= V <= 512, 0 <= K <= 127)");
+  SMER_REQUIRE(ldl >= V, "smer_logprob_rows: logits row stride");
+  SMER_REQUIRE(logits && row && code && keep && ban_idx && id && out_lp && out_arg && (ban_bits || K == 0),
+               "smer_logprob_rows: null pointer");
+  hipLaunchKernelGGL(logprob_rows_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, N, V, nrows, logits,
+                     ldl, row, code, keep, ban_idx, ban_bits, K, id, out_lp, out_arg);
+  SMER_CHECK_LAUNCH("smer_logprob_rows");
+  return SMER_OK;
+}

@@ -30,6 +30,9 @@ Differences, all opt-in keywords with reference defaults:
     every drawn token (`token_logprobs`: t = 1, the whole masked
     distribution) and each take's sum in `stats`; `rank=True` orders the
     takes of `variations=` by their mean log-probability per token.
+  * `score_infill(...)` / `score_batch(...)`: the same log-probabilities for
+    GIVEN content (the bar that was there, an edited take, another
+    checkpoint's take), teacher-forced: one full forward, no step loop.
 The grammar state machine, the -100 logit masking, the float64 softmax and
 the numpy RNG consumption are the reference's, so with the same
 `np.random` state the same token ids come out.
@@ -37,13 +40,14 @@ the numpy RNG consumption are the reference's, so with the same
 from __future__ import annotations
 
 import time
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from .decode import DecodeSession
 from .durations import durations_for_events
-from .wire import (change_controls, fill_empty_bars, mask_bar_and_track,  # noqa: F401
+from .wire import (change_controls, decoder_targets, fill_empty_bars, mask_bar_and_track,  # noqa: F401
                    mask_targets, restore_marked_input, track_names_of)
 
 
@@ -1281,3 +1285,331 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                      "seeds": seeds, "pitches": allowed, "sources": len(srcs), "prefill_rows": int(sess.prefill_rows),
                      "decode_phases_s": dict(sess.phase_s)}
     return out
+
+
+# --------------------------------------------------------------------------
+# scores of given content: teacher-forced infill log-probabilities
+# --------------------------------------------------------------------------
+MAX_BODY = 98  # tokens of a note span the 100-token cap keeps: m_0 + 98, the 99th draw is dropped
+
+
+class InfillScore(NamedTuple):
+    """What score_infill / score_batch return for one request, entry for
+    entry in the order the decode would have drawn the tokens."""
+    logprobs: np.ndarray    # float64 [n]: token_logprobs(logit row, keep)[token]
+    score: float            # their sum
+    tokens: np.ndarray      # int64 [n]: the scored ids, <eos> included where it is scored
+    mask_index: np.ndarray  # int32 [n]: the mask (in mask_targets order) of each entry
+    greedy: np.ndarray      # int64 [n]: the masked argmax at each position (first index on ties)
+
+
+class _ForcedPlan(NamedTuple):
+    """The scoring plan of one request (host only): the decoder input and,
+    per scored entry, the decoder row whose logits predict it, the grammar
+    state code of that draw, the ban row (-1: none), the token and its mask."""
+    src: np.ndarray
+    tgt: list
+    row: np.ndarray
+    code: np.ndarray
+    ban_idx: np.ndarray
+    ids: np.ndarray
+    mask_index: np.ndarray
+    ban_rows: object  # boolean [k, V], or None
+
+
+def _content_ids(vocab, bodies):
+    """Given content as id lists: token strings through the vocabulary, ints
+    as they are.  m_0, <eos>, an unknown string or an id outside the
+    vocabulary raises ValueError."""
+    V, table = vocab.vocab_size, vocab._char2idx
+    m0, eos = vocab.char2index('m_0'), vocab.eos_index
+    out = []
+    for k, body in enumerate(bodies):
+        if isinstance(body, (str, bytes)) or not hasattr(body, "__iter__"):
+            raise ValueError("content: span %d is not a sequence of tokens (got %r)" % (k, body))
+        seq = []
+        for x in (body.tolist() if isinstance(body, np.ndarray) else body):
+            if isinstance(x, str):
+                x = table.get(x)
+            elif isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+                x = None
+            if x is None or not 0 <= x < V:
+                raise ValueError("content: span %d holds a token that is not in the vocabulary" % k)
+            if x == m0 or x == eos:
+                raise ValueError("content: span %d holds m_0 or <eos> (the bodies carry neither)" % k)
+            seq.append(int(x))
+        out.append(seq)
+    return out
+
+
+def _split_targets(vocab, stream):
+    """The bodies of `decoder_targets`' stream [m_0, tokens..., <eos>] per
+    span."""
+    m0, eos = vocab.mask_indices[0], vocab.eos_index
+    bodies = []
+    for x in stream:
+        if x == m0:
+            bodies.append([])
+        elif not bodies:
+            raise ValueError("content: the target stream does not start with m_0")
+        else:
+            bodies[-1].append(x)
+    for b in bodies:
+        if b and b[-1] == eos:
+            del b[-1]
+    return bodies
+
+
+def _forced_plan(vocab, src, target, all_controls, no_whole, bodies, bans=None):
+    """Replay given content through a `_Span` without drawing: before every
+    commit(id) the decoder row that predicts the token (the row of the input
+    token before it), the span's state_code(), the ban row of the mask and
+    the id are recorded.  The decoder input is the span's final tgt_inp,
+    [m_0, body...] per mask.  Scored is exactly what the decode would have
+    drawn: a control span its one token (the <eos> commit() appends is not
+    drawn); a note span of n <= 97 tokens those and the <eos> that ends it; a
+    note span of MAX_BODY tokens those alone (the cap ended it: the decode's
+    99th draw is dropped whatever it is).  A note span whose last token is a
+    control token was ended by that token (commit() appends the <eos>
+    undrawn), so no <eos> is scored for it, and such a span may hold 99
+    tokens -- the take the decode itself returns when its 99th draw is a
+    control.  Raises ValueError for a wrong number of spans, a control span
+    that does not hold one token, a longer note body, or tokens after the one
+    that ends a span; touches neither the model nor np.random."""
+    sp = _Span(vocab, src, target, all_controls, no_whole, True, None, bans=bans)
+    if sp.n_masks == 0:
+        raise ValueError("nothing is masked: there is nothing to score")
+    if len(bodies) != sp.n_masks or len(target) < sp.n_masks:
+        raise ValueError("content: %d spans for %d masks" % (len(bodies), sp.n_masks))
+    ctrl = sp.all_controls
+    for k, body in enumerate(bodies):
+        if _target_code(target[k]) != 0:
+            if len(body) != 1:
+                raise ValueError("content: span %d is a control span and holds one token (got %d)"
+                                 % (k, len(body)))
+        elif len(body) > MAX_BODY and not (len(body) == MAX_BODY + 1 and body[-1] in ctrl):
+            raise ValueError("content: span %d holds %d tokens, a note span at most %d"
+                             % (k, len(body), MAX_BODY))
+    row, code, bidx, ids, midx = [], [], [], [], []
+
+    def record(k, tok):
+        row.append(len(sp.tgt_inp) + len(sp.this_in) - 1)
+        code.append(sp.state_code())
+        bidx.append(-1 if sp.ban_of_mask is None else int(sp.ban_of_mask[k]))
+        ids.append(tok)
+        midx.append(k)
+    for k, body in enumerate(bodies):
+        for tok in body:
+            if sp.mask_idx != k:
+                raise ValueError("content: span %d goes on after the token that ends it" % k)
+            record(k, tok)
+            sp.commit(tok)
+        if sp.mask_idx == k:  # still open: ended by <eos> (drawn, unless the cap or a control span ends it)
+            if _target_code(target[k]) == 0 and len(sp.this_in) < MAX_BODY + 1:
+                record(k, sp.eos)
+            sp.commit(sp.eos)
+    return _ForcedPlan(np.asarray(src, dtype=np.int64), list(sp.tgt_inp), np.asarray(row, dtype=np.int32),
+                       np.asarray(code, dtype=np.uint8), np.asarray(bidx, dtype=np.int8),
+                       np.asarray(ids, dtype=np.int64), np.asarray(midx, dtype=np.int32),
+                       None if sp.ban_rows is None else np.asarray(sp.ban_rows, dtype=bool))
+
+
+def _score_plan(vocab, events, tracks_to_generate, bars_to_generate, all_controls, content, allowed):
+    """The plan of one request from its events: `_prepare`'s masked source
+    and, with content None, the events' own content at the masked positions
+    (`decoder_targets` of the events `_prepare` masked, empty bars filled in
+    where it fills them).  Host only."""
+    events = list(events)
+    if len(bars_to_generate) == 0 or len(tracks_to_generate) == 0:
+        raise ValueError("nothing is masked: there is nothing to score")
+    bans = _request_bans(vocab, events, tracks_to_generate, bars_to_generate, allowed)
+    # (fill_empty_bars appends to the list it is given: `events` is the masked song afterwards)
+    src, _, _, target, no_whole = _prepare(events, vocab, tracks_to_generate, bars_to_generate)
+    if content is None:
+        _, tracks = mask_targets(events, tracks_to_generate, bars_to_generate)
+        bodies = _split_targets(vocab, decoder_targets(events, vocab, tracks, bars_to_generate))
+    else:
+        if isinstance(content, (str, bytes)) or not hasattr(content, "__len__"):
+            raise ValueError("content: one token sequence per mask (got %r)" % (content,))
+        bodies = list(content)
+    return _forced_plan(vocab, src, target, all_controls, no_whole, _content_ids(vocab, bodies), bans)
+
+
+def _plan_keep(vocab, plan, n):
+    """The boolean keep of entry n: allowed_ids of its state, & ~ban."""
+    keep = allowed_ids(vocab, **grammar_spec(vocab, int(plan.code[n]))[0])
+    k = int(plan.ban_idx[n])
+    return keep if k < 0 else keep & ~plan.ban_rows[k]
+
+
+def _host_scores(vocab, plan, logits):
+    """The definition, entry by entry: token_logprobs of logits[plan.row[n]]
+    under the entry's keep at its id, and the masked argmax.  logits: a
+    float32 array (or a dict) of rows indexed by decoder row."""
+    lp = np.empty(len(plan.ids), dtype=np.float64)
+    arg = np.empty(len(plan.ids), dtype=np.int64)
+    for n in range(len(plan.ids)):
+        keep = _plan_keep(vocab, plan, n)
+        r = logits[int(plan.row[n])]
+        lp[n] = token_logprobs(r, keep)[plan.ids[n]]
+        arg[n] = np.argmax(np.where(keep, np.asarray(r, dtype=np.float32).astype(np.float64), -100.0))
+    return lp, arg
+
+
+def _score_forward(model, plans):
+    """One full forward (no_grad, eval) over all plans, sources and targets
+    padded to the longest under the three key padding masks; the
+    cross-attention weights are not computed.  Returns logits [B, T, V]."""
+    dev = model.embedding.weight.device
+    B = len(plans)
+    S, T = max(len(q.src) for q in plans), max(len(q.tgt) for q in plans)
+    src, tgt = np.zeros((B, S), dtype=np.int64), np.zeros((B, T), dtype=np.int64)
+    spad, tpad = np.ones((B, S), dtype=bool), np.ones((B, T), dtype=bool)
+    for b, q in enumerate(plans):
+        src[b, :len(q.src)], spad[b, :len(q.src)] = q.src, False
+        tgt[b, :len(q.tgt)], tpad[b, :len(q.tgt)] = q.tgt, False
+    spad_t = torch.from_numpy(spad).to(dev)
+    model.eval()
+    need = model.need_weights
+    model.need_weights = False
+    try:
+        with torch.no_grad():
+            out, _ = model.forward(torch.from_numpy(src).to(dev), torch.from_numpy(tgt).to(dev),
+                                   src_key_padding_mask=spad_t,
+                                   tgt_key_padding_mask=torch.from_numpy(tpad).to(dev),
+                                   memory_key_padding_mask=spad_t.clone(),
+                                   tgt_mask=gen_nopeek_mask(T).unsqueeze(0).to(dev))
+    finally:
+        model.need_weights = need
+    return out
+
+
+def _device_scores(vocab, all_controls, plans, logits):
+    """smer_logprob_rows over every scored entry of every plan: one launch
+    (one per group of requests whose ban rows together exceed the kernel's
+    127) and one device-to-host copy of both outputs.  logits [B, T, V]
+    float32 on the device."""
+    from . import ops
+    B, T, V = logits.shape
+    dev = logits.device
+    flat = logits.reshape(B * T, V)
+    keep = torch.from_numpy(grammar_tables(vocab, all_controls)[0]).to(dev)
+    groups, cur, k_cur = [], [], 0
+    for b, q in enumerate(plans):
+        k = 0 if q.ban_rows is None else len(q.ban_rows)
+        if cur and k_cur + k > 127:
+            groups.append(cur)
+            cur, k_cur = [], 0
+        cur.append(b)
+        k_cur += k
+    groups.append(cur)
+    lps, args = {}, {}
+    for grp in groups:
+        rows, bidx, bits, k0 = [], [], [], 0
+        for b in grp:
+            q = plans[b]
+            rows.append(q.row.astype(np.int64) + b * T)
+            bidx.append(np.where(q.ban_idx >= 0, q.ban_idx.astype(np.int64) + k0, -1))
+            if q.ban_rows is not None:
+                bits.append(ban_bits(q.ban_rows))
+                k0 += len(q.ban_rows)
+        N = sum(len(r) for r in rows)
+        put = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.concatenate(a).astype(dt))).to(dev)  # noqa: E731
+        out = torch.empty(12 * N, dtype=torch.uint8, device=dev)  # float64 [N] | int32 [N]: one copy back
+        ops.logprob_rows(flat, put(rows, np.int32), put([plans[b].code for b in grp], np.uint8), keep,
+                         put(bidx, np.int8), put([x.view(np.int32) for x in bits], np.int32) if bits else None,
+                         put([plans[b].ids for b in grp], np.int32), out[:8 * N].view(torch.float64),
+                         out[8 * N:].view(torch.int32))
+        host = out.cpu().numpy()
+        lp, arg, at = host[:8 * N].view(np.float64), host[8 * N:].view(np.int32), 0
+        for b in grp:
+            n = len(plans[b].ids)
+            lps[b], args[b] = lp[at:at + n].copy(), arg[at:at + n].astype(np.int64)
+            at += n
+    return [lps[b] for b in range(B)], [args[b] for b in range(B)]
+
+
+def score_batch(model, requests, vocab, all_controls, *, contents=None, pitches=None, precision=None,
+                device_score=True):
+    """Teacher-forced log-probabilities of given infill content: what
+    `logprobs=True` reports for the tokens a decode draws, for tokens it did
+    not draw -- the bar that was there before masking, a take edited by hand,
+    a take of another checkpoint or precision.  All tokens are known, so
+    there is no step loop: ONE full forward over all requests (no_grad, eval,
+    causal mask, sources and targets padded to the longest under the key
+    padding masks, no cross-attention weights), then one launch of
+    smer_logprob_rows over every scored entry and one copy back.
+
+    requests: list of (events, tracks_to_generate, bars_to_generate), as
+    generation_batch takes them.
+    contents: None, or one value per request: None scores the events' own
+    content at the masked positions (what wire.decoder_targets extracts, after
+    the empty bars _prepare fills in) -- so the default call scores the
+    original bar, and a take is scored by passing its restored tokens as
+    `events`; otherwise a list with one sequence of token strings or ids per
+    mask, in mask_targets order, without m_0 and without <eos>.
+    What is scored is exactly what the decode would have drawn (see
+    _forced_plan): a control span (d / o / p / t) its one token; a note span
+    of n <= 97 tokens those and the <eos> after them, n + 1 entries; a note
+    span of exactly 98 tokens was ended by the 100-token cap, so its 98
+    tokens are scored and no end token is -- the decode's 99th draw is dropped
+    whatever it is, so summed over it the probability is 1.  A note span
+    whose last token is a control token was ended by that token and scores no
+    <eos> either.  Every number is token_logprobs(logit row, keep)[id] with
+    keep = allowed_ids(grammar state) & ~ban: the same float32 -> float64
+    widening, -100.0 and maximum subtraction.  A token outside the state's
+    keep set, or banned under `pitches`, is not an error: it scores from x =
+    -100 like any other entry.
+    pitches: as generation_batch (one value, or one per request).
+    precision: arithmetic of the forward (None: the model's own).
+    device_score: False, or a vocabulary above 512 tokens, copies the needed
+    logits rows to the host and applies token_logprobs per entry (the
+    definition).
+    Raises ValueError -- before the model or np.random is touched -- for a
+    request with nothing masked, a wrong number of spans, a control span whose
+    length is not 1, a note body longer than 98 tokens, m_0, <eos> or an
+    unknown token in a body, tokens after the one that ends a span, or a bad
+    pitches.  np.random is neither read nor written, and the warm decode
+    sessions are left alone.  Returns one InfillScore per request."""
+    n = len(requests)
+    if n == 0:
+        raise ValueError("no request to score")
+    if not isinstance(device_score, (bool, np.bool_)):
+        raise ValueError("device_score must be True or False (got %r)" % (device_score,))
+    if precision not in (None, "fp32", "bf16", "fp8"):
+        raise ValueError("precision must be None, 'fp32', 'bf16' or 'fp8' (got %r)" % (precision,))
+    if contents is None:
+        contents = [None] * n
+    elif not isinstance(contents, (list, tuple)) or len(contents) != n:
+        raise ValueError("contents: None, or one value per request (%d)" % n)
+    allowed = _check_pitches(pitches, [tr for _, tr, _ in requests], n)
+    plans = [_score_plan(vocab, ev, tr, br, all_controls, c, a)
+             for (ev, tr, br), c, a in zip(requests, contents, allowed)]
+    with _Precision(model, precision):
+        logits = _score_forward(model, plans)
+        if device_score and vocab.vocab_size <= 512 and logits.is_cuda:
+            lps, args = _device_scores(vocab, all_controls, plans, logits.float().contiguous())
+        else:
+            lps, args = [], []
+            for b, q in enumerate(plans):
+                need = np.unique(q.row)
+                got = logits[b].index_select(0, torch.from_numpy(need.astype(np.int64)).to(logits.device))
+                lp, arg = _host_scores(vocab, q, dict(zip(need.tolist(), got.float().cpu().numpy())))
+                lps.append(lp)
+                args.append(arg)
+    return [InfillScore(lp, float(np.sum(lp)), q.ids.copy(), q.mask_index.copy(), arg)
+            for q, lp, arg in zip(plans, lps, args)]
+
+
+def score_infill(model, events, device, vocab, all_controls, tracks_to_generate, bars_to_generate, *,
+                 content=None, pitches=None, precision="fp32", device_score=True):
+    """score_batch for one request, with the plugin call's defaults: the
+    forward runs in fp32 whatever precision the model trains in (None: the
+    model's own).  content: None (the events' own content at the masked
+    positions), or one token sequence per mask.  `device` is accepted for
+    symmetry with generation_all; the forward runs where the model is.
+    Returns an InfillScore; raises ValueError as score_batch does."""
+    return score_batch(model, [(events, tracks_to_generate, bars_to_generate)], vocab, all_controls,
+                       contents=[content], pitches=None if pitches is None else [
+                           _check_pitches(pitches, tracks_to_generate)],
+                       precision=precision, device_score=device_score)[0]

@@ -796,6 +796,40 @@ def logprob_commit(state, stage, out_tok, scratch, out_lp, *, V):
          _p(scratch), _ld(scratch), _p(out_lp), _stream())
 
 
+def logprob_rows(logits, row, code, keep, ban_idx, ban_bits, ids, out_lp, out_arg):
+    """Scores of given tokens at many rows of one forward (smer_logprob_rows):
+    for entry n, out_lp[n] = token_logprobs(logits[row[n]], keep[code[n]] &
+    ~ban)[ids[n]] in float64 and out_arg[n] the masked argmax of that row
+    (first index on ties).  logits float32 [nrows, V <= 512] (rows
+    contiguous), row int32 [N] (any order, repeats allowed), code uint8 [N]
+    (grammar state 0..12), keep uint8 [13, V], ban_idx int8 [N] (-1: no ban),
+    ban_bits int32 [K, 16] (the bits of uint32 words: token v is bit v % 32 of
+    word v // 32; K <= 127) or None (K = 0), ids int32 [N], out_lp float64
+    [N], out_arg int32 [N].  An entry whose id is outside [0, V) or whose row
+    is outside [0, nrows) leaves its outputs alone.  Only the outputs are
+    written."""
+    N = row.numel()
+    if logits.dim() != 2:
+        raise RuntimeError("logprob_rows: logits must be 2-D")
+    nrows, V = logits.shape
+    for t, dt in ((logits, torch.float32), (row, torch.int32), (code, torch.uint8), (keep, torch.uint8),
+                  (ban_idx, torch.int8), (ids, torch.int32), (out_lp, torch.float64),
+                  (out_arg, torch.int32)) + (((ban_bits, torch.int32),) if ban_bits is not None else ()):
+        if t.dtype != dt or t.device != logits.device:
+            raise RuntimeError("logprob_rows: expected %s on the logits' device" % dt)
+    if not all(t.is_contiguous() for t in (row, code, keep, ban_idx, ids, out_lp, out_arg)) or \
+            logits.stride(1) != 1 or (ban_bits is not None and not ban_bits.is_contiguous()):
+        raise RuntimeError("logprob_rows: expected contiguous tables and logits rows")
+    K = 0 if ban_bits is None else ban_bits.shape[0]
+    if N < 1 or nrows < 1 or not 1 <= V <= 32 * BAN_WORDS or tuple(keep.shape) != (13, V) or \
+            any(t.dim() != 1 or t.numel() != N for t in (row, code, ban_idx, ids, out_lp, out_arg)) or \
+            (ban_bits is not None and (ban_bits.dim() != 2 or ban_bits.shape[1] != BAN_WORDS or
+                                       not 1 <= K <= 127)):
+        raise RuntimeError("logprob_rows: shape mismatch")
+    call("smer_logprob_rows", N, V, nrows, _p(logits), _ld(logits), _p(row), _p(code), _p(keep),
+         _p(ban_idx), _p(ban_bits), K, _p(ids), _p(out_lp), _p(out_arg), _stream())
+
+
 # ---------------------------------------------------------------------------
 def layernorm(x, gamma, beta, y, mean, rstd, eps=1e-5):
     M, N = x.shape
