@@ -157,6 +157,37 @@ int smer_gemm_wgrad_fp8(int M, int N, int K, const void* dy8, long lddy, const v
  * never stamp.  Used by tools/gemm256s_phases.py. */
 int smer_gemm_debug_stamps(void* buf, size_t bytes);
 
+/* Diagnostics: what smer_gemm (rowsum 0) or smer_gemm_wgrad_bias_ex
+ * (SMER_PLAN_ROWSUM) would launch for a call, from the same decision the
+ * launchers run, without launching.  facts: the SMER_PLAN_* bits that hold
+ * for the call (an operand is passed, relu / dropout on, e.vec: every passed
+ * epilogue operand 16-B aligned with a row stride % 8, Cf 16-B aligned, a
+ * workspace passed; fp32: lda, ldb % 4 == 0 and A, B 16-B aligned).  cus: the
+ * CU count to plan for, 0 = the current device's; with cus > 0 no HIP call is
+ * made.  plan receives SMER_GEMM_PLAN_INTS ints: kernel id, template flags
+ * (bit 0 a_kcontig, 1 b_kcontig, 2 the skinny kernel's 4-step unroll), grid
+ * x, grid y, dynamic LDS bytes, split-K slices, their K depth, and the
+ * kernel id of the split-K reduction (-1: none).  smer_gemm_kernel_name:
+ * the name of a kernel id, NULL past the last.  Used by the GEMM edge tests. */
+#define SMER_PLAN_C 0x1
+#define SMER_PLAN_CF 0x2
+#define SMER_PLAN_BIAS 0x4
+#define SMER_PLAN_RELU 0x8
+#define SMER_PLAN_DROP 0x10
+#define SMER_PLAN_RESIDUAL 0x20
+#define SMER_PLAN_GATE 0x40
+#define SMER_PLAN_VEC 0x80
+#define SMER_PLAN_KV 0x100
+#define SMER_PLAN_Q8 0x200
+#define SMER_PLAN_CF_ALIGNED16 0x400
+#define SMER_PLAN_ROWSUM 0x800
+#define SMER_PLAN_WORKSPACE 0x1000
+#define SMER_PLAN_F32_ALIGNED 0x2000
+#define SMER_GEMM_PLAN_INTS 8
+int smer_gemm_plan(int dtype, int a_kcontig, int b_kcontig, int M, int N, int K, unsigned facts,
+                   long ldcf, size_t ws_bytes, int max_workgroups, int cus, int* plan);
+const char* smer_gemm_kernel_name(int kernel);
+
 /* Flash attention over [B*L, *] token-row layouts (row = b*L + i), head h
  * at column h*D.  kpm: uint8 [B, Lk] (1 = padded key) or NULL.  causal:
  * key j visible to query i iff j <= i.  lse: fp32 [B, H, Lq] (natural log).

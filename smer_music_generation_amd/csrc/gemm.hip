@@ -10,9 +10,14 @@
 // dgrad (NN) and wgrad (TN) all run without an explicit transpose pass.
 // f32 path (parity mode): LDS-tiled VALU FMA, same epilogue.
 #include "common.h"
+#include "gemm_plan.h"
+
+#include <unistd.h>  // environ
 
 #include <algorithm>
+#include <climits>
 #include <cstdlib>
+#include <cstring>
 
 struct GemmEpi {
   const float* bias;
@@ -326,13 +331,7 @@ __device__ __forceinline__ void splitk_tile_reduce(const GemmEpi& e, int M, int 
   }
 }
 
-// NSTG = 3 / 4 (weight gradients, LDS-DMA, one workgroup per CU): an
-// NSTG-stage LDS ring, each k-step's tiles requested NSTG - 1 steps ahead and
-// waited with a counted vmcnt before a raw barrier (the 2-stage form waits at the end of
-// every k-step for the tiles it requested at its start: one HBM round trip
-// per 64 of K against ~1 k cycles of MFMA work).  Fragment reads are asm,
-// so hipcc's wait insertion does not see them.
-template <bool AK, bool BKC, bool GL, int NSTG = 2>
+template <bool AK, bool BKC, bool GL>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(int M, int N, int K,
                                                            const bf16* __restrict__ A, long lda,
                                                            const bf16* __restrict__ B, long ldb,
@@ -399,17 +398,9 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(int M, int N, int K,
     f32x4 accr[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 
     const int nk = (k_end - k_begin + GBK - 1) / GBK;
-    static_assert(NSTG == 2 || ((NSTG == 3 || NSTG == 4) && GL && !AK && !BKC),
-                  "3 / 4 stages: LDS-DMA weight gradients only");
     if constexpr (GL) {
       stage_glds<AK>(smem, A, lda, M, m0, k_begin, tid);
       stage_glds<BKC>(smem + TILE_BYTES, B, ldb, N, n0, k_begin, tid);
-#pragma unroll
-      for (int p = 1; p < NSTG - 1; ++p)
-        if (NSTG > 2 && p < nk) {
-          stage_glds<AK>(smem + p * 2 * TILE_BYTES, A, lda, M, m0, k_begin + p * GBK, tid);
-          stage_glds<BKC>(smem + p * 2 * TILE_BYTES + TILE_BYTES, B, ldb, N, n0, k_begin + p * GBK, tid);
-        }
     } else {
       if (!prefetched) {
         stage_load<AK>(ra, A, lda, M, k_end, m0, k_begin, tid);
@@ -418,28 +409,12 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(int M, int N, int K,
       stage_store<AK>(ra, smem, tid);
       stage_store<BKC>(rb, smem + TILE_BYTES, tid);
     }
-    if constexpr (NSTG > 2) {  // stage 0 landed (stages 1.. may stay in flight: 8 DMAs per thread each)
-      asm volatile("" ::: "memory");
-      const int ahead = min(NSTG - 2, nk - 1);
-      if (ahead >= 2) __builtin_amdgcn_s_waitcnt(0x4F70);       // vmcnt(16)
-      else if (ahead == 1) __builtin_amdgcn_s_waitcnt(0x0F78);  // vmcnt(8)
-      else __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0)
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    } else {
-      __syncthreads();
-    }
+    __syncthreads();
 
     for (int kt = 0; kt < nk; ++kt) {
-      const int cur = NSTG == 2 ? kt & 1 : kt % NSTG;
+      const int cur = kt & 1;
       const bool more = kt + 1 < nk;
-      if constexpr (NSTG > 2) {
-        if (kt + NSTG - 1 < nk) {
-          char* nb = smem + ((kt + NSTG - 1) % NSTG) * 2 * TILE_BYTES;
-          stage_glds<AK>(nb, A, lda, M, m0, k_begin + (kt + NSTG - 1) * GBK, tid);
-          stage_glds<BKC>(nb + TILE_BYTES, B, ldb, N, n0, k_begin + (kt + NSTG - 1) * GBK, tid);
-        }
-      } else if constexpr (GL) {
+      if constexpr (GL) {
         if (more) {
           char* nb = smem + (cur ^ 1) * 2 * TILE_BYTES;
           stage_glds<AK>(nb, A, lda, M, m0, k_begin + (kt + 1) * GBK, tid);
@@ -504,20 +479,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(int M, int N, int K,
         stage_store<AK>(ra, smem + (cur ^ 1) * 2 * TILE_BYTES, tid);
         stage_store<BKC>(rb, smem + (cur ^ 1) * 2 * TILE_BYTES + TILE_BYTES, tid);
       }
-      if constexpr (NSTG > 2) {
-        // this step's fragment reads done (the next step's DMA refills this
-        // stage), the next step's tiles landed: the stages requested after
-        // it (up to NSTG - 2 of them, 8 DMAs per thread each) may stay in flight
-        asm volatile("" ::: "memory");
-        const int ahead = min(NSTG - 2, nk - kt - 2);
-        if (ahead >= 2) __builtin_amdgcn_s_waitcnt(0x4070);       // vmcnt(16) lgkmcnt(0)
-        else if (ahead == 1) __builtin_amdgcn_s_waitcnt(0x0078);  // vmcnt(8) lgkmcnt(0)
-        else __builtin_amdgcn_s_waitcnt(0x0070);                  // vmcnt(0) lgkmcnt(0)
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      } else {
-        __syncthreads();
-      }
+      __syncthreads();
     }
 
     // prefetch the next item's first K stage: its load latency hides behind
@@ -2190,77 +2152,66 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(int M, int N, int K,
 }
 
 // ---------------------------------------------------------------------------
-// Split-K (deterministic slabs) for a pure Cf (+)= A.B^T epilogue with few
-// output tiles and a long K, i.e. the weight gradients (K = tokens): without
-// it a [512 x 1536] wgrad occupies 48 of 256 CUs.
-// SMER_GEMM_GLDS=0 forces register staging (A/B comparisons, tests).
-static bool smer_gemm_glds_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_GEMM_GLDS");
-    v = (e && e[0] == '0') ? 0 : 1;
+// Dispatch.  gemm_plan (gemm_plan.h) decides kernel, grid, LDS bytes and
+// split-K from a GemmQuery and the GemmSwitches; the launchers below fill the
+// query, ask it and launch.  smer_gemm_plan returns the same plan unlaunched.
+// ---------------------------------------------------------------------------
+static_assert(gp::BM == GBM && gp::BN == GBN && gp::BK == GBK && gp::TILE_BYTES == TILE_BYTES &&
+                  gp::G64_STAGE == G64_STAGE && gp::G2 == G2 && gp::G2K == G2K && gp::G2_STAGE == G2_STAGE &&
+                  gp::G2_LDS == G2_LDS && gp::GS_KS == GS_KS && gp::GS_SLOT == GS_SLOT &&
+                  gp::SK_BM == SK_BM && gp::SK_BN == SK_BN,
+              "gemm_plan.h: tile geometry differs from the kernels'");
+
+// The one reader of the environment for the dispatch: a single pass over
+// the SMER_* entries, taking either the switches that tests and A/B tools
+// flip in-process (per_call) or the read-once ones.
+static GemmSwitches read_switches(GemmSwitches sw, bool per_call) {
+  for (char** p = environ; p && *p; ++p) {
+    const char* s = *p;
+    if (strncmp(s, "SMER_", 5) != 0) continue;
+    const char* v = nullptr;  // the value of the entry whose name `is`
+    auto is = [&](const char* name) {
+      const size_t n = strlen(name);
+      if (strncmp(s, name, n) != 0 || s[n] != '=') return false;
+      v = s + n + 1;
+      return true;
+    };
+    auto on = [&] { return v[0] != '0'; };
+    auto tri = [&](int dflt) { return v[0] == '0' ? 0 : v[0] == '1' ? 1 : dflt; };
+    auto num = [&](int lo, int hi) { return std::max(lo, std::min(hi, atoi(v))); };
+    if (per_call) {
+      if (is("SMER_GEMM256")) sw.gemm256 = on();
+      else if (is("SMER_GEMM256S")) sw.gemm256s = tri(-1);
+      else if (is("SMER_G256_NONPERSIST")) sw.g256_nonpersist = atoi(v);
+      else if (is("SMER_G256_SKEW")) sw.g256_skew = num(0, 64);
+      else if (is("SMER_GEMM64")) sw.gemm64 = on();
+      else if (is("SMER_WGRAD256S")) sw.wgrad256s = on();
+      else if (is("SMER_SPLITK_FUSED")) sw.splitk_fused = v[0] == '1';
+      else if (is("SMER_GEMM_F32_MFMA")) sw.f32_mfma = on();
+    } else {
+      if (is("SMER_GEMM_GLDS")) sw.gemm_glds = on();
+      else if (is("SMER_WGRAD_GLDS")) sw.wgrad_glds = on();
+      else if (is("SMER_SPLITK_DEPTH")) sw.splitk_depth = num(64, INT_MAX);
+      else if (is("SMER_WGRAD256")) sw.wgrad256 = tri(2);
+      else if (is("SMER_WGRAD256_SLOTS")) sw.wgrad256_slots = num(8, INT_MAX);
+      else if (is("SMER_WGRAD256_DEPTH")) sw.wgrad256_depth = num(64, INT_MAX);
+      else if (is("SMER_SKINNY16")) sw.skinny16 = on();
+      else if (is("SMER_SKINNY16_CAP")) sw.skinny16_cap = num(1, INT_MAX);
+      else if (is("SMER_WGRAD_WGP2")) sw.wgrad_wgp2 = num(1, 4);
+      else if (is("SMER_G256_MIN")) sw.g256_min = num(1, INT_MAX);
+      else if (is("SMER_SKINNY_KF")) sw.skinny_kf = on();
+      else if (is("SMER_SKINNY_ROWS_F32")) sw.skinny_rows_f32 = on();
+    }
   }
-  return v == 1;
+  return sw;
 }
-
-// SMER_WGRAD_GLDS=0: register staging for the 128x128 weight gradients
-// (round 5's workaround, see launch_bf16; A/B runs).  Default LDS-DMA since
-// round 6: the non-repeatable overlapped step was the packed-FP32 fault
-// (DESIGN.md section 8), not this kernel, and the library no longer
-// contains packed-FP32 instructions
-static bool smer_wgrad_glds() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_WGRAD_GLDS");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
+// the read-once switches alone, read on the first call (the decode entry
+// points, which take no per-call switch, stop here)
+static const GemmSwitches& gemm_switches_once() {
+  static const GemmSwitches once = read_switches(GemmSwitches{}, false);
+  return once;
 }
-
-// SMER_GEMM256=0 keeps every shape on the 128x128 kernel (A/B, tests).
-static bool smer_gemm256_enabled() {
-  const char* e = getenv("SMER_GEMM256");  // read per call: A/B scripts flip it in-process
-  return !(e && e[0] == '0');
-}
-
-// Whole-tile bf16-output shapes: the staggered kernel where it measured
-// faster than the two-stage one (tools/gemm256s_ab.py, round 4): K >= 1024
-// (C2 FFN2 forward 69.7 vs 73.3 us, FFN1 / QKV dgrads 66.0 / 52.6 vs 71.1 /
-// 56.6, C4 FFN1 dgrad 202 vs 224) and the NN dgrads with N >= 1024 (gated
-// FFN2 dgrad 104.8 vs 116.9); the K = 512 forwards keep the two-stage kernel
-// (FFN1 106.9 vs 101.8, QKV 68.8 vs 68.0: their epilogue, not the k-loop,
-// sets the time).  SMER_GEMM256S=1 / 0 forces it on / off (read per call:
-// A/B in-process).
-static bool smer_gemm256s_enabled(bool bkc, int N, int K) {
-  const char* e = getenv("SMER_GEMM256S");
-  if (e && e[0] == '1') return true;
-  if (e && e[0] == '0') return false;
-  return K >= 1024 || (!bkc && N >= 1024);
-}
-
-// SMER_G256_NONPERSIST (read per call): 1 = the NN dgrad shapes of the
-// 256x256 kernels run one workgroup per tile (grid = tiles) instead of a
-// persistent grid of one per CU, so the hardware dispatcher balances tiles
-// onto the CUs the side-stream weight gradients leave free; 2 = every
-// 256x256 forward / dgrad; 0 = persistent everywhere
-static int smer_g256_nonpersist() {
-  const char* e = getenv("SMER_G256_NONPERSIST");
-  return e ? atoi(e) : 0;
-}
-
-// SMER_G256_SKEW (A/B probe, read per call): start skew of the persistent
-// 256x256 forward / dgrad kernels, in units of ~2k cycles (GemmEpi.skew)
-static int smer_g256_skew() {
-  const char* e = getenv("SMER_G256_SKEW");
-  return e ? std::max(0, std::min(64, atoi(e))) : 0;
-}
-
-// SMER_GEMM64=0 keeps mid-size shapes on the 128x128 kernel (A/B, tests;
-// read per call)
-static bool smer_gemm64_enabled() {
-  const char* e = getenv("SMER_GEMM64");
-  return !(e && e[0] == '0');
-}
+static GemmSwitches gemm_switches() { return read_switches(gemm_switches_once(), true); }
 
 static int smer_num_cus() {
   static int cache[64] = {0};
@@ -2275,401 +2226,113 @@ static int smer_num_cus() {
   return cache[dev];
 }
 
-// minimum K depth of a split-K slice (SMER_SPLITK_DEPTH overrides; A/B runs)
-static int smer_splitk_depth() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_SPLITK_DEPTH");
-    v = e ? std::max(64, atoi(e)) : 1024;
-  }
-  return v;
+// what the dispatch reads of a call's epilogue
+static GemmQuery gemm_query(bool f32, bool ak, bool bk, int M, int N, int K, const GemmEpi& e) {
+  GemmQuery q;
+  q.f32 = f32; q.ak = ak; q.bk = bk; q.M = M; q.N = N; q.K = K;
+  q.C = e.C; q.Cf = e.Cf; q.bias = e.bias; q.relu = e.relu; q.drop = e.drop_thr; q.residual = e.residual;
+  q.gate = e.gate; q.vec = e.vec; q.kv = e.kv; q.q8 = e.q8; q.ldcf = e.ldcf;
+  q.cf_aligned16 = ((uintptr_t)e.Cf & 15) == 0;
+  return q;
 }
 
-// Weight gradients on the 256x256 kernel for outputs of at least 1536 x 768
-// (tools/bench_wgrad.py c4: 3072x768x65536 350 vs 426 us, 768x3072 316 vs
-// 387, 2304x768 271 vs 315; 768x768 equal at K = 65536 and 54 vs 43 us at
-// 16384; C4 step 90.1 vs 91.1 ms with every wgrad on it).  At C2's
-// 512-wide outputs the 128x128 kernel with its smaller split-K slabs is as
-// fast or faster.
-// Round 5 sent every shape whose split-K fills the chip to it (the 128x128
-// kernel then staged through registers: C2 13.66 vs 14.05 ms).  Round 6,
-// with the 128x128 kernel on LDS-DMA again: outputs with both sides >= 768
-// (or >= 1536 x 768) take it -- every C4 weight gradient (C4 fp8 84.5-85.0
-// vs 85.6-86.3 ms with only the round-4 rule), no C2 one (C2 13.08-13.16 vs
-// 13.19-13.22 ms with all of them; tools/ab_step.py, interleaved rounds).
-// SMER_WGRAD256=2 (default) / 1 / 0: that rule / every shape / never (A/B);
-// SMER_WGRAD256_DEPTH: minimum K depth of its split-K slices
-static bool smer_wgrad256_enabled(int M, int N) {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_WGRAD256");
-    v = (e && e[0] == '0') ? 0 : (e && e[0] == '1') ? 1 : 2;
-  }
-  return v == 1 || (v == 2 && ((long)M * N >= 1536L * 768 || (M >= 768 && N >= 768)));
-}
-// The 256x256 weight gradients on the staggered schedule
-// (gemm256s_wgrad_kernel; tools/bench_wgrad.py c4: 2304x768x65536 249 vs
-// 284 us, 3072x768 326 vs 356, 768x3072 302 vs 334, 768x768 equal);
-// SMER_WGRAD256S=0: the two-stage gemm256_wgrad_kernel (read per call)
-static bool smer_wgrad256s_enabled() {
-  const char* e = getenv("SMER_WGRAD256S");
-  return !(e && e[0] == '0');
-}
-// work items of the 256x256 weight-gradient grid (SMER_WGRAD256_SLOTS;
-// default one per CU): fewer split-K slices write fewer fp32 slab bytes and
-// leave CUs to the main stream's kernels (A/B runs)
-// Cap on the persistent weight-gradient grids for the current call
-// (smer_gemm_wgrad_bias_ex max_workgroups; 0 = none): a weight gradient
-// running on a second stream beside the dgrad chain leaves the other CUs to
-// that chain.  Set and cleared around one launch_bf16 call (host thread).
-static thread_local long g_wgrad_cap = 0;
-static long wgrad_cap(long v) { return g_wgrad_cap > 0 ? std::max(8L, std::min(v, g_wgrad_cap)) : v; }
-
-static long smer_wgrad256_slots() {
-  static long v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_WGRAD256_SLOTS");
-    v = e ? std::max(8, atoi(e)) : smer_num_cus();
-  }
-  return wgrad_cap(v);
-}
-static int smer_wgrad256_depth() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_WGRAD256_DEPTH");
-    v = e ? std::max(64, atoi(e)) : 512;
-  }
-  return v;
-}
-
-// 16-row decode Linear workgroups (SMER_SKINNY16=0: 64-row strips; A/B runs)
-static bool smer_skinny16_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_SKINNY16");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
-static long smer_skinny16_cap() {  // workgroups per CU (SMER_SKINNY16_CAP; A/B runs)
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_SKINNY16_CAP");
-    v = e ? std::max(1, atoi(e)) : 2;
-  }
-  return v;
-}
-
-// Resident split-K workgroups per 2 CUs (SMER_WGRAD_WGP2: 4 = two per CU,
-// the default since round 6 -- with the LDS-DMA 128x128 weight gradient back
-// the overlapped C2 step is the same (13.09-13.13 vs 13.08-13.10 ms) and the
-// serialised weight gradients run faster (GEMM family 0.244 vs 0.226 of
-// peak, bench.py's live roofline); 2 = one per CU (round 5: C2 13.49 vs
-// 13.56 ms with register staging); 1 = one per two CUs).  The weight gradients run on a second stream beside
-// the main chain: a smaller persistent grid leaves CUs (and LDS) to the main
-// stream's kernels and cuts the split-K slab bytes in proportion.
-// SMER_WGRAD_STAGES = 2 / 3 / 4: LDS stages of the 128x128 split-K weight
-// gradients at one resident workgroup per CU (A/B runs).  Default 2: the
-// deeper rings hold 96 / 128 KiB of LDS per CU, which the concurrent main-
-// stream kernels then cannot share (C2 step 13.28-13.33 ms at 2 stages,
-// 13.52-13.56 at 3, 13.61-13.62 at 4; two interleaved rounds, one box)
-static int smer_wgrad_stages() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_WGRAD_STAGES");
-    v = e ? std::max(2, std::min(4, atoi(e))) : 2;
-  }
-  return v;
-}
-// SMER_WGRAD_LDS_PAD (bytes, repeatability probes only): extra dynamic LDS
-// requested by the LDS-DMA 128x128 weight gradient, so fewer other
-// workgroups share its CU (160 KiB in all: the CU to itself as far as LDS goes)
-static size_t smer_wgrad_lds_pad() {
-  static long v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_WGRAD_LDS_PAD");
-    v = e ? std::max(0, std::min(96 * 1024, atoi(e))) : 0;
-  }
-  return (size_t)v;
-}
-static long smer_wgrad_resident() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_WGRAD_WGP2");
-    v = e ? std::max(1, std::min(4, atoi(e))) : 4;
-  }
-  return wgrad_cap(std::max(8L, (v * (long)smer_num_cus()) / 2));
-}
-
-// fewest 256x256 tiles for which a forward / dgrad shape takes the 256x256
-// kernel (SMER_G256_MIN, A/B runs; default: one per CU)
-static long smer_g256_min_tiles() {
-  static long v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_G256_MIN");
-    v = e ? std::max(1, atoi(e)) : smer_num_cus();
-  }
-  return v;
-}
-
-// Split-K tickets (fused last-arriver reduction): the LAST SPLITK_TICKET_BYTES
+// Split-K tickets (fused last-arriver reduction): the LAST gp::TICKET_BYTES
 // of a split-K workspace hold one u32 per output tile.  They must be zero
 // when the workspace is first used (callers allocate it zeroed); every
 // launch leaves them zero (the last arriver resets its tile's ticket).
-constexpr size_t SPLITK_TICKET_BYTES = 64 * 1024;
-// SMER_SPLITK_FUSED=1: the fused last-arriver reduction instead of the
-// separate splitk_reduce_kernel (read per call).  Off by default: C2 step
-// 13.64-16.62 ms fused vs 13.04-13.09 separate (three interleaved rounds,
-// tools/ab_step.py, round 6) -- every slice waits for its 64 KiB of
-// write-through slab stores before taking the ticket, and the last arriver
-// sums the tile alone, both stalls of the persistent weight-gradient
-// workgroups; bit-identical either way
-static bool smer_splitk_fused() {
-  const char* e = getenv("SMER_SPLITK_FUSED");
-  return e && e[0] == '1';
-}
-static size_t splitk_slab_bytes(size_t ws_bytes) {
-  return ws_bytes > SPLITK_TICKET_BYTES ? ws_bytes - SPLITK_TICKET_BYTES : 0;
-}
-
-static int choose_split(int M, int N, int K, const GemmEpi& e, size_t ws_bytes) {
-  bool cf_only = e.Cf && !e.C && !e.bias && !e.residual && !e.gate && !e.relu && !e.drop_thr;
-  if (!cf_only) return 1;
-  long tiles = (long)((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
-  if (tiles >= 512 || K < 1024 || ((long)M * N) % 4 != 0) return 1;
-  // ~2 resident workgroups per CU, K slices >= 1024 deep: more slices only
-  // add slab traffic (split * M * N * 8 bytes through HBM)
-  // (floor: a partial second wave of workgroups costs a whole slice time)
-  long s = smer_wgrad_resident() / tiles;
-  s = std::min<long>(s, K / smer_splitk_depth());
-  // slabs of M*N floats plus M floats of row-sum partials per K slice
-  s = std::min<long>(s, (long)(splitk_slab_bytes(ws_bytes) / (((size_t)M * N + M) * sizeof(float))));
-  s = std::max<long>(1, std::min<long>(s, 64));
-  return (int)s;
-}
-
-// SMER_SKINNY_KF=0: the skinny bf16 kernel's guarded-load form at every K (A/B runs)
-static bool smer_skinny_kf() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_SKINNY_KF");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
 template <bool AK, bool BKC>
-static void launch_bf16(int M, int N, int K, const void* A, long lda, const void* B, long ldb,
+static int launch_bf16(int M, int N, int K, const void* A, long lda, const void* B, long ldb,
                         const GemmEpi& e, void* ws, size_t ws_bytes, hipStream_t s,
-                        float* rowsum = nullptr) {
-  if (AK && BKC && M <= 4 * SK_BM && !rowsum) {
-    const int nsteps = (K + 31) / 32;
-    const int ntn = (N + SK_BN - 1) / SK_BN;
-    // 16-row workgroups while that keeps the grid within two per CU
-    // (per-workgroup load time, not the grid, bounds a decode Linear)
-    const bool m16 = smer_skinny16_enabled() && (long)ntn * ((M + 15) / 16) <= smer_skinny16_cap() * smer_num_cus();
-    const bool kf = K % 32 == 0 && smer_skinny_kf();
-#define SKB(U, MI)                                                                                     \
-  do {                                                                                                 \
-    if (kf)                                                                                            \
-      hipLaunchKernelGGL((gemm_skinny_bf16_kernel<8, U, MI, true>), grid, dim3(512), 0, s, M, N, K,    \
-                         (const bf16*)A, lda, (const bf16*)B, ldb, e);                                 \
-    else                                                                                               \
-      hipLaunchKernelGGL((gemm_skinny_bf16_kernel<8, U, MI, false>), grid, dim3(512), 0, s, M, N, K,   \
-                         (const bf16*)A, lda, (const bf16*)B, ldb, e);                                 \
+                        float* rowsum = nullptr, int max_workgroups = 0) {
+  const GemmSwitches sw = gemm_switches();
+  GemmQuery q = gemm_query(false, AK, BKC, M, N, K, e);
+  q.rowsum = rowsum != nullptr;
+  q.ws = ws != nullptr;
+  q.ws_bytes = ws_bytes;
+  q.cus = smer_num_cus();
+  q.max_workgroups = max_workgroups;
+  const GemmPlan p = gemm_plan(q, sw);
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+  const bf16 *a = (const bf16*)A, *b = (const bf16*)B;
+  // split-K: slabs, then the row-sum partials of each slice
+  float* slabs = (float*)ws;
+  float* rs_part = p.rs_offset ? slabs + p.rs_offset : nullptr;
+  float* rs_out = p.split > 1 ? rs_part : rowsum;
+  // > 64 KiB of dynamic LDS must be opted into, once per kernel
+#define LDS_ATTR(kern, bytes)                                                                   \
+  do {                                                                                          \
+    static bool set = false;                                                                    \
+    if (!set) {                                                                                 \
+      hipFuncSetAttribute((const void*)(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); \
+      set = true;                                                                               \
+    }                                                                                           \
   } while (0)
-    if (m16) {
-      const dim3 grid(ntn, (M + 15) / 16);
-      if (nsteps > 16) SKB(4, 1);
-      else SKB(2, 1);
-      return;
-    }
-    const dim3 grid(ntn, (M + SK_BM - 1) / SK_BM);
-    if (nsteps > 16) SKB(4, 4);  // 8 waves x 4 steps (16 waves would spill at 128 VGPRs)
-    else SKB(2, 4);
-#undef SKB
-    return;
-  }
-  // large-M forward / dgrad: 256x256 tiles when they fill the chip
-  if (AK && !rowsum && K % G2K == 0 && smer_gemm256_enabled()) {
-    const long t2 = (long)((M + G2 - 1) / G2) * ((N + G2 - 1) / G2);
-    // whole tiles with a bf16 output: the staggered kernel
-    if (t2 >= smer_g256_min_tiles() && smer_gemm256s_enabled(BKC, N, K) && M % G2 == 0 && N % G2 == 0 &&
-        K % GS_KS == 0 && K / GS_KS >= 4 && e.vec && e.C && !e.Cf && !e.kv && !e.q8 &&
-        !(e.residual && e.gate)) {
-      static bool attr_s = false;
-      if (!attr_s) {
-        hipFuncSetAttribute((const void*)gemm256s_bf16_kernel<true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS);
-        hipFuncSetAttribute((const void*)gemm256s_bf16_kernel<false>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS);
-        attr_s = true;
-      }
-      const int np = smer_g256_nonpersist();
-      const bool whole = np == 2 || (np == 1 && !BKC);
-      const int grid = (t2 > smer_num_cus() && !whole) ? (smer_num_cus() & ~7) : (int)t2;
+#define SKB(MI, KF)                                                                                         \
+  do {                                                                                                      \
+    if (p.unroll4)                                                                                          \
+      hipLaunchKernelGGL((gemm_skinny_bf16_kernel<8, 4, MI, KF>), grid, block, 0, s, M, N, K, a, lda, b, ldb, e); \
+    else                                                                                                    \
+      hipLaunchKernelGGL((gemm_skinny_bf16_kernel<8, 2, MI, KF>), grid, block, 0, s, M, N, K, a, lda, b, ldb, e); \
+  } while (0)
+  switch (p.kernel) {
+    case GK_SKINNY_M16_KF: SKB(1, true); break;
+    case GK_SKINNY_M16_GUARD: SKB(1, false); break;
+    case GK_SKINNY_S64_KF: SKB(4, true); break;
+    case GK_SKINNY_S64_GUARD: SKB(4, false); break;
+    case GK_G256S: {
+      LDS_ATTR(gemm256s_bf16_kernel<BKC>, G2_LDS);
       GemmEpi ed = e;
-      ed.dbg = gemm_dbg_for(grid, s);
-      ed.skew = smer_g256_skew();
-      hipLaunchKernelGGL(gemm256s_bf16_kernel<BKC>, dim3(grid), dim3(512), G2_LDS, s,
-                         M, N, K, (const bf16*)A, lda, (const bf16*)B, ldb, ed);
-      return;
+      ed.dbg = gemm_dbg_for(p.grid_x, s);
+      ed.skew = sw.g256_skew;
+      hipLaunchKernelGGL(gemm256s_bf16_kernel<BKC>, grid, block, p.lds, s, M, N, K, a, lda, b, ldb, ed);
+      break;
     }
-    if (t2 >= smer_g256_min_tiles()) {
-      const int np = smer_g256_nonpersist();
-      const bool whole = np == 2 || (np == 1 && !BKC);
-      const int grid = (t2 > smer_num_cus() && !whole) ? (smer_num_cus() & ~7) : (int)t2;
-      static bool attr_set = false;  // > 64 KiB dynamic LDS must be opted into
-      if (!attr_set) {
-        hipFuncSetAttribute((const void*)gemm256_bf16_kernel<AK, BKC, false>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS);
-        hipFuncSetAttribute((const void*)gemm256_bf16_kernel<AK, BKC, true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS);
-        attr_set = true;
-      }
-      // streamed-epilogue variant: whole tiles, bf16 C only, at most one of
-      // residual / gate
-      const bool fast = e.vec && e.C && !e.Cf && !e.kv && M % G2 == 0 && N % G2 == 0 &&
-                        !(e.residual && e.gate);
-      auto kern = fast ? gemm256_bf16_kernel<AK, BKC, true> : gemm256_bf16_kernel<AK, BKC, false>;
+    case GK_G256_STREAM:
+    case GK_G256_GENERIC: {
+      // streamed-epilogue variant: whole tiles, bf16 C only, at most one of residual / gate
+      auto kern = p.kernel == GK_G256_STREAM ? gemm256_bf16_kernel<AK, BKC, true> : gemm256_bf16_kernel<AK, BKC, false>;
+      LDS_ATTR((gemm256_bf16_kernel<AK, BKC, true>), G2_LDS);
+      LDS_ATTR((gemm256_bf16_kernel<AK, BKC, false>), G2_LDS);
       GemmEpi ek = e;
-      ek.skew = smer_g256_skew();
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(512), G2_LDS, s,
-                         M, N, K, (const bf16*)A, lda, (const bf16*)B, ldb, ek);
-      return;
+      ek.skew = sw.g256_skew;
+      hipLaunchKernelGGL(kern, grid, block, p.lds, s, M, N, K, a, lda, b, ldb, ek);
+      break;
     }
-  }
-  // weight gradients (both operands column images, pure fp32 output): the
-  // 256x256 tile when its split-K fills the chip with >= 512-deep slices
-  if (!AK && !BKC && K % G2K == 0 && ws && smer_wgrad256_enabled(M, N)) {
-    const bool cf_only = e.Cf && !e.C && !e.bias && !e.residual && !e.gate && !e.relu && !e.drop_thr &&
-                         ((long)M * N) % 4 == 0;
-    const long t2 = (long)((M + G2 - 1) / G2) * ((N + G2 - 1) / G2);
-    const long cus = smer_num_cus();
-    long ns = std::min<long>(smer_wgrad256_slots() / std::max<long>(1, t2), K / smer_wgrad256_depth());
-    ns = std::min<long>(ns, (long)(splitk_slab_bytes(ws_bytes) / (((size_t)M * N + M) * sizeof(float))));
-    ns = std::max<long>(1, std::min<long>(ns, 64));
-    if (cf_only && t2 * ns * 4 >= 3 * cus) {
-      int kchunk = (int)(((K + ns - 1) / ns + G2K - 1) / G2K * G2K);
-      const int split = (K + kchunk - 1) / kchunk;
-      static bool attr_set = false;
-      if (!attr_set) {
-        hipFuncSetAttribute((const void*)gemm256_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            2 * G2_STAGE);
-        attr_set = true;
-      }
-      float* rs_part = (split > 1 && rowsum) ? (float*)ws + (size_t)split * M * N : nullptr;
-      const long nwg = t2 * split;
-      const long gcap = wgrad_cap(cus);
-      const int grid = nwg > gcap ? (int)(gcap & ~7L) : (int)nwg;
-      if (smer_wgrad256s_enabled() && M % G2 == 0 && N % G2 == 0 && e.vec) {
-        static bool attr_s = false;
-        if (!attr_s) {
-          hipFuncSetAttribute((const void*)gemm256s_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              4 * GS_SLOT);
-          attr_s = true;
-        }
-        hipLaunchKernelGGL(gemm256s_wgrad_kernel, dim3(grid), dim3(512), 4 * GS_SLOT, s, M, N, K,
-                           (const bf16*)A, lda, (const bf16*)B, ldb, e, split, kchunk, (float*)ws,
-                           split > 1 ? rs_part : rowsum);
-      } else
-      hipLaunchKernelGGL(gemm256_wgrad_kernel, dim3(grid), dim3(512), 2 * G2_STAGE, s, M, N, K,
-                         (const bf16*)A, lda, (const bf16*)B, ldb, e, split, kchunk, (float*)ws,
-                         split > 1 ? rs_part : rowsum);
-      if (split > 1) {
-        long n4 = ((long)M * N) / 4 + (rowsum ? M : 0);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, M, N, split,
-                           (const float*)ws, e.alpha, e.Cf, e.ldcf, e.accumulate,
-                           (const float*)rs_part, rowsum, e.rs_accumulate);
-      }
-      return;
+    case GK_WGRAD256S:
+      LDS_ATTR(gemm256s_wgrad_kernel, 4 * GS_SLOT);
+      hipLaunchKernelGGL(gemm256s_wgrad_kernel, grid, block, p.lds, s, M, N, K, a, lda, b, ldb, e, p.split,
+                         p.kchunk, slabs, rs_out);
+      break;
+    case GK_WGRAD256:
+      LDS_ATTR(gemm256_wgrad_kernel, 2 * G2_STAGE);
+      hipLaunchKernelGGL(gemm256_wgrad_kernel, grid, block, p.lds, s, M, N, K, a, lda, b, ldb, e, p.split,
+                         p.kchunk, slabs, rs_out);
+      break;
+    case GK_GEMM64:
+      hipLaunchKernelGGL((gemm64_bf16_kernel<BKC>), grid, block, p.lds, s, M, N, K, a, lda, b, ldb, e);
+      break;
+    case GK_G128_GLDS:
+    case GK_G128_REG: {
+      // LDS-DMA staging, or through registers (a K or slice depth that is no multiple of 64)
+      auto kern = p.kernel == GK_G128_GLDS ? gemm_bf16_kernel<AK, BKC, true> : gemm_bf16_kernel<AK, BKC, false>;
+      unsigned* tickets =
+          p.reduce == GK_SPLITK_FUSED ? (unsigned*)((char*)ws + ws_bytes - gp::TICKET_BYTES) : nullptr;
+      hipLaunchKernelGGL(kern, grid, block, p.lds, s, M, N, K, a, lda, b, ldb, e, p.split, p.kchunk, slabs,
+                         rs_out, tickets, rowsum);
+      break;
     }
+    default:
+      return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_gemm(bf16): the plan names no bf16 kernel");
   }
-  int tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
-  int split = choose_split(M, N, K, e, ws ? ws_bytes : 0);
-  // mid-size forward / dgrad: fewer 128x128 tiles than two per CU -> 64x128
-  if (AK && !rowsum && split == 1 && K % GBK == 0 && tiles <= 4 * smer_num_cus() &&
-      M > 4 * SK_BM && smer_gemm_glds_enabled() && smer_gemm64_enabled()) {
-    const long t64 = (long)((M + 63) / 64) * ((N + GBN - 1) / GBN);
-    const long res = 3L * smer_num_cus();
-    const int grid = t64 > res ? (int)(res & ~7L) : (int)t64;
-    hipLaunchKernelGGL((gemm64_bf16_kernel<BKC>), dim3(grid), dim3(256), 2 * G64_STAGE, s, M, N, K,
-                       (const bf16*)A, lda, (const bf16*)B, ldb, e);
-    return;
-  }
-  int kchunk = K;
-  if (split > 1) {
-    kchunk = ((K + split - 1) / split + GBK - 1) / GBK * GBK;
-    split = (K + kchunk - 1) / kchunk;
-  }
-  float* rs_part = (split > 1 && rowsum) ? (float*)ws + (size_t)split * M * N : nullptr;
-  // fused split-K reduction by the tile's last-arriving slice (no separate
-  // reduce launch): whole float4 rows of dW
-  unsigned* tickets = nullptr;
-  if (split > 1 && smer_splitk_fused() && (N & 3) == 0 && (e.ldcf & 3) == 0 &&
-      ((uintptr_t)e.Cf & 15) == 0 && (size_t)tiles * 4 <= SPLITK_TICKET_BYTES &&
-      ws_bytes >= SPLITK_TICKET_BYTES)
-    tickets = (unsigned*)((char*)ws + ws_bytes - SPLITK_TICKET_BYTES);
-  // persistent grid: two resident workgroups per CU (LDS 64 KiB, <= 256 VGPRs);
-  // split-K weight gradients: smer_wgrad_resident()
-  const long nwg = (long)tiles * split;
-  const long resident = split > 1 ? smer_wgrad_resident() : 2L * smer_num_cus();
-  const int grid = nwg > resident ? (int)(resident & ~7L) : (int)nwg;
-  // LDS-DMA staging needs whole 64-deep K steps in every slice.  (Round 5
-  // staged the weight gradients through registers because with LDS-DMA the
-  // overlapped step was not repeatable; round 6 traced that to packed-FP32
-  // VALU results corrupted beside LDS-DMA on the same CU, DESIGN.md section
-  // 8, and builds the library without them: SMER_WGRAD_GLDS=0 keeps the
-  // register form for A/B runs)
-  const bool gl = (K % GBK) == 0 && (kchunk % GBK) == 0 && smer_gemm_glds_enabled() &&
-                  ((AK || BKC) || smer_wgrad_glds());
-  if constexpr (!AK && !BKC) {
-    // weight gradients at one resident workgroup per CU: the 3-stage ring
-    const int ns = smer_wgrad_stages();
-    if (gl && split > 1 && smer_wgrad_resident() <= smer_num_cus() && ns > 2) {
-      static bool attr = false;
-      if (!attr) {
-        hipFuncSetAttribute((const void*)gemm_bf16_kernel<false, false, true, 3>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 6 * TILE_BYTES);
-        hipFuncSetAttribute((const void*)gemm_bf16_kernel<false, false, true, 4>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 8 * TILE_BYTES);
-        attr = true;
-      }
-      if (ns == 4)
-        hipLaunchKernelGGL((gemm_bf16_kernel<false, false, true, 4>), dim3(grid), dim3(256), 8 * TILE_BYTES, s,
-                           M, N, K, (const bf16*)A, lda, (const bf16*)B, ldb, e, split, kchunk, (float*)ws,
-                           rs_part, tickets, rowsum);
-      else
-        hipLaunchKernelGGL((gemm_bf16_kernel<false, false, true, 3>), dim3(grid), dim3(256), 6 * TILE_BYTES, s,
-                           M, N, K, (const bf16*)A, lda, (const bf16*)B, ldb, e, split, kchunk, (float*)ws,
-                           rs_part, tickets, rowsum);
-      goto reduce;
-    }
-  }
-  {
-    auto kern = gl ? gemm_bf16_kernel<AK, BKC, true> : gemm_bf16_kernel<AK, BKC, false>;
-    size_t lds = 4 * TILE_BYTES;
-    if (!AK && !BKC && gl && smer_wgrad_lds_pad()) {
-      lds += smer_wgrad_lds_pad();
-      static bool attr_pad = false;
-      if (!attr_pad) {
-        hipFuncSetAttribute((const void*)gemm_bf16_kernel<false, false, true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_pad = true;
-      }
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds,
-                       s, M, N, K, (const bf16*)A, lda, (const bf16*)B, ldb, e, split, kchunk,
-                       (float*)ws, split > 1 ? rs_part : rowsum, tickets, rowsum);
-  }
-reduce:
-  if (split > 1 && !tickets) {
+#undef SKB
+#undef LDS_ATTR
+  if (p.reduce == GK_SPLITK_REDUCE) {
     long n4 = ((long)M * N) / 4 + (rowsum ? M : 0);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, M, N, split,
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, M, N, p.split,
                        (const float*)ws, e.alpha, e.Cf, e.ldcf, e.accumulate,
                        (const float*)rs_part, rowsum, e.rs_accumulate);
   }
+  return SMER_OK;
 }
 // Skinny f32 NT GEMM (parity-mode decode steps: M = 2 rows per request).
 // Latency-bound: at M = 2 the step streams the fp32 weights (14.7 MB per C2
@@ -2850,49 +2513,37 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(int M, int N, int K,
         epi_apply<float>(e, M, N, m0 + 16 * i + 4 * g + r, n0 + 16 * j + c16, acc[i][j][r]);
 }
 
-// SMER_GEMM_F32_MFMA=0 keeps fp32 NT shapes on the VALU tile kernel (A/B, tests)
-static bool smer_gemm_f32_mfma() {
-  const char* e = getenv("SMER_GEMM_F32_MFMA");
-  return !(e && e[0] == '0');
-}
+static_assert(gp::SKF_BN == SKF_BN && gp::SKF_BM == SKF_BM && gp::SKF_NW == SKF_NW && gp::SKF_UNR == SKF_UNR,
+              "gemm_plan.h: skinny fp32 geometry differs from the kernels'");
 
-static void launch_skinny_rows_f32(int M, int N, int K, const float* A, long lda, const float* W, long ldw,
-                                   const GemmEpi& e, hipStream_t s);
-// SMER_SKINNY_ROWS_F32=0: fp32 Linears of <= 64 rows on gemm_skinny_f32_kernel (A/B runs)
-static bool smer_skinny_rows_f32() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SMER_SKINNY_ROWS_F32");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-template <bool AK, bool BKC>
-static void launch_f32(int M, int N, int K, const void* A, long lda, const void* B, long ldb,
-                       const GemmEpi& e, hipStream_t s) {
-  if (AK && BKC && M <= 64 && K % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 &&
-      (((uintptr_t)A | (uintptr_t)B) & 15) == 0) {
-    if (K <= SKF_NW * SKF_UNR * 64 && smer_skinny_rows_f32()) {
-      launch_skinny_rows_f32(M, N, K, (const float*)A, lda, (const float*)B, ldb, e, s);
-      return;
-    }
-    const dim3 grid((N + SKF_BN - 1) / SKF_BN, (M + SKF_BM - 1) / SKF_BM);
-    hipLaunchKernelGGL(gemm_skinny_f32_kernel, grid, dim3(64 * SKF_NW), 0, s, M, N, K, (const float*)A,
-                       lda, (const float*)B, ldb, e);
-    return;
-  }
-  dim3 grid((N + 63) / 64, (M + 63) / 64);
-  if (AK && BKC && K % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 &&
-      (((uintptr_t)A | (uintptr_t)B) & 15) == 0 && smer_gemm_f32_mfma()) {
-    hipLaunchKernelGGL(gemm_f32_mfma_kernel<2>, grid, dim3(256), 0, s, M, N, K, (const float*)A, lda,
-                       (const float*)B, ldb, e);
-    return;
-  }
-  hipLaunchKernelGGL((gemm_f32_kernel<AK, BKC>), grid, dim3(256), 0, s, M, N, K,
-                     (const float*)A, lda, (const float*)B, ldb, e);
-}
-
+static void launch_skinny_rows_f32(dim3 grid, size_t lds, int M, int N, int K, const float* A, long lda,
+                                   const float* W, long ldw, const GemmEpi& e, hipStream_t s);
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+template <bool AK, bool BKC>
+static int launch_f32(int M, int N, int K, const void* A, long lda, const void* B, long ldb,
+                       const GemmEpi& e, hipStream_t s) {
+  GemmQuery q = gemm_query(true, AK, BKC, M, N, K, e);
+  q.f32_aligned = lda % 4 == 0 && ldb % 4 == 0 && aligned16(A) && aligned16(B);
+  const GemmPlan p = gemm_plan(q, gemm_switches());
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+  const float *a = (const float*)A, *b = (const float*)B;
+  switch (p.kernel) {
+    case GK_F32_ROWS: launch_skinny_rows_f32(grid, p.lds, M, N, K, a, lda, b, ldb, e, s); break;
+    case GK_F32_SKINNY:
+      hipLaunchKernelGGL(gemm_skinny_f32_kernel, grid, block, 0, s, M, N, K, a, lda, b, ldb, e);
+      break;
+    case GK_F32_MFMA:
+      hipLaunchKernelGGL(gemm_f32_mfma_kernel<2>, grid, block, 0, s, M, N, K, a, lda, b, ldb, e);
+      break;
+    case GK_F32_TILE:
+      hipLaunchKernelGGL((gemm_f32_kernel<AK, BKC>), grid, block, 0, s, M, N, K, a, lda, b, ldb, e);
+      break;
+    default:
+      return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_gemm(f32): the plan names no fp32 kernel");
+  }
+  return SMER_OK;
+}
 
 extern "C" int smer_gemm(int dtype, int a_kcontig, int b_kcontig, int M, int N, int K,
                          const void* A, long lda, const void* B, long ldb, const float* bias,
@@ -2925,15 +2576,13 @@ extern "C" int smer_gemm(int dtype, int a_kcontig, int b_kcontig, int M, int N, 
                  "smer_gemm(bf16): column-image B needs ldb >= round_up(N, 8)");
     SMER_REQUIRE(!workspace || aligned16(workspace), "smer_gemm: workspace alignment");
     if (K == 0) return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_gemm: K == 0");
-    if (a_kcontig && b_kcontig) launch_bf16<true, true>(M, N, K, A, lda, B, ldb, e, workspace, ws_bytes, s);
-    else if (a_kcontig) launch_bf16<true, false>(M, N, K, A, lda, B, ldb, e, workspace, ws_bytes, s);
-    else if (b_kcontig) launch_bf16<false, true>(M, N, K, A, lda, B, ldb, e, workspace, ws_bytes, s);
-    else launch_bf16<false, false>(M, N, K, A, lda, B, ldb, e, workspace, ws_bytes, s);
+    auto launch = a_kcontig ? (b_kcontig ? launch_bf16<true, true> : launch_bf16<true, false>)
+                            : (b_kcontig ? launch_bf16<false, true> : launch_bf16<false, false>);
+    if (int rc = launch(M, N, K, A, lda, B, ldb, e, workspace, ws_bytes, s, nullptr, 0)) return rc;
   } else if (dtype == SMER_F32) {
-    if (a_kcontig && b_kcontig) launch_f32<true, true>(M, N, K, A, lda, B, ldb, e, s);
-    else if (a_kcontig) launch_f32<true, false>(M, N, K, A, lda, B, ldb, e, s);
-    else if (b_kcontig) launch_f32<false, true>(M, N, K, A, lda, B, ldb, e, s);
-    else launch_f32<false, false>(M, N, K, A, lda, B, ldb, e, s);
+    auto launch = a_kcontig ? (b_kcontig ? launch_f32<true, true> : launch_f32<true, false>)
+                            : (b_kcontig ? launch_f32<false, true> : launch_f32<false, false>);
+    if (int rc = launch(M, N, K, A, lda, B, ldb, e, s)) return rc;
   } else {
     return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_gemm: dtype");
   }
@@ -2966,10 +2615,33 @@ extern "C" int smer_gemm_wgrad_bias_ex(int dtype, int M, int N, int K, const voi
   e.Cf = dW; e.ldcf = lddw; e.accumulate = accumulate; e.rs_accumulate = db_accumulate;
   auto a16 = [](const void* p, long ld) { return p == nullptr || ((((uintptr_t)p) & 15) == 0 && ld % 8 == 0); };
   e.vec = a16(dW, lddw);
-  g_wgrad_cap = max_workgroups > 0 ? max_workgroups : 0;
-  launch_bf16<false, false>(M, N, K, dy, lddy, x, ldx, e, workspace, ws_bytes, (hipStream_t)stream, db);
-  g_wgrad_cap = 0;
+  if (int rc = launch_bf16<false, false>(M, N, K, dy, lddy, x, ldx, e, workspace, ws_bytes, (hipStream_t)stream,
+                                         db, max_workgroups))
+    return rc;
   SMER_CHECK_LAUNCH("smer_gemm_wgrad_bias");
+  return SMER_OK;
+}
+
+extern "C" const char* smer_gemm_kernel_name(int kernel) { return gemm_kernel_name(kernel); }
+
+extern "C" int smer_gemm_plan(int dtype, int a_kcontig, int b_kcontig, int M, int N, int K, unsigned facts,
+                              long ldcf, size_t ws_bytes, int max_workgroups, int cus, int* plan) {
+  SMER_REQUIRE(dtype == SMER_BF16 || dtype == SMER_F32, "smer_gemm_plan: dtype");
+  SMER_REQUIRE(M > 0 && N > 0 && K > 0 && cus >= 0 && plan, "smer_gemm_plan: sizes / null plan");
+  auto has = [&](unsigned f) { return (facts & f) != 0; };
+  GemmQuery q;
+  q.f32 = dtype == SMER_F32; q.ak = a_kcontig; q.bk = b_kcontig; q.M = M; q.N = N; q.K = K;
+  q.C = has(SMER_PLAN_C); q.Cf = has(SMER_PLAN_CF); q.bias = has(SMER_PLAN_BIAS); q.relu = has(SMER_PLAN_RELU);
+  q.drop = has(SMER_PLAN_DROP); q.residual = has(SMER_PLAN_RESIDUAL); q.gate = has(SMER_PLAN_GATE);
+  q.vec = has(SMER_PLAN_VEC); q.kv = has(SMER_PLAN_KV); q.q8 = has(SMER_PLAN_Q8);
+  q.cf_aligned16 = has(SMER_PLAN_CF_ALIGNED16); q.rowsum = has(SMER_PLAN_ROWSUM);
+  q.ws = has(SMER_PLAN_WORKSPACE); q.f32_aligned = has(SMER_PLAN_F32_ALIGNED);
+  q.ldcf = ldcf; q.ws_bytes = ws_bytes; q.max_workgroups = max_workgroups;
+  q.cus = cus > 0 ? cus : smer_num_cus();
+  const GemmPlan p = gemm_plan(q, gemm_switches());
+  const int out[SMER_GEMM_PLAN_INTS] = {p.kernel, p.ak | p.bk << 1 | p.unroll4 << 2, p.grid_x, p.grid_y,
+                                        (int)p.lds, p.split, p.kchunk, p.reduce};
+  std::copy(out, out + SMER_GEMM_PLAN_INTS, plan);
   return SMER_OK;
 }
 
@@ -3169,7 +2841,7 @@ extern "C" int smer_linear_decode_ln(int M, int N, int K, const void* Y, long ld
 #define SKLN(U, NC, KF)                                                                                  \
   hipLaunchKernelGGL((gemm_skinny_ln_kernel<8, U, NC, KF>), grid, dim3(512), lds, s, M, N, K, (const bf16*)Y, \
                      ldy, gamma, beta, eps, (bf16*)X, ldx, (const bf16*)W, ldw, e)
-  if (K % 32 == 0 && smer_skinny_kf()) {
+  if (K % 32 == 0 && gemm_switches_once().skinny_kf) {
     if (K <= 512) SKLN(2, 1, true);
     else if (K <= 1024) SKLN(4, 2, true);
     else SKLN(4, 4, true);
@@ -3202,7 +2874,7 @@ extern "C" int smer_linear_decode(int M, int N, int K, const void* A, long lda, 
   e.kv_req = kv_req; e.kv_pos = kv_pos; e.kv_col0 = kv_col0;
   auto a16 = [](const void* p, long ld) { return p == nullptr || ((((uintptr_t)p) & 15) == 0 && ld % 8 == 0); };
   e.vec = a16(bias, 8) && a16(residual, ldr) && a16(C, ldc) && a16(Cf, ldcf);
-  launch_bf16<true, true>(M, N, K, A, lda, W, ldw, e, nullptr, 0, (hipStream_t)stream);
+  if (int rc = launch_bf16<true, true>(M, N, K, A, lda, W, ldw, e, nullptr, 0, (hipStream_t)stream)) return rc;
   SMER_CHECK_LAUNCH("smer_linear_decode");
   return SMER_OK;
 }
@@ -3364,11 +3036,9 @@ static void skinny_f32_lds_attr() {
 }
 // fp32 Linear of <= 64 rows, K <= 2048 (K % 4 == 0, 16-B aligned rows):
 // rows through LDS, all weight loads of the single round issued first
-static void launch_skinny_rows_f32(int M, int N, int K, const float* A, long lda, const float* W, long ldw,
-                                   const GemmEpi& e, hipStream_t s) {
+static void launch_skinny_rows_f32(dim3 grid, size_t lds, int M, int N, int K, const float* A, long lda,
+                                   const float* W, long ldw, const GemmEpi& e, hipStream_t s) {
   skinny_f32_lds_attr();
-  const dim3 grid((N + SKF_BN - 1) / SKF_BN, (M + SKF_BM - 1) / SKF_BM);
-  const size_t lds = (size_t)std::min(M, SKF_BM) * K * sizeof(float);
   hipLaunchKernelGGL(gemm_skinny_ln_f32_kernel<false>, grid, dim3(64 * SKF_NW), lds, s, M, N, K, A, lda,
                      (const float*)nullptr, (const float*)nullptr, 0.f, (float*)nullptr, 0L, W, ldw, e);
 }
@@ -3485,10 +3155,11 @@ extern "C" int smer_linear_decode_f32(int M, int N, int K, const void* A, long l
   SMER_REQUIRE(!kv || (kv_req && kv_pos && kv_col0 >= 0 && kv_col0 < N), "smer_linear_decode_f32: kv scatter arguments");
   const GemmEpi e = decode_epi(bias, relu, residual, ldr, C, ldc, Cf, ldcf, kv, kv_row_stride, kv_req_stride,
                                kv_req, kv_pos, kv_col0);
-  if (K <= SKF_NW * SKF_UNR * 64 && smer_skinny_rows_f32()) {
-    launch_skinny_rows_f32(M, N, K, (const float*)A, lda, (const float*)W, ldw, e, (hipStream_t)stream);
+  const dim3 grid((N + SKF_BN - 1) / SKF_BN, (M + SKF_BM - 1) / SKF_BM);
+  if (K <= SKF_NW * SKF_UNR * 64 && gemm_switches_once().skinny_rows_f32) {
+    launch_skinny_rows_f32(grid, (size_t)std::min(M, SKF_BM) * K * sizeof(float), M, N, K, (const float*)A, lda,
+                           (const float*)W, ldw, e, (hipStream_t)stream);
   } else {
-    const dim3 grid((N + SKF_BN - 1) / SKF_BN, (M + SKF_BM - 1) / SKF_BM);
     hipLaunchKernelGGL(gemm_skinny_f32_kernel, grid, dim3(64 * SKF_NW), 0, (hipStream_t)stream, M, N, K,
                        (const float*)A, lda, (const float*)W, ldw, e);
   }
@@ -4538,21 +4209,20 @@ extern "C" int smer_gemm_wgrad_fp8(int M, int N, int K, const void* dy8, long ld
   GemmEpi e{};
   e.alpha = 1.f; e.drop_scale = 1.f;
   e.Cf = dW; e.ldcf = lddw; e.accumulate = accumulate; e.vec = 1; e.rs_accumulate = db_accumulate;
-  g_wgrad_cap = max_workgroups > 0 ? max_workgroups : 0;
+  const GemmSwitches& sw = gemm_switches_once();
   const long t2 = (long)(M / G2) * (N / G2);
   const int nbn = N / G2;
   const long cus = smer_num_cus();
-  long ns = std::min<long>(smer_wgrad256_slots() / t2, K / smer_wgrad256_depth());
+  const size_t slab_bytes = workspace && ws_bytes > gp::TICKET_BYTES ? ws_bytes - gp::TICKET_BYTES : 0;
+  long ns = std::min<long>(gp::cap(max_workgroups, sw.wgrad256_slots ? sw.wgrad256_slots : cus) / t2, K / sw.wgrad256_depth);
   // per slice: an M x N slab and nbn x M bias partials
-  ns = std::min<long>(ns, (long)(splitk_slab_bytes(workspace ? ws_bytes : 0) /
-                                 (((size_t)M * N + (size_t)nbn * M) * sizeof(float))));
+  ns = std::min<long>(ns, (long)(slab_bytes / (((size_t)M * N + (size_t)nbn * M) * sizeof(float))));
   ns = std::max<long>(1, std::min<long>(ns, 64));
   const int KS = 2 * GS_KS;
   const int kchunk = (int)(((K + ns - 1) / ns + KS - 1) / KS * KS);
   const int split = (K + kchunk - 1) / kchunk;
   const long nwg = t2 * split;
-  const long gcap = wgrad_cap(cus);
-  g_wgrad_cap = 0;
+  const long gcap = gp::cap(max_workgroups, cus);
   const int grid = nwg > gcap ? (int)(gcap & ~7L) : (int)nwg;
   static bool attr = false;
   if (!attr) {
@@ -4563,7 +4233,7 @@ extern "C" int smer_gemm_wgrad_fp8(int M, int N, int K, const void* dy8, long ld
   // split-K: alpha-scaled slabs, then the bias partials
   const size_t slab_floats = split > 1 ? (size_t)split * M * N : 0;
   float* rs_part = db ? (float*)workspace + slab_floats : nullptr;
-  if (db && (slab_floats + (size_t)split * nbn * M) * sizeof(float) > splitk_slab_bytes(ws_bytes))
+  if (db && (slab_floats + (size_t)split * nbn * M) * sizeof(float) > slab_bytes)  // db: workspace non-null
     return smer_set_error(SMER_ERR_INVALID, "smer_gemm_wgrad_fp8: workspace too small for the bias partials");
   hipLaunchKernelGGL(gemm256s_wgrad_fp8_kernel, dim3(grid), dim3(512), 4 * GS_SLOT, s, M, N, K,
                      (const uint8_t*)dy8, lddy, (const uint8_t*)x8, ldx, dy_inv, x_inv, e, split, kchunk,

@@ -338,23 +338,31 @@ def _cdiv(a, b):
 
 
 def expected_kernel(dtype, ak, bk, M, N, K, epi, env, cus):
-    """Pure-Python mirror of launch_bf16 / launch_f32 (csrc/gemm.hip) with
-    every cached switch at its default: the kernel a call runs on, as one of
-    KERNEL_NAMES; a split-K launch is "<kernel>+splitk_reduce" or
-    "<kernel>+splitk_fused"."""
+    """The kernel name of expected_plan."""
+    return expected_plan(dtype, ak, bk, M, N, K, epi, env, cus).name
+
+
+def expected_plan(dtype, ak, bk, M, N, K, epi, env, cus):
+    """Pure-Python mirror of the GEMM dispatch (csrc/gemm_plan.h gemm_plan,
+    an independent statement held against the library's smer_gemm_plan by
+    the tests) with every cached switch at its default: `name`, the kernel a
+    call runs on, as one of KERNEL_NAMES, a split-K launch being
+    "<kernel>+splitk_reduce" or "<kernel>+splitk_fused"; `split` and `kchunk`
+    of the weight-gradient paths (None where the mirror computes none)."""
+    P = lambda name, split=None, kchunk=None: SimpleNamespace(name=name, split=split, kchunk=kchunk)  # noqa: E731
     env = env or {}
     on = lambda k: env.get(k, "")[:1] != "0"  # noqa: E731
     if dtype == F32:
         al = K % 4 == 0 and (epi.lda or 0) % 4 == 0 and not epi.a_off
         if ak and bk and M <= 64 and al:
-            return "f32_rows" if K <= 2048 else "f32_skinny"
+            return P("f32_rows" if K <= 2048 else "f32_skinny")
         if ak and bk and al and on("SMER_GEMM_F32_MFMA"):
-            return "f32_mfma"
-        return "f32_tile"
+            return P("f32_mfma")
+        return P("f32_tile")
     rowsum = epi.rowsum
     if ak and bk and M <= 256 and not rowsum:
         m16 = _cdiv(N, 16) * _cdiv(M, 16) <= 2 * cus
-        return "skinny_%s_%s" % ("m16" if m16 else "s64", "kf" if K % 32 == 0 else "guard")
+        return P("skinny_%s_%s" % ("m16" if m16 else "s64", "kf" if K % 32 == 0 else "guard"))
     # smer_gemm_wgrad_bias_ex max_workgroups (wgrad_cap), the pure Cf (+)= A B^T epilogue, slabs that fit
     cap = (lambda v: max(8, min(v, epi.max_wg))) if epi.max_wg > 0 else (lambda v: v)
     cf_only = epi.Cf and not (epi.C or epi.bias or epi.residual or epi.gate or epi.relu or epi.drop)
@@ -366,8 +374,8 @@ def expected_kernel(dtype, ak, bk, M, N, K, epi, env, cus):
         stag = s == "1" or (s != "0" and (K >= 1024 or (not bk and N >= 1024)))
         ok = epi.vec and epi.C and not epi.Cf and whole and not (epi.residual and epi.gate)
         if stag and ok and K % 32 == 0 and K // 32 >= 4:
-            return "g256s"
-        return "g256_stream" if ok else "g256_generic"
+            return P("g256s")
+        return P("g256_stream" if ok else "g256_generic")
     if not ak and not bk and K % 64 == 0 and epi.ws and (M * N >= 1536 * 768 or (M >= 768 and N >= 768)):
         ns = min(cap(cus) // max(1, t2), K // 512, fit)
         ns = max(1, min(ns, 64))
@@ -375,13 +383,13 @@ def expected_kernel(dtype, ak, bk, M, N, K, epi, env, cus):
             kchunk = _cdiv(_cdiv(K, ns), 64) * 64
             split = _cdiv(K, kchunk)
             name = "wgrad256s" if on("SMER_WGRAD256S") and whole and epi.vec else "wgrad256"
-            return name + ("+splitk_reduce" if split > 1 else "")
+            return P(name + ("+splitk_reduce" if split > 1 else ""), split, kchunk)
     tiles = _cdiv(M, 128) * _cdiv(N, 128)
     split = 1
     if cf_only and epi.ws and not (tiles >= 512 or K < 1024 or (M * N) % 4 != 0):
         split = max(1, min(cap(max(8, 2 * cus)) // tiles, K // 1024, fit, 64))
     if ak and not rowsum and split == 1 and K % 64 == 0 and tiles <= 4 * cus and M > 256 and on("SMER_GEMM64"):
-        return "gemm64"
+        return P("gemm64")
     kchunk = K
     if split > 1:
         kchunk = _cdiv(_cdiv(K, split), 64) * 64
@@ -391,14 +399,67 @@ def expected_kernel(dtype, ak, bk, M, N, K, epi, env, cus):
         fused = env.get("SMER_SPLITK_FUSED", "")[:1] == "1" and N % 4 == 0 and epi.ldcf % 4 == 0 and \
             tiles * 4 <= TICKET_BYTES
         name += "+splitk_fused" if fused else "+splitk_reduce"
-    return name
+    return P(name, split, kchunk)
 
 
-def label(case, run, cus):
+def mirror_plan(case, run, cus):
     f = epi_flags(case, run)
     if case.dtype == F32:
         f.lda = case.a_ld if case.a_ld is not None else in_ld(case, "A")
-    return expected_kernel(case.dtype, case.ak, case.bk, case.M, case.N, case.K, f, case.env, cus)
+    return expected_plan(case.dtype, case.ak, case.bk, case.M, case.N, case.K, f, case.env, cus)
+
+
+def label(case, run, cus):
+    return mirror_plan(case, run, cus).name
+
+
+# include/smer_hip.h SMER_PLAN_*, by the field of epi_flags that sets each
+PLAN_BITS = dict(C=0x1, Cf=0x2, bias=0x4, relu=0x8, drop=0x10, residual=0x20, gate=0x40, vec=0x80,
+                 rowsum=0x800, ws=0x1000)
+PLAN_CF_ALIGNED16, PLAN_F32_ALIGNED = 0x400, 0x2000
+
+
+def library_plan(lib, case, run, cus):
+    """What the library's own dispatch would launch for a run (smer_gemm_plan:
+    nothing is launched; cus = 0 asks for the current device's CU count), in
+    the form of expected_plan.  smer_gemm_plan takes the facts of a call as
+    plain ints, so this is the library's plan for this module's MODEL of the
+    call (epi_flags: e.vec, the workspace of ops._gemm_call / linear_wgrad;
+    16-B aligned buffers but for a_off, the strides of input_bufs), not for
+    the pointers tests/test_gemm_edges_gpu.py execute() passes: it holds the
+    library's decision against the mirror's, and a fact that epi_flags
+    mis-models is wrong on both sides alike."""
+    import ctypes
+    f = epi_flags(case, run)
+    facts = sum(bit for k, bit in PLAN_BITS.items() if getattr(f, k)) | PLAN_CF_ALIGNED16
+    if case.dtype == F32:
+        lda = case.a_ld if case.a_ld is not None else in_ld(case, "A")
+        if lda % 4 == 0 and in_ld(case, "B") % 4 == 0 and case.a_off % 4 == 0:
+            facts |= PLAN_F32_ALIGNED
+    out = (ctypes.c_int * 8)()
+    rc = lib.smer_gemm_plan(1 if case.dtype == BF16 else 0, int(case.ak), int(case.bk), case.M, case.N, case.K,
+                            facts, f.ldcf, WS_BYTES if f.ws else 0, run.max_wg, cus, out)
+    assert rc == 0, lib.smer_last_error()
+    kernel, _, _, _, _, split, kchunk, reduce = out
+    name = "+".join(lib.smer_gemm_kernel_name(i).decode() for i in (kernel, reduce) if i >= 0)
+    return SimpleNamespace(name=name, split=split, kchunk=kchunk)
+
+
+def plan_mismatches(lib, cus, setenv, lib_cus=None):
+    """Every (case, run) of the table whose mirror and library plans differ at
+    `cus` CUs (the library asked with lib_cus when given: 0 is the device's
+    own count), the case's env applied through `setenv(env)`:
+    [(case id, run id, mirror, library)]."""
+    bad = []
+    for case in CASES:
+        setenv(case.env)
+        for run in case.runs:
+            m = mirror_plan(case, run, cus)
+            l = library_plan(lib, case, run, cus if lib_cus is None else lib_cus)
+            same = m.name == l.name and (m.split is None or (m.split, m.kchunk) == (l.split, l.kchunk))
+            if not same:
+                bad.append((case.id, run_id(run), vars(m), vars(l)))
+    return bad
 
 
 def all_runs():

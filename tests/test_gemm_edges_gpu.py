@@ -1,8 +1,12 @@
 """smer_gemm (bf16 and fp32) and smer_gemm_wgrad_bias_ex (csrc/gemm.hip)
 against the float64 reference of tests/gemmref.py, element by element, at the
 shapes where launch_bf16 / launch_f32 change kernel or template arguments
-(gemmref.CASES; each run is labelled with gemmref.expected_kernel for the
+(gemmref.CASES; before each run the library's own plan for the call,
+smer_gemm_plan, must name the kernel gemmref.expected_kernel expects at the
 device's CU count).
+
+ * test_plan_matches_mirror: the library's dispatch against the mirror over
+   the whole table, at the device's CU count and at 64 / 256 / 304.
 
  * test_exact: inputs whose every product and partial sum is exact in fp32
    (classes S and F, gemmref's docstring; the precondition is asserted): C,
@@ -56,6 +60,31 @@ def set_env(monkeypatch, env):
             monkeypatch.setenv(k, env[k])
         else:
             monkeypatch.delenv(k, raising=False)
+
+
+def planned(case, run):
+    """The library's plan for a run as gemmref models the call execute()
+    makes (G.library_plan), on this device and under the current
+    environment; printed as the run's label."""
+    from smer_music_generation_amd import _lib as L
+    name = G.library_plan(L.load(), case, run, 0).name
+    print("%s %s -> %s" % (case.id, G.run_id(run), name))
+    return name
+
+
+@pytest.mark.parametrize("ncus", [0, 64, 256, 304], ids=lambda n: "cus%d" % n if n else "device")
+def test_plan_matches_mirror(monkeypatch, ncus):
+    """The library's dispatch (smer_gemm_plan: the very gemm_plan the
+    launchers run, nothing launched) and gemmref's mirror agree on every
+    (case, run) of the table, split-K slices and depth included, at this
+    device's CU count and at 64 / 256 / 304; the library's kernel names are
+    gemmref.KERNEL_NAMES."""
+    from smer_music_generation_amd import _lib as L
+    lib = L.load()
+    names = [lib.smer_gemm_kernel_name(i) for i in range(len(G.KERNEL_NAMES) + 1)]
+    assert names == [n.encode() for n in G.KERNEL_NAMES] + [None]
+    bad = G.plan_mismatches(lib, ncus or cus(), lambda env: set_env(monkeypatch, env), lib_cus=ncus)
+    assert not bad, bad
 
 
 class Operands:
@@ -135,7 +164,7 @@ def test_exact(monkeypatch, case, cls):
     opnd = Operands(case, cls)
     prod, _ = G.product64(case, cls, dev)
     for run in case.runs:
-        print("%s %s %s -> %s" % (case.id, cls, G.run_id(run), G.label(case, run, cus())))
+        assert planned(case, run) == G.label(case, run, cus()), "%s %s %s" % (case.id, cls, G.run_id(run))
         ref = G.reference(case, cls, run, prod)
         check_exact(execute(opnd, run, ref), ref, case)
         if "SMER_SPLITK_FUSED" in case.env:
@@ -146,7 +175,7 @@ def test_exact(monkeypatch, case, cls):
 def test_bound(monkeypatch, cid, run):
     case = G.BY_ID[cid]
     set_env(monkeypatch, case.env)
-    print("%s R %s -> %s" % (case.id, G.run_id(run), G.label(case, run, cus())))
+    assert planned(case, run) == G.label(case, run, cus()), "%s R %s" % (case.id, G.run_id(run))
     prod, sabs = G.product64(case, "R", dev)
     ref = G.reference(case, "R", run, prod)
     bound = G.r_bound(case, run, ref, sabs)

@@ -120,6 +120,34 @@ def test_table_edges_at_256_cus():
     assert [G.epi_flags(c, r).vec for r in c.runs] == [True] * 7 + [False, True, False]
 
 
+@pytest.mark.parametrize("ncus", [64, 256, 304])
+def test_plan_matches_mirror(monkeypatch, ncus):
+    """The library's dispatch (smer_gemm_plan with an explicit CU count: no
+    HIP call, nothing launched) and the mirror agree on every (case, run) of
+    the table, split-K slices and depth included.  Skips only where
+    libsmer_hip.so is not built or cannot be loaded without a GPU;
+    tests/test_gemm_edges_gpu.py runs the same comparison on the device."""
+    import os
+    from smer_music_generation_amd import _lib as L
+    if not os.path.exists(L.LIB_PATH):
+        pytest.skip("libsmer_hip.so is not built")
+    try:
+        lib = L.load()
+    except OSError as e:
+        if torch.cuda.is_available():
+            raise
+        pytest.skip("libsmer_hip.so does not load without a GPU: %s" % e)
+
+    def setenv(env):
+        for k in G.ENV_SWITCHES:
+            monkeypatch.setenv(k, env[k]) if k in env else monkeypatch.delenv(k, raising=False)
+
+    names = [lib.smer_gemm_kernel_name(i) for i in range(len(G.KERNEL_NAMES) + 1)]
+    assert names == [n.encode() for n in G.KERNEL_NAMES] + [None]
+    bad = G.plan_mismatches(lib, ncus, setenv)
+    assert not bad, bad
+
+
 # --------------------------------------------------------------- frames
 def test_buf_frames():
     d = torch.arange(12.0).view(3, 4)
