@@ -51,6 +51,8 @@
  *                        around any grammar step
  *   smer_logprob_rows    the same number for given tokens at many rows of one
  *                        full forward, each at its own grammar state
+ *   smer_logits_template infill templates: the given opening of a span (a
+ *                        token, or any pitch) forced ahead of any grammar step
  *   smer_layernorm_*   residual LayerNorm, eps 1e-5 (transformer.py:392,395,
  *                        462,466,469; final norms 274-275, 329-330)
  *   smer_embed_*         embedding gather x sqrt(d) + sinusoidal PE + dropout
@@ -505,6 +507,27 @@ int smer_logprob_rows(int N, int V, int nrows, const float* logits, long ldl, co
                       const uint8_t* code, const uint8_t* keep, const int8_t* ban_idx,
                       const uint32_t* ban_bits, int K, const int32_t* id, double* out_lp,
                       int32_t* out_arg, smer_stream_t stream);
+/* Infill templates (not a reference operation): the first positions of a span
+ * are given, as a token or as "any pitch".  Run between the vocabulary
+ * projection and any smer_grammar_*_step entry on the same logits, state, cls
+ * and max_masks -- after smer_logits_ban and smer_logprob_stage, if any, so
+ * that a score is taken from the row before it is rewritten.  For request r
+ * it reads `done`, the mask index and the span length (state word 2) from the
+ * state row and takes e = tape[(r * max_masks + mask index) * L + length - 1]
+ * (int16 [R, max_masks, L]):
+ *   0 <= e < V  stores 0.f at logits[(2r+1) * ldl + e] and -100.f at every
+ *               other v < V of that row;
+ *   e == -2     stores -100.f at every v < V whose cls[v] lacks the pitch bit
+ *               (2);
+ *   e == -1     (free), any other value, done requests, mask indices outside
+ *               0..max_masks-1 and lengths outside 1..L write nothing.
+ * The grammar entries form keep ? logit : -100.f, so a logit of exactly -100.f
+ * is drawn as a masked one; the caller guarantees that the forced token is
+ * kept by the state it is forced in.  V <= 512.  Status return, no
+ * allocation, no synchronisation. */
+int smer_logits_template(int R, int V, float* logits, long ldl, const int32_t* state, int nst,
+                         const uint8_t* cls, const int16_t* tape, int max_masks, int L,
+                         smer_stream_t stream);
 
 int smer_layernorm_fwd(int dtype, int M, int N, const void* x, long ldx,
                        const float* gamma, const float* beta, float eps,

@@ -1249,3 +1249,54 @@ extern "C" int smer_logprob_rows(int N, int V, int nrows, const float* logits, l
   SMER_CHECK_LAUNCH("smer_logprob_rows");
   return SMER_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Infill templates: for the first positions of a span the token, or only its
+// class, is given; the row is rewritten so that the grammar kernel can draw
+// nothing else.  Both grammar kernels form x = keep[i] ? logit[i] : -100.f, so
+// a kept logit stored as exactly -100.f is a masked one, and the forced
+// token's 0.f survives because the host validated that its state keeps it.
+//   tape int16 [R, max_masks, L]: the entry that governs the draw made when
+//   the span holds i body tokens (ST_LEN == i + 1) is tape[r, midx, i]:
+//   -1 free, 0 .. V-1 that token, -2 any pitch token (the C_PITCH bit of cls).
+// One wave per request, 8 tokens per lane (V <= 512), logits_ban_kernel's
+// layout.  A token entry stores 0.f at the token and -100.f at every other
+// i < V; -2 stores -100.f at every i < V that is no pitch.  Done rows, free
+// entries, a mask index or a position outside the tape and an entry >= V
+// write nothing; the lookups are clamped, not guarded, and only the stores
+// are predicated.  The class bytes do not depend on the state, so their loads
+// run beside the state -> tape chain.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void logits_template_kernel(
+    int R, int V, float* __restrict__ logits, long ldl, const int32_t* __restrict__ state, int nst,
+    const uint8_t* __restrict__ cls, const int16_t* __restrict__ tape, int max_masks, int L) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int32_t* st = state + (long)r * nst;
+  const int done = st[ST_DONE], midx = st[ST_MIDX], at = st[ST_LEN] - 1;
+  const int mc = min(max(midx, 0), max_masks - 1), ac = min(max(at, 0), L - 1);
+  const int e = (int)tape[((long)r * max_masks + mc) * L + ac];
+  const bool on = !done && midx >= 0 && midx < max_masks && at >= 0 && at < L;
+  const bool tok = on && e >= 0 && e < V, pitch = on && e == -2;
+  float* lr = logits + (long)(2 * r + 1) * ldl;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int i = lane * 8 + j;
+    const bool is_pitch = cls[min(i, V - 1)] & C_PITCH;
+    if (i < V && (tok || (pitch && !is_pitch))) lr[i] = (tok && i == e) ? 0.f : -100.f;
+  }
+}
+
+// Graph-capturable, no allocation, no synchronisation.  logits, state and cls
+// are the grammar entry's own arguments (request r's row at (2r+1) * ldl).
+extern "C" int smer_logits_template(int R, int V, float* logits, long ldl, const int32_t* state, int nst,
+                                    const uint8_t* cls, const int16_t* tape, int max_masks, int L,
+                                    smer_stream_t stream) {
+  SMER_REQUIRE(R > 0 && V > 0 && V <= 512 && nst >= 9 && max_masks > 0 && L > 0,
+               "smer_logits_template: sizes (V <= 512)");
+  SMER_REQUIRE(ldl >= V, "smer_logits_template: logits row stride");
+  SMER_REQUIRE(logits && state && cls && tape, "smer_logits_template: null pointer");
+  hipLaunchKernelGGL(logits_template_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, R, V, logits, ldl,
+                     state, nst, cls, tape, max_masks, L);
+  SMER_CHECK_LAUNCH("smer_logits_template");
+  return SMER_OK;
+}

@@ -129,12 +129,15 @@ class _GrammarGraph:
     grammar kernel.  score: it also takes the log-probability of every drawn
     token (smer_logprob_stage before the grammar kernel, smer_logprob_commit
     after it) into g_logp float64 [R, cap], entry for entry with g_out.
+    tpl: the graph runs smer_logits_template in front of the grammar kernel
+    (after the score stage, which therefore sees the row the model gave), on
+    g_tape int16 [R, nm, TPL_LEN].
     Construction allocates; load() writes a call's inputs, before the capture
     and before every later call alike."""
 
     def __init__(self, sess, key, mode, nm, keep_shape, cls_shape, *, eos, m0, lookahead, max_span,
-                 use_ring, ban, score):
-        self.key, self.mode, self.ban, self.score = key, mode, ban, score
+                 use_ring, ban, score, tpl=False):
+        self.key, self.mode, self.ban, self.score, self.tpl = key, mode, ban, score, tpl
         self.graph = None
         R, cap, dev = sess.R, sess.Tmax, sess.dev
 
@@ -158,6 +161,8 @@ class _GrammarGraph:
             b["g_lp_row"] = zeros(R, 512, dtype=torch.float64)
             b["g_lp_stage"] = torch.full((R,), -1, dtype=torch.int32, device=dev)
             b["g_logp"] = zeros(R, cap, dtype=torch.float64)
+        if tpl:
+            b["g_tape"] = torch.full((R, nm, ops.TPL_LEN), ops.TPL_FREE, dtype=torch.int16, device=dev)
         # live counts: the step's grammar kernel publishes its count into a
         # pinned host ring itself (no per-step memset / D2H copy between the
         # replays); SMER_GRAMMAR_RING=0: memset + copy per step (A/B)
@@ -167,7 +172,7 @@ class _GrammarGraph:
         self.gargs = dict(eos=eos, m0=m0, trash_pos=sess.Tmax - 1, max_span=max_span,
                           ring=self.ring if use_ring else None)
 
-    def load(self, st, tg, keep, cls, src_len, ban=None, sampler=None):
+    def load(self, st, tg, keep, cls, src_len, ban=None, sampler=None, tape=None):
         """Write one call's inputs (host arrays) and clear its outputs."""
         b = self.bufs
 
@@ -181,6 +186,8 @@ class _GrammarGraph:
         if self.ban:
             up("g_banmask", ban[0])
             up("g_banbits", ban[1].view(np.int32))
+        if self.tpl:
+            up("g_tape", tape)
         if self.mode != "greedy":
             up("g_reject", np.ascontiguousarray(sampler.reject, dtype=np.uint8))
             up("g_mt_rows" if self.mode == "rows" else "g_mt", sampler.mt.view(np.int32))
@@ -201,6 +208,8 @@ class _GrammarGraph:
             ops.logits_ban(logits, state, b["g_banmask"], b["g_banbits"])
         if self.score:  # the row's log-softmax while the row exists, the drawn token's entry after
             ops.logprob_stage(logits, state, targets, keep, b["g_lp_row"], b["g_lp_stage"])
+        if self.tpl:  # the given opening of a span: forced after the score saw the model's row
+            ops.logits_template(logits, state, b["g_cls"], b["g_tape"])
         if self.mode == "greedy":
             ops.grammar_greedy_step(logits, state, targets, keep, b["g_cls"], b["g_srclen"], ids, meta,
                                     b["g_out"], b["g_alive"], **self.gargs)
@@ -627,7 +636,7 @@ class DecodeSession:
         return t_b - t_a, time.perf_counter() - t_b
 
     def sampled_decode(self, spans, keep, reject, cls, *, eos, m0, lookahead=3, max_span=100,
-                       t=1.0, p=None, seeds=None, bans=None, score=False):
+                       t=1.0, p=None, seeds=None, bans=None, score=False, templates=None):
         """The sampled infill loop (the reference's sampling(): softmax with
         temperature, then weighted_sampling or, with p, nucleus, and its
         redraws) on device: each step is one replay of the captured
@@ -644,8 +653,8 @@ class DecodeSession:
         request form of the kernel (smer_grammar_sample_step_rows), the "rows"
         graph kept beside the unseeded "stream" one, and np.random is neither
         read nor written.  Other seeds replay that graph.
-        bans, score: as greedy_decode's; the scores are taken at t = 1 over
-        the whole masked distribution, whatever t and p are.
+        bans, score, templates: as greedy_decode's; the scores are taken at
+        t = 1 over the whole masked distribution, whatever t and p are.
         Returns a DecodeResult whose `fails` flag the ids whose redraws ran
         out."""
         if all(sp.done for sp in spans):  # nothing to draw: np.random stays untouched
@@ -683,7 +692,7 @@ class DecodeSession:
             mt_h[624] = int(st0[2])
         res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead, max_span=max_span,
                                    sampler=_Sampler(reject, mt_h, tp_h, seeds is not None), bans=bans,
-                                   score=score)
+                                   score=score, templates=templates)
         if seeds is None:  # the stream goes on where the device left it
             m = self._greedy.bufs["g_mt"].cpu().numpy().view(np.uint32)
             np.random.set_state(("MT19937", m[:624].copy(), int(m[624]), st0[3], st0[4]))
@@ -691,7 +700,7 @@ class DecodeSession:
                             fails=[[(x >> 16) & 1 for x in q] for q in res.ids])
 
     def greedy_decode(self, spans, keep, cls, *, eos, m0, lookahead=3, max_span=100, bans=None,
-                      score=False):
+                      score=False, templates=None):
         """Run the greedy infill loop of `spans` (generation._Span, one per
         request slot 0..len-1, freshly started, sources prefilled) entirely
         on device: each step is one replay of the captured decoder step +
@@ -708,12 +717,20 @@ class DecodeSession:
         if constrained) and the result's `logp` holds, per request, the float64
         log-probabilities of its emitted ids (generation.token_logprobs at each
         id, t = 1, the whole masked distribution).  Without it: the graphs
-        without those nodes, as ever."""
+        without those nodes, as ever.
+        templates (infill templates): per span None or its rows, one per mask:
+        None, or the items of the span's opening (a token id, or ops.TPL_PITCH),
+        at most ops.TPL_LEN of them.  With any span templated the call replays
+        the '+tpl' graph of its mode (after '+ban', before '+score'), whose
+        extra node (smer_logits_template) forces the items from a tape that is
+        device data refreshed per call: other templates replay that graph, and
+        a span without one gets an all-free tape.  None (or all None): the
+        graphs without that node, as ever."""
         return self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
-                                    max_span=max_span, bans=bans, score=score)
+                                    max_span=max_span, bans=bans, score=score, templates=templates)
 
     def _grammar_decode(self, spans, keep, cls, *, eos, m0, lookahead, max_span, sampler=None, bans=None,
-                        score=False):
+                        score=False, templates=None):
         """greedy_decode, or with `sampler` (a _Sampler) sampled_decode."""
         R = len(spans)
         if R > self.R:
@@ -773,12 +790,31 @@ class DecodeSession:
             ban = (bm_h, bb_h)
             gkey += (K,)
         gname = mode if ban is None else mode + "+ban"
+        # infill templates: once more a graph of its own, whose tape is device
+        # data; a call without any replays the graphs that never held the node
+        tape = None
+        if templates is not None and any(x is not None for x in templates):
+            if len(templates) != R:
+                raise ValueError("one templates entry (or None) per span")
+            if keep.shape[1] > 512:
+                raise ValueError("templates: the device path serves vocabularies up to 512 tokens")
+            tape = np.full((self.R, nm, ops.TPL_LEN), ops.TPL_FREE, dtype=np.int16)
+            for r, rows in enumerate(templates):
+                for k, row in enumerate(rows or ()):
+                    if row is None or not len(row):
+                        continue
+                    if k >= nm or len(row) > ops.TPL_LEN:
+                        raise ValueError("templates: at most %d rows of at most %d items per request"
+                                         % (nm, ops.TPL_LEN))
+                    tape[r, k, :len(row)] = row
+            gname += "+tpl"
+            gkey += ("tpl", ops.TPL_LEN)
         if score:  # take scores: again a graph of its own, with buffers of its own
             if keep.shape[1] > 512:
                 raise ValueError("score: the device path scores vocabularies up to 512 tokens")
             gname += "+score"
             gkey += ("score",)
-        inputs = (st, tg, keep, cls, self.src_len, ban, sampler)
+        inputs = (st, tg, keep, cls, self.src_len, ban, sampler, tape)
         gg = self._graphs.get(gname)
         if gg is not None and gg.key == gkey:
             # the captured step + grammar graph of an earlier call with the
@@ -793,7 +829,7 @@ class DecodeSession:
             self._graphs.pop(gname, None)  # a stale graph's buffers go before the new ones are made
             gg = _GrammarGraph(self, gkey, mode, nm, keep.shape, cls.shape, eos=eos, m0=m0,
                                lookahead=lookahead, max_span=max_span, use_ring=use_ring,
-                               ban=ban is not None, score=score)
+                               ban=ban is not None, score=score, tpl=tape is not None)
             gg.load(*inputs)
             warm_s, capture_s = self._capture_grammar(gg)
             self._graphs[gname] = gg

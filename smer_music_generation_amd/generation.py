@@ -33,6 +33,10 @@ Differences, all opt-in keywords with reference defaults:
   * `score_infill(...)` / `score_batch(...)`: the same log-probabilities for
     GIVEN content (the bar that was there, an edited take, another
     checkpoint's take), teacher-forced: one full forward, no step loop.
+  * `template=None` on `generation_all` / `infill` / `generation_batch`: the
+    opening of a span is given -- token by token, or as ANY_PITCH, "a pitch of
+    the model's choice" -- and the model writes the rest (`rhythm_template`
+    keeps a bar's rhythm, `opening_template` its first tokens).
 The grammar state machine, the -100 logit masking, the float64 softmax and
 the numpy RNG consumption are the reference's, so with the same
 `np.random` state the same token ids come out.
@@ -47,6 +51,7 @@ import torch
 
 from .decode import DecodeSession
 from .durations import durations_for_events
+from .ops import TPL_PITCH
 from .wire import (change_controls, decoder_targets, fill_empty_bars, mask_bar_and_track,  # noqa: F401
                    mask_targets, restore_marked_input, track_names_of)
 
@@ -152,17 +157,60 @@ def allowed_ids(vocab, **flags):
     return keep
 
 
-def sampling(logit, vocab, p=None, t=1.0, greedy=False, rng=np.random, ban=None, **flags):
+class _AnyPitch:
+    """The type of ANY_PITCH."""
+    __slots__ = ()
+
+    def __repr__(self):
+        return "ANY_PITCH"
+
+
+# A template item (`template=`): any pitch token, and only a pitch token.
+ANY_PITCH = _AnyPitch()
+
+_PITCH_MASKS = {}
+
+
+def _pitch_mask(vocab):
+    """Boolean [V]: the pitch tokens."""
+    hit = _PITCH_MASKS.get(id(vocab))
+    if hit is None or hit[0] is not vocab:
+        m = np.zeros(vocab.vocab_size, dtype=bool)
+        m[vocab.pitch_indices] = True
+        m.setflags(write=False)
+        hit = _PITCH_MASKS[id(vocab)] = (vocab, m)
+    return hit[1]
+
+
+def _forced(x, vocab, item):
+    """A template item applied to the masked row x (`where(keep, logit,
+    -100)`, float64 or float32) ahead of the division by t.  A token id: 0.0
+    at the token and -100.0 at every other entry.  TPL_PITCH: -100.0 at every
+    entry that is no pitch token; the pitch entries keep what the grammar mask
+    and the pitch ban gave them."""
+    if item == TPL_PITCH:
+        return np.where(_pitch_mask(vocab), x, x.dtype.type(-100.0))
+    out = np.full_like(x, -100.0)
+    out[item] = 0.0
+    return out
+
+
+def sampling(logit, vocab, p=None, t=1.0, greedy=False, rng=np.random, ban=None, force=None, **flags):
     """`generation.py:41-95` with vectorised masking.  rng: the stream the
     draw comes from (np.random: the global one, as the reference).  ban
     (boolean [V], True = banned; None: nothing): `keep &= ~ban`, a banned
-    token's logit becomes -100.0 exactly as a masked class's does."""
+    token's logit becomes -100.0 exactly as a masked class's does.  force (a
+    template item: a token id, or ANY_PITCH; None: nothing): the masked row is
+    rewritten by `_forced` before the softmax; the draw itself, and what it
+    takes from rng, is the draw of any other row."""
     if isinstance(logit, torch.Tensor):
         logit = logit.squeeze().detach().cpu().numpy()
     keep = allowed_ids(vocab, **flags)
     if ban is not None:
         keep = keep & ~np.asarray(ban, dtype=bool)
     lg = np.where(keep, np.asarray(logit, dtype=np.float32).astype(np.float64), -100.0)
+    if force is not None:
+        lg = _forced(lg, vocab, TPL_PITCH if force is ANY_PITCH else int(force))
     probs = softmax_with_temperature(lg, t)
     if greedy:
         return int(np.argmax(probs))
@@ -506,7 +554,7 @@ class _Span:
     """Decoding state of one request: mask index, span tokens, grammar flags."""
 
     def __init__(self, vocab, src, mask_target, all_controls, no_whole, greedy, logger, t=1.0,
-                 p=None, rng=np.random, bans=None, score=False):
+                 p=None, rng=np.random, bans=None, score=False, template=None):
         self.v = vocab
         self.t = t
         self.p = p
@@ -519,6 +567,9 @@ class _Span:
         # path assigns its own); without, nothing is computed
         self.score = bool(score)
         self.logp = []
+        # infill template (_check_template's rows): per mask None or the items
+        # of the span's opening, token ids or TPL_PITCH; None: no template
+        self.tpl = template
         self.src = src
         self.mask_target = mask_target
         self.all_controls = set(int(c) for c in all_controls)
@@ -558,6 +609,14 @@ class _Span:
             return None
         return self.ban_of_mask, ban_bits(self.ban_rows)
 
+    def forced(self):
+        """The template item that governs the draw about to be made (a token
+        id, or TPL_PITCH), or None: item len(this_in) - 1 of the mask's row."""
+        if self.tpl is None or self.mask_idx >= len(self.tpl):
+            return None
+        row, i = self.tpl[self.mask_idx], len(self.this_in) - 1
+        return None if row is None or i >= len(row) else row[i]
+
     def _score(self, logit, flags, ban, idx):
         """The emitted id's log-probability (t = 1, the whole distribution,
         the redraws not counted) from the draw's own keep; draws nothing."""
@@ -578,6 +637,9 @@ class _Span:
         ban = self.ban()
         if ban is not None:  # (an unconstrained draw is the call it always was)
             flags = dict(flags, ban=ban)
+        force = self.forced()
+        if force is not None:  # (after the ban; _draw scores from the flags it was given: the row before this)
+            flags = dict(flags, force=force)
         idx = sampling(logit, self.v, p=self.p, t=self.t, greedy=self.greedy, rng=self.rng, **flags)
         if check is None:
             return idx
@@ -728,7 +790,7 @@ class _Precision:
 def generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
                    bars_to_generate, *, greedy=False, use_kv_cache=True, stats=None,
                    precision="fp32", warm=True, device_grammar=True, t=1.0, p=None, variations=None,
-                   seed=None, pitches=None, logprobs=False, rank=False):
+                   seed=None, pitches=None, logprobs=False, rank=False, template=None):
     """`generation.py:468-696`.  Returns (restored '<U9' tokens,
     mask_track_names, mask_bar_names) or None (nothing masked / on error,
     after printing it, as the reference does).  `stats` (a dict, opt-in)
@@ -815,12 +877,44 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
     being short -- ties to the lower take index; `stats` receives 'order', the
     take indices in returned order, while 'seeds', 'logprobs' and 'scores'
     stay in take order.  Anything but a bool for either, or rank without
-    variations, raises ValueError before the model or np.random is touched."""
+    variations, raises ValueError before the model or np.random is touched.
+    template: None (default): every draw is free, today's behaviour bit for
+    bit.  Otherwise one row per mask, in mask_targets order; a row is None
+    (free) or a sequence of items: a token (string or id) -- that token is
+    emitted at that position; ANY_PITCH -- any pitch token, and only a pitch
+    token; '<eos>', as the last item of a note span's row only -- the span ends
+    there.  Item i governs the draw made when the span holds i body tokens;
+    the positions past the row are free, so a row is a determined opening
+    followed by free decoding (rhythm_template and opening_template build the
+    two common ones).  A constrained draw is a masked draw, as `pitches` is:
+    after the float32 -> float64 widening, the grammar mask and the pitch ban,
+    and before the division by t, a token item v sets x[v] = 0.0 and every
+    other entry to -100.0, and ANY_PITCH sets every entry that is no pitch to
+    -100.0.  The draw, the redraw loop and what they take from the stream are
+    those of any other step, so the stream afterwards is defined by them, and
+    every path -- device, host loop, use_kv_cache=False -- agrees on it.  Any
+    other token keeps probability about e^(-100/t) each: not zero (DESIGN
+    section 8).  logprobs=True reports the emitted token's log-probability
+    under the model, the grammar mask and the pitch ban BEFORE the template
+    is applied -- the number score_infill gives for the same token.  With
+    variations all takes carry the template.  On the device the step graphs
+    named '+tpl' force the items from a tape (smer_logits_template); a call
+    without a template replays the graphs it always did.  _check_template
+    lists what raises ValueError, before the model or np.random is touched."""
     t, p = _check_tp(t, p)
     n = None if variations is None else _check_variations(variations)
     seeds = _check_seed(seed, None, n)
     allowed = _check_pitches(pitches, tracks_to_generate)
     score = _check_score(logprobs, rank, variations)
+    tpl = None
+    if template is not None:
+        try:
+            q = _prepare(list(events), vocab, tracks_to_generate, bars_to_generate)
+            bans = _request_bans(vocab, list(events), tracks_to_generate, bars_to_generate, allowed)
+        except Exception as e:  # reference behaviour (generation.py:695-696): what the call itself would print
+            print(e)
+            return None
+        tpl = _check_template(template, vocab, q[0], q[3], all_controls, q[4], bans)
     if stats is not None:
         stats["seeds"] = seeds
         stats["pitches"] = allowed
@@ -834,7 +928,8 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
                                            return_stats=True, device_grammar=device_grammar, warm=warm,
                                            t=t, p=p, variations=[n],
                                            seed=None if seeds is None else [seeds[0]],
-                                           pitches=[allowed], logprobs=score, rank=bool(rank))
+                                           pitches=[allowed], logprobs=score, rank=bool(rank),
+                                           template=None if template is None else [template])
                 if stats is not None:
                     stats["steps"] = st["steps"]
                     if score:
@@ -849,7 +944,7 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
         return _generation_all(model, events, device, vocab, logger, all_controls,
                                tracks_to_generate, bars_to_generate, greedy, use_kv_cache, stats,
                                warm, device_grammar, t, p, None if seeds is None else seeds[0],
-                               allowed, score)
+                               allowed, score, tpl)
 
 
 _REJECT_CACHE = {}
@@ -877,6 +972,14 @@ def _device_bans(spans):
     call then replays the graphs without the ban kernel)."""
     bans = [sp.device_bans() for sp in spans]
     return bans if any(b is not None for b in bans) else None
+
+
+def _device_templates(spans):
+    """`templates=` of DecodeSession.greedy_decode / sampled_decode: per span
+    None or its rows; None when no span has a template (the call then replays
+    the graphs without the template kernel)."""
+    tpls = [sp.tpl for sp in spans]
+    return tpls if any(x is not None for x in tpls) else None
 
 
 def _replay(spans, res, logger, sampled=True):
@@ -923,7 +1026,7 @@ def _sampled_on_device(sess, st, vocab, all_controls, logger, seed=None):
     res = sess.sampled_decode([st], keep, reject_table(vocab), cls, eos=vocab.eos_index,
                               m0=vocab.char2index('m_0'), t=st.t, p=st.p,
                               seeds=None if seed is None else [seed], bans=_device_bans([st]),
-                              score=st.score)
+                              score=st.score, templates=_device_templates([st]))
     if res.err[0] & 2:
         if seed is None:
             np.random.set_state(rng0)
@@ -935,10 +1038,11 @@ def _sampled_on_device(sess, st, vocab, all_controls, logger, seed=None):
 
 def _generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
                     bars_to_generate, greedy, use_kv_cache, stats, warm=True, device_grammar=True,
-                    t=1.0, p=None, seed=None, allowed=None, score=False):
+                    t=1.0, p=None, seed=None, allowed=None, score=False, tpl=None):
     def fresh_span():  # a seeded request starts its own stream (anew after a device redo)
         rng = np.random if seed is None else np.random.RandomState(seed)
-        return _Span(vocab, src, target, all_controls, no_whole, greedy, logger, t, p, rng, bans, score)
+        return _Span(vocab, src, target, all_controls, no_whole, greedy, logger, t, p, rng, bans, score,
+                     tpl)
     try:
         bans = _request_bans(vocab, events, tracks_to_generate, bars_to_generate, allowed)
         src, mtn, mbn, target, no_whole = _prepare(events, vocab, tracks_to_generate,
@@ -1066,7 +1170,7 @@ def _batch_session(model, R, Smax, Tmax, precision, exact_tmax=False, warm=True,
 def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logger=None,
                      max_tgt=None, precision=None, return_stats=False, device_grammar=True,
                      warm=True, t=1.0, p=None, variations=None, seed=None, pitches=None,
-                     logprobs=False, rank=False):
+                     logprobs=False, rank=False, template=None):
     """Decode many infill requests in lockstep on one KV-cached session.
 
     requests: list of (events, tracks_to_generate, bars_to_generate).
@@ -1131,6 +1235,13 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
     of take indices per request; 'generated', 'seeds', 'logprobs' and 'scores'
     stay in take order.  Both are validated as bools before anything else is
     touched (ValueError).
+    template: None, or one value per request (see generation_all): None for a
+    request without a template, else its rows, one per mask.  With variations
+    all takes of a request carry its template.  A call in which no request
+    has one replays the step graphs it always did; otherwise the '+tpl' graph
+    of its mode ('greedy+tpl', 'rows+ban+tpl+score', ..), in which the
+    requests without a template read an all-free tape.  Validated before
+    anything else is touched (ValueError).
     Returns a list of (restored, mask_track_names, mask_bar_names) (None
     where nothing was masked), and optionally {'tokens', 'steps', 'sources',
     'prefill_rows', 'seeds' (the effective seed of every entry of 'generated',
@@ -1145,15 +1256,23 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
     bans = [_request_bans(vocab, list(ev), tr, br, a) for (ev, tr, br), a in zip(requests, allowed)]
     preps = [_prepare(list(ev), vocab, tr, br) for ev, tr, br in requests]
     srcs = [q[0] for q in preps]
+    if template is None:
+        tpls = [None] * len(requests)
+    elif not isinstance(template, (list, tuple)) or len(template) != len(requests):
+        raise ValueError("template: None, or one value per request (%d)" % len(requests))
+    else:
+        tpls = [_check_template(x, vocab, q[0], q[3], all_controls, q[4], bn)
+                for x, q, bn in zip(template, preps, bans)]
     if takes is not None:  # the expanded list: take k of request i is a request of its own
+        tpls = [x for x, n in zip(tpls, takes) for _ in range(n)]
         preps = [q for q, n in zip(preps, takes) for _ in range(n)]
         tps = [x for x, n in zip(tps, takes) for _ in range(n)]
         bans = [x for x, n in zip(bans, takes) for _ in range(n)]
 
     def fresh_spans():  # seeded: every request's stream starts (again) at its seed
         rngs = [np.random] * len(preps) if seeds is None else [np.random.RandomState(x) for x in seeds]
-        return [_Span(vocab, q[0], q[3], all_controls, q[4], greedy, logger, a, b, g, bn, score)
-                for q, (a, b), g, bn in zip(preps, tps, rngs, bans)]
+        return [_Span(vocab, q[0], q[3], all_controls, q[4], greedy, logger, a, b, g, bn, score, tp)
+                for q, (a, b), g, bn, tp in zip(preps, tps, rngs, bans, tpls)]
     spans = fresh_spans()
     R = len(preps)
     Smax = max(len(q[0]) for q in preps)
@@ -1177,12 +1296,15 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
         fed = [0] * R
         latency = None
         kv_reads = None
-        if greedy and device_grammar:
+        # (the template kernel serves vocabularies up to 512 tokens, as the sampler does: a
+        # templated greedy call above that runs the host loop below)
+        if greedy and device_grammar and (vocab.vocab_size <= 512 or _device_templates(spans) is None):
             keep, cls = grammar_tables(vocab, all_controls)
             m0 = vocab.char2index('m_0')
             ts = time.perf_counter()
             res = sess.greedy_decode(spans, keep, cls, eos=vocab.eos_index, m0=m0,
-                                     bans=_device_bans(spans), score=score)
+                                     bans=_device_bans(spans), score=score,
+                                     templates=_device_templates(spans))
             t_dev = time.perf_counter() - ts
             seqs, steps = res.ids, res.steps
             # completion time of each request from the call's start: host
@@ -1207,7 +1329,7 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
             res = sess.sampled_decode(
                 spans, keep, reject_table(vocab), cls, eos=vocab.eos_index,
                 m0=vocab.char2index('m_0'), t=[a for a, _ in tps], p=[b for _, b in tps],
-                seeds=seeds, bans=_device_bans(spans), score=score)
+                seeds=seeds, bans=_device_bans(spans), score=score, templates=_device_templates(spans))
             t_dev = time.perf_counter() - ts
             if np.any(res.err & 2):
                 # some row's probabilities missed 1 by more than 1e-9
@@ -1245,7 +1367,12 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                     ban = spans[i].ban()
                     if ban is not None:
                         keep[k] &= ~ban
-                ids = np.argmax(np.where(keep, lg, np.float32(-100.0)), axis=1)
+                x = np.where(keep, lg, np.float32(-100.0))
+                for k, i in enumerate(live):  # the template rewrites the masked row; the score below reads lg and keep
+                    force = spans[i].forced()
+                    if force is not None:
+                        x[k] = _forced(x[k], vocab, force)
+                ids = np.argmax(x, axis=1)
                 for k, i in enumerate(live):
                     if score:  # the argmax is taken outside _draw: score it from the same keep row
                         spans[i].logp.append(token_logprobs(lg[k], keep[k])[ids[k]])
@@ -1613,3 +1740,156 @@ def score_infill(model, events, device, vocab, all_controls, tracks_to_generate,
                        contents=[content], pitches=None if pitches is None else [
                            _check_pitches(pitches, tracks_to_generate)],
                        precision=precision, device_score=device_score)[0]
+
+
+# --------------------------------------------------------------------------
+# infill templates: the opening of a span is given, the model writes the rest
+# --------------------------------------------------------------------------
+def _check_template(template, vocab, src, target, all_controls, no_whole, bans=None):
+    """Validated template of one request: None stays None; otherwise one row
+    per mask, in mask_targets order, each None (free) or a sequence of items
+    -- a token (string or id), ANY_PITCH, or '<eos>' as the last item of a
+    note span's row.  Item i governs the draw made when the span holds i body
+    tokens.  Returns the rows as tuples of token ids and TPL_PITCH (None for a
+    free row), the form `_Span` and the device tape take.
+    Every row is replayed through a `_Span` without drawing (the grammar flags
+    follow token classes alone, so an ANY_PITCH item moves them as any pitch
+    does).  Raises ValueError for a wrong number of rows; a control span's row
+    that is not exactly one token of that span's class; a token outside the
+    keep set of its state (the pitch ban of `bans` applied) or one its redraw
+    check would reject; ANY_PITCH in a state, or on a track, that keeps no
+    pitch; m_0 or an unknown token; '<eos>' anywhere but last; items after the
+    token that ends the span; a note row of more than MAX_BODY body items.
+    Touches neither the model nor np.random."""
+    if template is None:
+        return None
+    if isinstance(template, (str, bytes)) or not hasattr(template, "__len__"):
+        raise ValueError("template: one row per mask (got %r)" % (template,))
+    sp = _Span(vocab, src, target, all_controls, no_whole, True, None, bans=bans)
+    if len(template) != sp.n_masks or len(target) < sp.n_masks:
+        raise ValueError("template: %d rows for %d masks" % (len(template), sp.n_masks))
+    V, table, pitch = vocab.vocab_size, vocab._char2idx, _pitch_mask(vocab)
+    rows = []
+    for k, row in enumerate(template):
+        if row is None:
+            rows.append(None)
+            continue
+        if isinstance(row, (str, bytes)) or not hasattr(row, "__iter__"):
+            raise ValueError("template: row %d is not a sequence of items (got %r)" % (k, row))
+        items = row.tolist() if isinstance(row, np.ndarray) else list(row)
+        note = _target_code(target[k]) == 0
+        if not note and len(items) != 1:
+            raise ValueError("template: row %d belongs to a control span and holds one token (got %d)"
+                             % (k, len(items)))
+        sp.mask_idx, sp.done = k, False  # every span starts from cleared flags: the rows replay apart
+        sp._start_span()
+        out = []
+        for i, x in enumerate(items):
+            if sp.done or sp.mask_idx != k:
+                raise ValueError("template: row %d goes on after the token that ends its span" % k)
+            if x is not ANY_PITCH:
+                if isinstance(x, str):
+                    x = table.get(x)
+                elif isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+                    x = None
+                if x is None or not 0 <= x < V:
+                    raise ValueError("template: row %d holds an item that is not in the vocabulary" % k)
+                x = int(x)
+                if x == sp.m0:
+                    raise ValueError("template: row %d holds m_0" % k)
+                if x == sp.eos and not (note and i == len(items) - 1):
+                    raise ValueError("template: '<eos>' only as the last item of a note span's row (row %d)" % k)
+            if i >= MAX_BODY and x != sp.eos:
+                raise ValueError("template: row %d holds more than %d body items" % (k, MAX_BODY))
+            flags, check, _ = sp.spec()
+            keep = allowed_ids(vocab, **flags)
+            ban = sp.ban()
+            if ban is not None:
+                keep = keep & ~ban
+            if x is ANY_PITCH:
+                ok = np.flatnonzero(keep & pitch)
+                if check is not None:
+                    ok = [j for j in ok if not check(int(j))]
+                if len(ok) == 0:
+                    raise ValueError("template: row %d asks for a pitch where the grammar%s allows none (item %d)"
+                                     % (k, " and pitches=" if ban is not None else "", i))
+                x, tok = TPL_PITCH, int(ok[0])
+            else:
+                if not keep[x]:
+                    raise ValueError("template: row %d, item %d: %r is not allowed there (grammar state %d%s)"
+                                     % (k, i, vocab.index2char(x), sp.state_code(),
+                                        ", pitches=" if ban is not None else ""))
+                if check is not None and check(x):
+                    raise ValueError("template: row %d, item %d: %r would be redrawn there (grammar state %d)"
+                                     % (k, i, vocab.index2char(x), sp.state_code()))
+                tok = x
+            out.append(x)
+            sp.commit(tok)
+        rows.append(tuple(out))
+    return rows
+
+
+def _template_bodies(events, vocab, tracks_to_generate, bars_to_generate, content):
+    """(bodies as id lists, target codes) of a request for the template
+    builders: `content` in score_infill's format, or with None the events' own
+    content at the masked positions."""
+    events = list(events)
+    if len(bars_to_generate) == 0 or len(tracks_to_generate) == 0:
+        raise ValueError("nothing is masked: there is nothing to build a template from")
+    # (fill_empty_bars appends to the list it is given: `events` is the masked song afterwards)
+    src, _, _, target, _ = _prepare(events, vocab, tracks_to_generate, bars_to_generate)
+    if content is None:
+        _, tracks = mask_targets(events, tracks_to_generate, bars_to_generate)
+        bodies = _split_targets(vocab, decoder_targets(events, vocab, tracks, bars_to_generate))
+    else:
+        if isinstance(content, (str, bytes)) or not hasattr(content, "__len__"):
+            raise ValueError("content: one token sequence per mask (got %r)" % (content,))
+        bodies = list(content)
+    n = int(np.sum(np.asarray(src) == vocab.char2index('m_0')))
+    if len(bodies) != n or len(target) < n:
+        raise ValueError("content: %d spans for %d masks" % (len(bodies), n))
+    return _content_ids(vocab, bodies), [_target_code(t) for t in target[:n]]
+
+
+def rhythm_template(events, vocab, tracks_to_generate, bars_to_generate, *, content=None):
+    """The template that keeps a bar's rhythm and lets the model choose new
+    notes: every note span's row is its content with each pitch token replaced
+    by ANY_PITCH, closed by '<eos>' where the content's span ended on one (a
+    body shorter than the 98-token cap whose last token is no control token);
+    control spans are free (None).  content: score_infill's format (one
+    sequence of tokens or ids per mask, without m_0 and <eos>); None: the
+    events' own content at the masked positions.  Pass the result as
+    `template=`; the call validates it against its grammar."""
+    bodies, codes = _template_bodies(events, vocab, tracks_to_generate, bars_to_generate, content)
+    pitch, eos = _pitch_mask(vocab), vocab.eos_index
+    ctrl = {i for idxs in vocab.control_indices.values() for i in idxs}
+    rows = []
+    for body, code in zip(bodies, codes):
+        if code != 0:
+            rows.append(None)
+            continue
+        row = [ANY_PITCH if pitch[x] else x for x in body[:MAX_BODY]]
+        if len(body) < MAX_BODY and not (body and body[-1] in ctrl):
+            row.append(eos)
+        rows.append(row)
+    return rows
+
+
+def opening_template(events, vocab, tracks_to_generate, bars_to_generate, *, content=None, keep=1):
+    """The template that keeps the opening of every note span and lets the
+    model finish it: each note span's row is the first `keep` body tokens of
+    its content (all of them when it holds fewer); control spans are free.
+    keep: one int in 0..98, or one per note span in mask order.  content: as
+    rhythm_template's."""
+    bodies, codes = _template_bodies(events, vocab, tracks_to_generate, bars_to_generate, content)
+    n_note = sum(1 for c in codes if c == 0)
+    ks = list(keep) if isinstance(keep, (list, tuple, np.ndarray)) else [keep] * n_note
+    if len(ks) != n_note:
+        raise ValueError("keep: one int, or one per note span (%d)" % n_note)
+    for x in ks:
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or not 0 <= x <= MAX_BODY:
+            raise ValueError("keep must be an int in 0..%d (got %r)" % (MAX_BODY, x))
+    rows, it = [], iter(ks)
+    for body, code in zip(bodies, codes):
+        rows.append(list(body[:int(next(it))]) if code == 0 else None)
+    return rows

@@ -830,6 +830,36 @@ def logprob_rows(logits, row, code, keep, ban_idx, ban_bits, ids, out_lp, out_ar
          _p(ban_idx), _p(ban_bits), K, _p(ids), _p(out_lp), _p(out_arg), _stream())
 
 
+TPL_LEN = 99      # entries of one tape row: the 98 body draws the span cap keeps and the draw after them
+TPL_FREE = -1     # tape entry: the draw is free
+TPL_PITCH = -2    # tape entry: any pitch token, and only a pitch token
+
+
+def logits_template(logits, state, cls, tape):
+    """Infill templates ahead of a grammar step (smer_logits_template; after
+    logits_ban and logprob_stage, if any): for every request r that is not
+    done, e = tape[r, mask index, span length - 1] rewrites logits row 2r + 1:
+    a token 0 <= e < V puts 0 at e and -100 at every other entry, TPL_PITCH
+    puts -100 at every entry that is no pitch token (bit 2 of cls), TPL_FREE
+    (or a mask index / length outside the tape, or an entry >= V) leaves the
+    row alone.  logits float32 [>= 2R, V <= 512] (rows contiguous), state
+    int32 [R, nst] (the grammar state), cls uint8 [V] (the grammar step's
+    class table), tape int16 [R, max_masks, L]."""
+    R, nst = state.shape
+    V = logits.shape[1]
+    for t, dt in ((logits, torch.float32), (state, torch.int32), (cls, torch.uint8), (tape, torch.int16)):
+        if t.dtype != dt or t.device != logits.device:
+            raise RuntimeError("logits_template: expected %s on the logits' device" % dt)
+    if not (state.is_contiguous() and cls.is_contiguous() and tape.is_contiguous()) or \
+            logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError("logits_template: expected contiguous tables and logits rows")
+    if logits.shape[0] < 2 * R or tape.dim() != 3 or tape.shape[0] != R or tape.shape[1] < 1 or \
+            tape.shape[2] < 1 or cls.dim() != 1 or cls.shape[0] != V or not 1 <= V <= 512 or nst < 9:
+        raise RuntimeError("logits_template: shape mismatch")
+    call("smer_logits_template", R, V, _p(logits), _ld(logits), _p(state), nst, _p(cls), _p(tape),
+         tape.shape[1], tape.shape[2], _stream())
+
+
 # ---------------------------------------------------------------------------
 def layernorm(x, gamma, beta, y, mean, rstd, eps=1e-5):
     M, N = x.shape
