@@ -53,6 +53,8 @@
  *                        full forward, each at its own grammar state
  *   smer_logits_template infill templates: the given opening of a span (a
  *                        token, or any pitch) forced ahead of any grammar step
+ *   smer_bar_clock       the bar clock: a note span never passes the bar line
+ *                        and ends only on it, ahead of any grammar step
  *   smer_layernorm_*   residual LayerNorm, eps 1e-5 (transformer.py:392,395,
  *                        462,466,469; final norms 274-275, 329-330)
  *   smer_embed_*         embedding gather x sqrt(d) + sinusoidal PE + dropout
@@ -528,6 +530,34 @@ int smer_logprob_rows(int N, int V, int nrows, const float* logits, long ldl, co
 int smer_logits_template(int R, int V, float* logits, long ldl, const int32_t* state, int nst,
                          const uint8_t* cls, const int16_t* tape, int max_masks, int L,
                          smer_stream_t stream);
+/* Bar clock (not a reference operation): a note span fills its bar exactly.
+ * Run between the vocabulary projection and any smer_grammar_*_step entry on
+ * the same logits, state, targets, max_masks, out_tok, cap and cls -- after
+ * smer_logits_ban and smer_logprob_stage, before smer_logits_template.  All
+ * lengths are integers in sixteenths: units uint8 [V] is each token's length (0:
+ * not a duration), bar_len int32 [R] each request's bar length L (0: the
+ * request has no clock), clock int32 [R, 8] the words T (cursor), P (previous
+ * group's length), A (pending duration sum), G | S << 1 (a duration group is
+ * open, a 'sep' is pending) and seen; the caller zeroes it once per decode.
+ * For a request that is not done, with c = state word 7 (the token count): if
+ * the span length (state word 2) is 1 the five words become 0; else, if c ==
+ * seen + 1 and 1 <= c <= cap, the clock advances by out_tok[r * cap + c - 1] &
+ * 0xFFFF (when below V): a duration token (cls bit 4) of u units sets A += u,
+ * G = 1; any other token first closes an open group (T = base + A, P = A, A =
+ * S = G = 0, with base = S ? T - P : T) and then, if it is 'sep' (cls bit 8),
+ * sets S = 1.  Then seen = c.  With end = base + A, a row that is not done, has
+ * L > 0, a mask index in 0..max_masks-1 whose target is 0 (a note span) and c
+ * <= cap stores -100.f at logits[(2r+1) * ldl + v] for every v < V that is
+ *   a duration of u units with end + u > L;
+ *   a pitch, 'continue' or 'rest' (cls bits 2, 1, 16) with end >= L;
+ *   'sep' with (G ? base : T - P) >= L;
+ *   eos or a control token (cls bit 32) with end != L.
+ * Done requests write nothing at all.  V <= 512.  Status return, no
+ * allocation, no synchronisation. */
+int smer_bar_clock(int R, int V, float* logits, long ldl, const int32_t* state, int nst,
+                   const int8_t* targets, int max_masks, const int32_t* out_tok, int cap,
+                   const uint8_t* cls, const uint8_t* units, int eos, const int32_t* bar_len,
+                   int32_t* clock, smer_stream_t stream);
 
 int smer_layernorm_fwd(int dtype, int M, int N, const void* x, long ldx,
                        const float* gamma, const float* beta, float eps,

@@ -1300,3 +1300,107 @@ extern "C" int smer_logits_template(int R, int V, float* logits, long ldl, const
   SMER_CHECK_LAUNCH("smer_logits_template");
   return SMER_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Bar clock (fill_bar=): a note span never passes the bar line and can end
+// only when its bar is exactly full.  The first stateful constraint: the node
+// follows the tokens drawn, in integers (sixteenths), by the cursor rule of
+// codec._Writer -- consecutive duration tokens sum into one group, any other
+// token closes an open group, 'sep' rewinds the next group by the previous
+// one (generation._BarClock is the host mirror, word for word).
+//   clock int32 [R, 8]: T cursor, P previous group's length, A pending
+//   duration sum, flags G | S << 1 (a group is open, a 'sep' is pending), seen
+//   (the ST_COUNT the clock has followed); words 5..7 unused;
+//   units uint8 [V]: a token's length in sixteenths (0: no duration);
+//   bar_len int32 [R]: the bar's length L, 0 = the request has no clock.
+// Per step, for a request that is not done, with c = ST_COUNT: at the start of
+// a span (ST_LEN == 1) the clock is cleared; else, if c == seen + 1 and 1 <= c
+// <= cap, it advances by out_tok[r, c - 1] (the token the grammar kernel
+// emitted in the step before; bit 16 is the redraw-failure flag); then seen =
+// c, so a second launch in one step changes nothing.  With base = S ? T - P : T
+// and end = base + A, an active row (not done, L > 0, a note span's mask, c <=
+// cap) stores -100.f over
+//   a duration of u units iff end + u > L,
+//   a pitch, 'continue' and 'rest' iff end >= L (each needs a sixteenth after it),
+//   'sep' iff (G ? base : T - P) >= L (where the group after it would start),
+//   <eos> and the control tokens (which end a note span) iff end != L.
+// Both grammar kernels form x = keep[i] ? logit[i] : -100.f, so a kept logit
+// stored as exactly -100.f is a masked one (logits_ban_kernel's argument).
+// One wave per request, 8 tokens per lane (V <= 512), logits_ban_kernel's
+// layout.  The lookups are clamped, not guarded, and only the stores are
+// predicated; a done row stores nothing at all, and a row whose count has run
+// past out_tok (c > cap: its clock missed a token) stores no logit.  The
+// candidates' class and unit bytes do not depend on the state, so their loads
+// run beside the state -> out_tok -> class / units chain.
+// ---------------------------------------------------------------------------
+namespace {
+constexpr int CK_WORDS = 8;
+}  // namespace
+
+__global__ __launch_bounds__(64) void bar_clock_kernel(
+    int R, int V, float* __restrict__ logits, long ldl, const int32_t* __restrict__ state, int nst,
+    const int8_t* __restrict__ targets, int max_masks, const int32_t* __restrict__ out_tok, int cap,
+    const uint8_t* __restrict__ cls, const uint8_t* __restrict__ units, int eos,
+    const int32_t* __restrict__ bar_len, int32_t* __restrict__ clock) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int32_t* st = state + (long)r * nst;
+  const int done = st[ST_DONE], midx = st[ST_MIDX], len = st[ST_LEN], c = st[ST_COUNT];
+  int32_t* ck = clock + (long)r * CK_WORDS;
+  const int cv = ck[lane & (CK_WORDS - 1)];  // lane k <- word k, then broadcast
+  int T = __shfl(cv, 0, 64), P = __shfl(cv, 1, 64), A = __shfl(cv, 2, 64);
+  const int fl = __shfl(cv, 3, 64), seen = __shfl(cv, 4, 64);
+  int G = fl & 1, S = (fl >> 1) & 1;
+  const int L = bar_len[r];
+  const int tgt = (int)targets[(long)r * max_masks + min(max(midx, 0), max_masks - 1)];
+  const int tok = out_tok[(long)r * cap + min(max(c - 1, 0), cap - 1)] & 0xFFFF;
+  const int tcls = cls[min(tok, V - 1)], tun = units[min(tok, V - 1)];
+  if (len == 1) {
+    T = P = A = G = S = 0;
+  } else if (c == seen + 1 && c >= 1 && c <= cap && tok < V) {
+    if (tcls & C_DUR) {
+      A += tun;
+      G = 1;
+    } else {
+      if (G) {  // _Writer.flush
+        T = (S ? T - P : T) + A;
+        P = A;
+        A = S = G = 0;
+      }
+      if (tcls & C_SEPSTR) S = 1;
+    }
+  }
+  if (!done && lane < 5)
+    ck[lane] = lane == 0 ? T : lane == 1 ? P : lane == 2 ? A : lane == 3 ? (G | (S << 1)) : c;
+  const int base = S ? T - P : T, end = base + A, sep_base = G ? base : T - P;
+  const bool on = !done && L > 0 && midx >= 0 && midx < max_masks && tgt == 0 && c <= cap;
+  float* lr = logits + (long)(2 * r + 1) * ldl;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int i = lane * 8 + j, ic = min(i, V - 1);
+    const int cb = cls[ic], u = units[ic];
+    const bool ban = ((cb & C_DUR) && end + u > L) ||
+                     ((cb & (C_PITCH | C_CONT | C_RESTSTR)) && end >= L) ||
+                     ((cb & C_SEPSTR) && sep_base >= L) ||
+                     (((cb & C_CTRL) || i == eos) && end != L);
+    if (on && ban && i < V) lr[i] = -100.f;
+  }
+}
+
+// Graph-capturable, no allocation, no synchronisation.  logits, state,
+// targets, out_tok and cls are the grammar entry's own arguments (request r's
+// row at (2r+1) * ldl); the caller zeroes `clock` once per decode.
+extern "C" int smer_bar_clock(int R, int V, float* logits, long ldl, const int32_t* state, int nst,
+                              const int8_t* targets, int max_masks, const int32_t* out_tok, int cap,
+                              const uint8_t* cls, const uint8_t* units, int eos, const int32_t* bar_len,
+                              int32_t* clock, smer_stream_t stream) {
+  SMER_REQUIRE(R > 0 && V > 0 && V <= 512 && nst >= 9 && max_masks > 0 && cap > 0,
+               "smer_bar_clock: sizes (V <= 512)");
+  SMER_REQUIRE(ldl >= V, "smer_bar_clock: logits row stride");
+  SMER_REQUIRE(eos >= 0 && eos < V, "smer_bar_clock: token ids");
+  SMER_REQUIRE(logits && state && targets && out_tok && cls && units && bar_len && clock,
+               "smer_bar_clock: null pointer");
+  hipLaunchKernelGGL(bar_clock_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, R, V, logits, ldl, state,
+                     nst, targets, max_masks, out_tok, cap, cls, units, eos, bar_len, clock);
+  SMER_CHECK_LAUNCH("smer_bar_clock");
+  return SMER_OK;
+}

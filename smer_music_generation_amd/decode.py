@@ -132,12 +132,16 @@ class _GrammarGraph:
     tpl: the graph runs smer_logits_template in front of the grammar kernel
     (after the score stage, which therefore sees the row the model gave), on
     g_tape int16 [R, nm, TPL_LEN].
+    bar: the graph runs smer_bar_clock between the score stage and the
+    template kernel, on g_barlen int32 [R] (0: the request has no clock),
+    g_units uint8 [V] and g_clock int32 [R, CLOCK_WORDS], which follows the
+    tokens of g_out and is zeroed per call as g_out is.
     Construction allocates; load() writes a call's inputs, before the capture
     and before every later call alike."""
 
     def __init__(self, sess, key, mode, nm, keep_shape, cls_shape, *, eos, m0, lookahead, max_span,
-                 use_ring, ban, score, tpl=False):
-        self.key, self.mode, self.ban, self.score, self.tpl = key, mode, ban, score, tpl
+                 use_ring, ban, score, tpl=False, bar=False):
+        self.key, self.mode, self.ban, self.score, self.tpl, self.bar = key, mode, ban, score, tpl, bar
         self.graph = None
         R, cap, dev = sess.R, sess.Tmax, sess.dev
 
@@ -163,6 +167,10 @@ class _GrammarGraph:
             b["g_logp"] = zeros(R, cap, dtype=torch.float64)
         if tpl:
             b["g_tape"] = torch.full((R, nm, ops.TPL_LEN), ops.TPL_FREE, dtype=torch.int16, device=dev)
+        if bar:
+            b["g_barlen"] = zeros(R)
+            b["g_units"] = zeros(cls_shape, dtype=torch.uint8)
+            b["g_clock"] = zeros(R, ops.CLOCK_WORDS)
         # live counts: the step's grammar kernel publishes its count into a
         # pinned host ring itself (no per-step memset / D2H copy between the
         # replays); SMER_GRAMMAR_RING=0: memset + copy per step (A/B)
@@ -172,7 +180,7 @@ class _GrammarGraph:
         self.gargs = dict(eos=eos, m0=m0, trash_pos=sess.Tmax - 1, max_span=max_span,
                           ring=self.ring if use_ring else None)
 
-    def load(self, st, tg, keep, cls, src_len, ban=None, sampler=None, tape=None):
+    def load(self, st, tg, keep, cls, src_len, ban=None, sampler=None, tape=None, bar=None):
         """Write one call's inputs (host arrays) and clear its outputs."""
         b = self.bufs
 
@@ -188,6 +196,10 @@ class _GrammarGraph:
             up("g_banbits", ban[1].view(np.int32))
         if self.tpl:
             up("g_tape", tape)
+        if self.bar:
+            up("g_barlen", bar[0])
+            up("g_units", bar[1])
+            b["g_clock"].zero_()
         if self.mode != "greedy":
             up("g_reject", np.ascontiguousarray(sampler.reject, dtype=np.uint8))
             up("g_mt_rows" if self.mode == "rows" else "g_mt", sampler.mt.view(np.int32))
@@ -208,6 +220,9 @@ class _GrammarGraph:
             ops.logits_ban(logits, state, b["g_banmask"], b["g_banbits"])
         if self.score:  # the row's log-softmax while the row exists, the drawn token's entry after
             ops.logprob_stage(logits, state, targets, keep, b["g_lp_row"], b["g_lp_stage"])
+        if self.bar:  # the bar clock: follows the token the step before drew, then bans by the cursor
+            ops.bar_clock(logits, state, targets, b["g_out"], b["g_cls"], b["g_units"], b["g_barlen"],
+                          b["g_clock"], eos=self.gargs["eos"])
         if self.tpl:  # the given opening of a span: forced after the score saw the model's row
             ops.logits_template(logits, state, b["g_cls"], b["g_tape"])
         if self.mode == "greedy":
@@ -285,7 +300,7 @@ class DecodeSession:
         self._pe_ptr = model.pos_enc.pe.data_ptr()
         self.plan = None      # the _StepPlan of the last _run (None: no step has run yet)
         self._side = None     # the second chain's stream, made on first use
-        self._graphs = {}     # name ("greedy", "stream+ban", "rows+ban+score", ..) -> _GrammarGraph
+        self._graphs = {}     # name ("greedy", "stream+ban", "rows+ban+bar+tpl+score", ..) -> _GrammarGraph
         self._greedy = None   # the _GrammarGraph of the last call
         self.phase_s = {}     # host seconds of the last device loop's phases (bench / probes)
 
@@ -636,7 +651,7 @@ class DecodeSession:
         return t_b - t_a, time.perf_counter() - t_b
 
     def sampled_decode(self, spans, keep, reject, cls, *, eos, m0, lookahead=3, max_span=100,
-                       t=1.0, p=None, seeds=None, bans=None, score=False, templates=None):
+                       t=1.0, p=None, seeds=None, bans=None, score=False, templates=None, bars=None):
         """The sampled infill loop (the reference's sampling(): softmax with
         temperature, then weighted_sampling or, with p, nucleus, and its
         redraws) on device: each step is one replay of the captured
@@ -653,7 +668,7 @@ class DecodeSession:
         request form of the kernel (smer_grammar_sample_step_rows), the "rows"
         graph kept beside the unseeded "stream" one, and np.random is neither
         read nor written.  Other seeds replay that graph.
-        bans, score, templates: as greedy_decode's; the scores are taken at
+        bans, score, templates, bars: as greedy_decode's; the scores are taken at
         t = 1 over the whole masked distribution, whatever t and p are.
         Returns a DecodeResult whose `fails` flag the ids whose redraws ran
         out."""
@@ -692,7 +707,7 @@ class DecodeSession:
             mt_h[624] = int(st0[2])
         res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead, max_span=max_span,
                                    sampler=_Sampler(reject, mt_h, tp_h, seeds is not None), bans=bans,
-                                   score=score, templates=templates)
+                                   score=score, templates=templates, bars=bars)
         if seeds is None:  # the stream goes on where the device left it
             m = self._greedy.bufs["g_mt"].cpu().numpy().view(np.uint32)
             np.random.set_state(("MT19937", m[:624].copy(), int(m[624]), st0[3], st0[4]))
@@ -700,7 +715,7 @@ class DecodeSession:
                             fails=[[(x >> 16) & 1 for x in q] for q in res.ids])
 
     def greedy_decode(self, spans, keep, cls, *, eos, m0, lookahead=3, max_span=100, bans=None,
-                      score=False, templates=None):
+                      score=False, templates=None, bars=None):
         """Run the greedy infill loop of `spans` (generation._Span, one per
         request slot 0..len-1, freshly started, sources prefilled) entirely
         on device: each step is one replay of the captured decoder step +
@@ -725,12 +740,22 @@ class DecodeSession:
         extra node (smer_logits_template) forces the items from a tape that is
         device data refreshed per call: other templates replay that graph, and
         a span without one gets an all-free tape.  None (or all None): the
-        graphs without that node, as ever."""
+        graphs without that node, as ever.
+        bars (the bar clock): per span its bar length in sixteenths, 0 for a
+        span without a clock.  With any span clocked the call replays the
+        '+bar' graph of its mode (after '+ban', before '+tpl'), whose extra
+        node (smer_bar_clock) sits between the score stage and the template
+        kernel; the lengths and the unit table are device data refreshed per
+        call, and the clock words are zeroed per call.  None: the graphs
+        without that node, as ever (generation passes None when no request
+        sets fill_bar; a list of zeros runs the node on rows it leaves alone,
+        which is how tools/barclock_bench.py prices it)."""
         return self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
-                                    max_span=max_span, bans=bans, score=score, templates=templates)
+                                    max_span=max_span, bans=bans, score=score, templates=templates,
+                                    bars=bars)
 
     def _grammar_decode(self, spans, keep, cls, *, eos, m0, lookahead, max_span, sampler=None, bans=None,
-                        score=False, templates=None):
+                        score=False, templates=None, bars=None):
         """greedy_decode, or with `sampler` (a _Sampler) sampled_decode."""
         R = len(spans)
         if R > self.R:
@@ -747,7 +772,7 @@ class DecodeSession:
         cap = self.Tmax
         st = np.zeros((self.R, self.N_STATE), dtype=np.int32)
         tg = np.zeros((self.R, nm), dtype=np.int8)
-        from .generation import _target_code  # late import: generation imports decode
+        from .generation import _target_code, unit_table  # late import: generation imports decode
         feeds = []
         for r, sp in enumerate(spans):
             st[r, 2] = 1                      # this_in = [m_0]
@@ -790,6 +815,22 @@ class DecodeSession:
             ban = (bm_h, bb_h)
             gkey += (K,)
         gname = mode if ban is None else mode + "+ban"
+        # the bar clock: a graph of its own again, whose lengths, unit table and
+        # clock words are its own buffers; a call without any replays the
+        # graphs that never held the node
+        bar = None
+        if bars is not None:
+            if len(bars) != R:
+                raise ValueError("one bars entry per span")
+            if keep.shape[1] > 512:
+                raise ValueError("bars: the device path serves vocabularies up to 512 tokens")
+            bl_h = np.zeros(self.R, dtype=np.int32)
+            bl_h[:R] = [int(x) for x in bars]
+            if bl_h.min() < 0 or bl_h.max() > 255:
+                raise ValueError("bars: a bar length is 0 (no clock) or 1..255 sixteenths")
+            bar = (bl_h, np.array(unit_table(spans[0].v), dtype=np.uint8))  # (a writable copy: the table is read-only)
+            gname += "+bar"
+            gkey += ("bar",)
         # infill templates: once more a graph of its own, whose tape is device
         # data; a call without any replays the graphs that never held the node
         tape = None
@@ -814,7 +855,7 @@ class DecodeSession:
                 raise ValueError("score: the device path scores vocabularies up to 512 tokens")
             gname += "+score"
             gkey += ("score",)
-        inputs = (st, tg, keep, cls, self.src_len, ban, sampler, tape)
+        inputs = (st, tg, keep, cls, self.src_len, ban, sampler, tape, bar)
         gg = self._graphs.get(gname)
         if gg is not None and gg.key == gkey:
             # the captured step + grammar graph of an earlier call with the
@@ -829,7 +870,7 @@ class DecodeSession:
             self._graphs.pop(gname, None)  # a stale graph's buffers go before the new ones are made
             gg = _GrammarGraph(self, gkey, mode, nm, keep.shape, cls.shape, eos=eos, m0=m0,
                                lookahead=lookahead, max_span=max_span, use_ring=use_ring,
-                               ban=ban is not None, score=score, tpl=tape is not None)
+                               ban=ban is not None, score=score, tpl=tape is not None, bar=bar is not None)
             gg.load(*inputs)
             warm_s, capture_s = self._capture_grammar(gg)
             self._graphs[gname] = gg

@@ -37,6 +37,10 @@ Differences, all opt-in keywords with reference defaults:
     opening of a span is given -- token by token, or as ANY_PITCH, "a pitch of
     the model's choice" -- and the model writes the rest (`rhythm_template`
     keeps a bar's rhythm, `opening_template` its first tokens).
+  * `fill_bar=False` on the same three: True makes every infilled note span
+    fill its bar exactly (a clock in sixteenths follows the tokens drawn and
+    masks what would pass the bar line or end the span beside it);
+    `bar_units` and `bar_fill` are its public helpers.
 The grammar state machine, the -100 logit masking, the float64 softmax and
 the numpy RNG consumption are the reference's, so with the same
 `np.random` state the same token ids come out.
@@ -550,11 +554,147 @@ def grammar_tables(vocab, all_controls):
     return keep, cls
 
 
+# --------------------------------------------------------------------------
+# the bar clock (`fill_bar=`): how much of its bar a note span has filled
+# --------------------------------------------------------------------------
+BAR_UNITS = {'whole': 16, 'half': 8, 'quarter': 4, 'eighth': 2, 'sixteenth': 1}  # in sixteenths
+_UNIT_CACHE = {}
+
+
+def unit_table(vocab):
+    """uint8 [V]: the length of every token in sixteenths (BAR_UNITS for the
+    duration tokens, 0 for every other token)."""
+    hit = _UNIT_CACHE.get(id(vocab))
+    if hit is None or hit[0] is not vocab:
+        u = np.zeros(vocab.vocab_size, dtype=np.uint8)
+        for i in vocab.duration_only_indices:
+            u[i] = BAR_UNITS.get(vocab.index2char(i), 0)
+        u.setflags(write=False)
+        hit = _UNIT_CACHE[id(vocab)] = (vocab, u)
+    return hit[1]
+
+
+def _class_table(vocab, all_controls):
+    """grammar_tables' cls uint8 [V] alone."""
+    return grammar_tables(vocab, all_controls)[1]
+
+
+def bar_units(events):
+    """The length L of a bar of `events` in sixteenths: bar_duration /
+    name_to_time['sixteenth'] of durations_for_events (16 for 4/4, 12 for 3/4
+    and 6/8).  A length that is no integer in 1..255 raises ValueError."""
+    try:
+        name_to_time, _, _, bar_duration = durations_for_events(events)
+        L = float(bar_duration) / float(name_to_time['sixteenth'])
+    except (KeyError, IndexError, TypeError, ValueError, ZeroDivisionError):
+        raise ValueError("fill_bar: the events carry no usable time signature") from None
+    if not (np.isfinite(L) and L == int(L) and 1 <= L <= 255):
+        raise ValueError("fill_bar: a bar of %r sixteenths (an integer in 1..255 is needed)" % (L,))
+    return int(L)
+
+
+class _BarClock:
+    """The cursor of one note span in sixteenths (the `_Writer` rule of
+    codec.py: consecutive duration tokens sum into one group, 'sep' rewinds by
+    the previous group), and what it bans so that the span never passes the
+    bar line and can end only on it.  T cursor, P the previous group's length,
+    A the pending duration sum, G a duration group is open, S a 'sep' is
+    pending.  cls: grammar_tables' class bits per token, units: unit_table.
+    Pure: integers in, a boolean row out."""
+    __slots__ = ("L", "cls", "units", "T", "P", "A", "G", "S")
+
+    def __init__(self, L, cls, units):
+        self.L, self.cls, self.units = int(L), np.asarray(cls), np.asarray(units)
+        self.T = self.P = self.A = self.G = self.S = 0
+
+    def reset(self):
+        self.T = self.P = self.A = self.G = self.S = 0
+
+    @property
+    def base(self):
+        return self.T - self.P if self.S else self.T
+
+    @property
+    def end(self):
+        return self.base + self.A
+
+    @property
+    def cursor(self):
+        """Where the span's cursor stands once an open group is closed (a
+        'sep' that no group follows rewinds nothing)."""
+        return self.end if self.G else self.T
+
+    def advance(self, cls_bits, units):
+        """Follow one emitted token: its class bits and its length."""
+        if cls_bits & 4:  # a duration token: the group grows
+            self.A += int(units)
+            self.G = 1
+            return
+        if self.G:  # any other token first closes an open group (_Writer.flush)
+            self.T, self.P = self.base + self.A, self.A
+            self.A = self.S = self.G = 0
+        if cls_bits & 8:
+            self.S = 1
+
+    def advance_id(self, idx):
+        self.advance(int(self.cls[idx]), int(self.units[idx]))
+
+    def banned(self, vocab):
+        """Boolean [V]: the candidates the clock bans in its current state."""
+        L, cls, units = self.L, self.cls, self.units
+        base, end = self.base, self.end
+        ban = np.zeros(vocab.vocab_size, dtype=bool)
+        dur = (cls & 4) != 0
+        ban[dur] = end + units[dur].astype(np.int64) > L
+        if end >= L:  # each needs at least a sixteenth after it
+            ban[(cls & (1 | 2 | 16)) != 0] = True
+        if (base if self.G else self.T - self.P) >= L:
+            ban[(cls & 8) != 0] = True
+        if end != L:
+            ban[(cls & 32) != 0] = True
+            ban[vocab.eos_index] = True
+        return ban
+
+
+def bar_fill(vocab, tokens):
+    """(final cursor, peak end) in sixteenths of one span's tokens (strings or
+    ids; m_0 and <eos> count as any other non-duration token): where the
+    `_Writer` rule leaves the cursor once the last group is closed, and the
+    furthest a group reached on the way."""
+    table = vocab._char2idx
+    cls = np.zeros(vocab.vocab_size, dtype=np.uint8)
+    cls[vocab.duration_only_indices] |= 4
+    cls[vocab.sep_indices] |= 8
+    ck = _BarClock(255, cls, unit_table(vocab))
+    peak = 0
+    for x in (tokens.tolist() if isinstance(tokens, np.ndarray) else tokens):
+        ck.advance_id(table[x] if isinstance(x, str) else int(x))
+        peak = max(peak, ck.end)
+    return ck.cursor, peak
+
+
+def _check_fill_bar(fill_bar, n=None):
+    """Validated `fill_bar` of a call: a bool (n None: the plugin call), or
+    with n requests a bool for all of them or one per request.  Raises
+    ValueError; touches neither the model nor np.random."""
+    def one(x):
+        if not isinstance(x, (bool, np.bool_)):
+            raise ValueError("fill_bar must be True or False (got %r)" % (x,))
+        return bool(x)
+    if isinstance(fill_bar, (list, tuple, np.ndarray)):
+        if n is None:
+            raise ValueError("fill_bar is one bool here")
+        if len(fill_bar) != n:
+            raise ValueError("fill_bar: one bool, or one per request (%d)" % n)
+        return [one(x) for x in fill_bar]
+    return one(fill_bar) if n is None else [one(fill_bar)] * n
+
+
 class _Span:
     """Decoding state of one request: mask index, span tokens, grammar flags."""
 
     def __init__(self, vocab, src, mask_target, all_controls, no_whole, greedy, logger, t=1.0,
-                 p=None, rng=np.random, bans=None, score=False, template=None):
+                 p=None, rng=np.random, bans=None, score=False, template=None, bar_len=0):
         self.v = vocab
         self.t = t
         self.p = p
@@ -570,6 +710,13 @@ class _Span:
         # infill template (_check_template's rows): per mask None or the items
         # of the span's opening, token ids or TPL_PITCH; None: no template
         self.tpl = template
+        # the bar clock (fill_bar=): bar_len is the bar's length in sixteenths
+        # (0: off); the clock follows the tokens of the note span being drawn,
+        # and `fill` receives (cursor, bar_len) of every note span that ends
+        self.bar_len = int(bar_len)
+        self.clock = _BarClock(bar_len, _class_table(vocab, all_controls), unit_table(vocab)) \
+            if self.bar_len else None
+        self.fill = []
         self.src = src
         self.mask_target = mask_target
         self.all_controls = set(int(c) for c in all_controls)
@@ -591,6 +738,24 @@ class _Span:
         self.this_in = [self.m0]
         self.this_ev = ['m_0']
         self.in_pitch = self.in_rest = self.in_sep = self.in_continue = False
+        if self.clock is not None:
+            self.clock.reset()
+
+    def _note_span(self):
+        return self.mask_idx < len(self.mask_target) and _target_code(self.mask_target[self.mask_idx]) == 0
+
+    def clock_ban(self):
+        """Boolean [V]: what the bar clock bans for the draw about to be made
+        (note spans only), or None."""
+        if self.clock is None or self.done or not self._note_span():
+            return None
+        return self.clock.banned(self.v)
+
+    def _span_ends(self):
+        """A span ended (this_in still holds it, the dropped last token
+        included): under the bar clock a note span reports its cursor."""
+        if self.clock is not None and self._note_span():
+            self.fill.append((bar_fill(self.v, self.this_in[1:-1])[0], self.bar_len))
 
     def prefix(self):
         return self.tgt_inp + self.this_in
@@ -635,6 +800,9 @@ class _Span:
 
     def _draw_id(self, logit, check, failmsg, flags):
         ban = self.ban()
+        cb = self.clock_ban()
+        if cb is not None:  # (_draw scores from the unclocked ban: what score_infill gives)
+            ban = cb if ban is None else ban | cb
         if ban is not None:  # (an unconstrained draw is the call it always was)
             flags = dict(flags, ban=ban)
         force = self.forced()
@@ -698,6 +866,8 @@ class _Span:
         eos, ctrl = self.eos, self.all_controls
         this_in, this_ev = self.this_in, self.this_ev
         for idx in seq:
+            if self.clock is not None:
+                self.clock.advance_id(idx)
             if idx in ctrl:
                 this_in += [idx, eos]
                 this_ev += [i2c(idx), '<eos>']
@@ -705,6 +875,7 @@ class _Span:
                 this_in.append(idx)
                 this_ev.append(i2c(idx))
             if this_in[-1] == eos or len(this_in) >= 100:
+                self._span_ends()
                 self.tgt_inp.extend(this_in[:-1])
                 self.total.extend(this_ev[:-1])
                 self.mask_idx += 1
@@ -728,6 +899,8 @@ class _Span:
             self.in_sep = True
         if ev == 'rest':
             self.in_rest = True
+        if self.clock is not None:
+            self.clock.advance_id(idx)
         if idx in self.all_controls:
             self.this_in += [idx, self.eos]
             self.this_ev += [ev, '<eos>']
@@ -735,6 +908,7 @@ class _Span:
             self.this_in.append(idx)
             self.this_ev.append(ev)
         if self.this_in[-1] == self.eos or len(self.this_in) >= 100:
+            self._span_ends()
             self.tgt_inp.extend(self.this_in[:-1])
             self.total.extend(self.this_ev[:-1])
             self.mask_idx += 1
@@ -790,7 +964,7 @@ class _Precision:
 def generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
                    bars_to_generate, *, greedy=False, use_kv_cache=True, stats=None,
                    precision="fp32", warm=True, device_grammar=True, t=1.0, p=None, variations=None,
-                   seed=None, pitches=None, logprobs=False, rank=False, template=None):
+                   seed=None, pitches=None, logprobs=False, rank=False, template=None, fill_bar=False):
     """`generation.py:468-696`.  Returns (restored '<U9' tokens,
     mask_track_names, mask_bar_names) or None (nothing masked / on error,
     after printing it, as the reference does).  `stats` (a dict, opt-in)
@@ -900,12 +1074,35 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
     variations all takes carry the template.  On the device the step graphs
     named '+tpl' force the items from a tape (smer_logits_template); a call
     without a template replays the graphs it always did.  _check_template
-    lists what raises ValueError, before the model or np.random is touched."""
+    lists what raises ValueError, before the model or np.random is touched.
+    fill_bar: False (default): today's behaviour bit for bit.  True: every note
+    span (mask target 'r') fills its bar exactly -- it never passes the bar
+    line and can end only on it; control spans are untouched.  The bar's length
+    L is bar_units(events) sixteenths, and a clock (_BarClock: the cursor rule
+    of codec._Writer in integers) follows the tokens drawn.  It is a masked
+    draw, as `pitches` is: after the widening, the grammar mask and the pitch
+    ban, and before the template and the division by t, the logits of the
+    candidates the clock bans become -100.0 -- a duration that would cross the
+    bar line; a pitch, 'continue' or 'rest' at a full bar; a 'sep' that would
+    rewind to the bar line; <eos> and the control tokens while the bar is not
+    full.  The draw, the redraw loop and what they take from the stream are
+    those of any other step, and every path -- device, host loop,
+    use_kv_cache=False -- agrees.  logprobs=True reports what it reports
+    without the keyword (the model, the grammar mask and the pitch ban: the
+    number score_infill gives).  Under fill_bar a template is validated
+    against the clock as well.  A span cut by the 100-token cap cannot be
+    forced full: it is reported as it is.  `stats` receives
+    'bar_fill': per take, one (cursor, L) per note span.  On the device the
+    step graphs named '+bar' run the clock (smer_bar_clock); a call without
+    the keyword replays the graphs it always did.  Anything but a bool, or a
+    bar whose length is no integer in 1..255 sixteenths, raises ValueError
+    before the model or np.random is touched."""
     t, p = _check_tp(t, p)
     n = None if variations is None else _check_variations(variations)
     seeds = _check_seed(seed, None, n)
     allowed = _check_pitches(pitches, tracks_to_generate)
     score = _check_score(logprobs, rank, variations)
+    bar_len = bar_units(events) if _check_fill_bar(fill_bar) else 0
     tpl = None
     if template is not None:
         try:
@@ -914,7 +1111,7 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
         except Exception as e:  # reference behaviour (generation.py:695-696): what the call itself would print
             print(e)
             return None
-        tpl = _check_template(template, vocab, q[0], q[3], all_controls, q[4], bans)
+        tpl = _check_template(template, vocab, q[0], q[3], all_controls, q[4], bans, bar_len)
     if stats is not None:
         stats["seeds"] = seeds
         stats["pitches"] = allowed
@@ -929,9 +1126,12 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
                                            t=t, p=p, variations=[n],
                                            seed=None if seeds is None else [seeds[0]],
                                            pitches=[allowed], logprobs=score, rank=bool(rank),
-                                           template=None if template is None else [template])
+                                           template=None if template is None else [template],
+                                           fill_bar=[bool(bar_len)])
                 if stats is not None:
                     stats["steps"] = st["steps"]
+                    if bar_len:
+                        stats["bar_fill"] = st["bar_fill"]
                     if score:
                         stats["logprobs"], stats["scores"] = st["logprobs"], st["scores"]
                     if rank:
@@ -944,7 +1144,7 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
         return _generation_all(model, events, device, vocab, logger, all_controls,
                                tracks_to_generate, bars_to_generate, greedy, use_kv_cache, stats,
                                warm, device_grammar, t, p, None if seeds is None else seeds[0],
-                               allowed, score, tpl)
+                               allowed, score, tpl, bar_len)
 
 
 _REJECT_CACHE = {}
@@ -980,6 +1180,14 @@ def _device_templates(spans):
     the graphs without the template kernel)."""
     tpls = [sp.tpl for sp in spans]
     return tpls if any(x is not None for x in tpls) else None
+
+
+def _device_bars(spans):
+    """`bars=` of DecodeSession.greedy_decode / sampled_decode: per span its
+    bar length in sixteenths (0: no clock); None when no span has one (the
+    call then replays the graphs without the clock kernel)."""
+    bars = [sp.bar_len for sp in spans]
+    return bars if any(bars) else None
 
 
 def _replay(spans, res, logger, sampled=True):
@@ -1026,7 +1234,7 @@ def _sampled_on_device(sess, st, vocab, all_controls, logger, seed=None):
     res = sess.sampled_decode([st], keep, reject_table(vocab), cls, eos=vocab.eos_index,
                               m0=vocab.char2index('m_0'), t=st.t, p=st.p,
                               seeds=None if seed is None else [seed], bans=_device_bans([st]),
-                              score=st.score, templates=_device_templates([st]))
+                              score=st.score, templates=_device_templates([st]), bars=_device_bars([st]))
     if res.err[0] & 2:
         if seed is None:
             np.random.set_state(rng0)
@@ -1038,11 +1246,11 @@ def _sampled_on_device(sess, st, vocab, all_controls, logger, seed=None):
 
 def _generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
                     bars_to_generate, greedy, use_kv_cache, stats, warm=True, device_grammar=True,
-                    t=1.0, p=None, seed=None, allowed=None, score=False, tpl=None):
+                    t=1.0, p=None, seed=None, allowed=None, score=False, tpl=None, bar_len=0):
     def fresh_span():  # a seeded request starts its own stream (anew after a device redo)
         rng = np.random if seed is None else np.random.RandomState(seed)
         return _Span(vocab, src, target, all_controls, no_whole, greedy, logger, t, p, rng, bans, score,
-                     tpl)
+                     tpl, bar_len)
     try:
         bans = _request_bans(vocab, events, tracks_to_generate, bars_to_generate, allowed)
         src, mtn, mbn, target, no_whole = _prepare(events, vocab, tracks_to_generate,
@@ -1085,6 +1293,8 @@ def _generation_all(model, events, device, vocab, logger, all_controls, tracks_t
                 if score:
                     stats["logprobs"] = [np.asarray(st.logp, dtype=np.float64)]
                     stats["scores"] = [float(np.sum(stats["logprobs"][0]))]
+                if bar_len:
+                    stats["bar_fill"] = [list(st.fill)]
         return restore_marked_input(_src_tokens(vocab, src), st.total), mtn, mbn
     except Exception as e:  # reference behaviour (generation.py:695-696)
         print(e)
@@ -1170,7 +1380,7 @@ def _batch_session(model, R, Smax, Tmax, precision, exact_tmax=False, warm=True,
 def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logger=None,
                      max_tgt=None, precision=None, return_stats=False, device_grammar=True,
                      warm=True, t=1.0, p=None, variations=None, seed=None, pitches=None,
-                     logprobs=False, rank=False, template=None):
+                     logprobs=False, rank=False, template=None, fill_bar=False):
     """Decode many infill requests in lockstep on one KV-cached session.
 
     requests: list of (events, tracks_to_generate, bars_to_generate).
@@ -1242,6 +1452,14 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
     of its mode ('greedy+tpl', 'rows+ban+tpl+score', ..), in which the
     requests without a template read an all-free tape.  Validated before
     anything else is touched (ValueError).
+    fill_bar: the bar clock (see generation_all), one bool for all requests or
+    one per request; with variations all takes of a request carry it.  A call
+    in which no request sets it replays the step graphs it always did;
+    otherwise the '+bar' graph of its mode ('greedy+bar', 'rows+ban+bar+tpl',
+    ..), in which the requests without it have bar length 0 and are left
+    alone.  The stats dict then receives 'bar_fill': per entry of 'generated'
+    None, or one (cursor, L) per note span.  Validated before anything else is
+    touched (ValueError).
     Returns a list of (restored, mask_track_names, mask_bar_names) (None
     where nothing was masked), and optionally {'tokens', 'steps', 'sources',
     'prefill_rows', 'seeds' (the effective seed of every entry of 'generated',
@@ -1253,6 +1471,8 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
     seeds = _check_seed(seed, len(requests), takes)
     allowed = _check_pitches(pitches, [tr for _, tr, _ in requests], len(requests))
     score = _check_score(logprobs, rank, variations)
+    bar_lens = [bar_units(ev) if fb else 0
+                for (ev, _, _), fb in zip(requests, _check_fill_bar(fill_bar, len(requests)))]
     bans = [_request_bans(vocab, list(ev), tr, br, a) for (ev, tr, br), a in zip(requests, allowed)]
     preps = [_prepare(list(ev), vocab, tr, br) for ev, tr, br in requests]
     srcs = [q[0] for q in preps]
@@ -1261,9 +1481,10 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
     elif not isinstance(template, (list, tuple)) or len(template) != len(requests):
         raise ValueError("template: None, or one value per request (%d)" % len(requests))
     else:
-        tpls = [_check_template(x, vocab, q[0], q[3], all_controls, q[4], bn)
-                for x, q, bn in zip(template, preps, bans)]
+        tpls = [_check_template(x, vocab, q[0], q[3], all_controls, q[4], bn, bl)
+                for x, q, bn, bl in zip(template, preps, bans, bar_lens)]
     if takes is not None:  # the expanded list: take k of request i is a request of its own
+        bar_lens = [x for x, n in zip(bar_lens, takes) for _ in range(n)]
         tpls = [x for x, n in zip(tpls, takes) for _ in range(n)]
         preps = [q for q, n in zip(preps, takes) for _ in range(n)]
         tps = [x for x, n in zip(tps, takes) for _ in range(n)]
@@ -1271,8 +1492,8 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
 
     def fresh_spans():  # seeded: every request's stream starts (again) at its seed
         rngs = [np.random] * len(preps) if seeds is None else [np.random.RandomState(x) for x in seeds]
-        return [_Span(vocab, q[0], q[3], all_controls, q[4], greedy, logger, a, b, g, bn, score, tp)
-                for q, (a, b), g, bn, tp in zip(preps, tps, rngs, bans, tpls)]
+        return [_Span(vocab, q[0], q[3], all_controls, q[4], greedy, logger, a, b, g, bn, score, tp, bl)
+                for q, (a, b), g, bn, tp, bl in zip(preps, tps, rngs, bans, tpls, bar_lens)]
     spans = fresh_spans()
     R = len(preps)
     Smax = max(len(q[0]) for q in preps)
@@ -1296,15 +1517,16 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
         fed = [0] * R
         latency = None
         kv_reads = None
-        # (the template kernel serves vocabularies up to 512 tokens, as the sampler does: a
-        # templated greedy call above that runs the host loop below)
-        if greedy and device_grammar and (vocab.vocab_size <= 512 or _device_templates(spans) is None):
+        # (the template and clock kernels serve vocabularies up to 512 tokens, as the sampler
+        # does: a templated or clocked greedy call above that runs the host loop below)
+        if greedy and device_grammar and (vocab.vocab_size <= 512 or (
+                _device_templates(spans) is None and _device_bars(spans) is None)):
             keep, cls = grammar_tables(vocab, all_controls)
             m0 = vocab.char2index('m_0')
             ts = time.perf_counter()
             res = sess.greedy_decode(spans, keep, cls, eos=vocab.eos_index, m0=m0,
                                      bans=_device_bans(spans), score=score,
-                                     templates=_device_templates(spans))
+                                     templates=_device_templates(spans), bars=_device_bars(spans))
             t_dev = time.perf_counter() - ts
             seqs, steps = res.ids, res.steps
             # completion time of each request from the call's start: host
@@ -1329,7 +1551,8 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
             res = sess.sampled_decode(
                 spans, keep, reject_table(vocab), cls, eos=vocab.eos_index,
                 m0=vocab.char2index('m_0'), t=[a for a, _ in tps], p=[b for _, b in tps],
-                seeds=seeds, bans=_device_bans(spans), score=score, templates=_device_templates(spans))
+                seeds=seeds, bans=_device_bans(spans), score=score, templates=_device_templates(spans),
+                bars=_device_bars(spans))
             t_dev = time.perf_counter() - ts
             if np.any(res.err & 2):
                 # some row's probabilities missed 1 by more than 1e-9
@@ -1368,7 +1591,10 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
                     if ban is not None:
                         keep[k] &= ~ban
                 x = np.where(keep, lg, np.float32(-100.0))
-                for k, i in enumerate(live):  # the template rewrites the masked row; the score below reads lg and keep
+                for k, i in enumerate(live):  # the bar clock and the template rewrite the masked row; the score below reads lg and keep
+                    cb = spans[i].clock_ban()
+                    if cb is not None:
+                        x[k][cb] = np.float32(-100.0)
                     force = spans[i].forced()
                     if force is not None:
                         x[k] = _forced(x[k], vocab, force)
@@ -1405,6 +1631,8 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
             extra = {"logprobs": lp_all, "scores": [float(np.sum(a)) for a in lp_all]}
         if rank:
             extra["order"] = order
+        if any(bar_lens):
+            extra["bar_fill"] = [list(st.fill) if st.bar_len else None for st in spans]
         return out, {**extra, "tokens": tokens, "steps": steps, "prepare_s": t1 - t0,
                      "prefill_s": t2 - t1, "decode_s": t3 - t2, "step_call_s": t_dev,
                      "request_latency_s": latency, "kv_row_reads": kv_reads,
@@ -1745,7 +1973,7 @@ def score_infill(model, events, device, vocab, all_controls, tracks_to_generate,
 # --------------------------------------------------------------------------
 # infill templates: the opening of a span is given, the model writes the rest
 # --------------------------------------------------------------------------
-def _check_template(template, vocab, src, target, all_controls, no_whole, bans=None):
+def _check_template(template, vocab, src, target, all_controls, no_whole, bans=None, bar_len=0):
     """Validated template of one request: None stays None; otherwise one row
     per mask, in mask_targets order, each None (free) or a sequence of items
     -- a token (string or id), ANY_PITCH, or '<eos>' as the last item of a
@@ -1760,12 +1988,16 @@ def _check_template(template, vocab, src, target, all_controls, no_whole, bans=N
     check would reject; ANY_PITCH in a state, or on a track, that keeps no
     pitch; m_0 or an unknown token; '<eos>' anywhere but last; items after the
     token that ends the span; a note row of more than MAX_BODY body items.
+    bar_len (fill_bar=: the bar's length in sixteenths, 0: none): the rows are
+    replayed with the bar clock, and an item the clock bans is rejected too -- a
+    row that overruns the bar, ANY_PITCH at a full bar, a closing '<eos>' on a
+    bar that is not full.
     Touches neither the model nor np.random."""
     if template is None:
         return None
     if isinstance(template, (str, bytes)) or not hasattr(template, "__len__"):
         raise ValueError("template: one row per mask (got %r)" % (template,))
-    sp = _Span(vocab, src, target, all_controls, no_whole, True, None, bans=bans)
+    sp = _Span(vocab, src, target, all_controls, no_whole, True, None, bans=bans, bar_len=bar_len)
     if len(template) != sp.n_masks or len(target) < sp.n_masks:
         raise ValueError("template: %d rows for %d masks" % (len(template), sp.n_masks))
     V, table, pitch = vocab.vocab_size, vocab._char2idx, _pitch_mask(vocab)
@@ -1806,6 +2038,12 @@ def _check_template(template, vocab, src, target, all_controls, no_whole, bans=N
             ban = sp.ban()
             if ban is not None:
                 keep = keep & ~ban
+            cb = sp.clock_ban()
+            if cb is not None:
+                if cb[sp.v.pitch_indices[0]] if x is ANY_PITCH else cb[x]:
+                    raise ValueError("template: row %d, item %d: fill_bar does not allow %s there (the bar holds "
+                                     "%d of %d sixteenths)" % (k, i, "a pitch" if x is ANY_PITCH else
+                                                               repr(vocab.index2char(x)), sp.clock.end, bar_len))
             if x is ANY_PITCH:
                 ok = np.flatnonzero(keep & pitch)
                 if check is not None:

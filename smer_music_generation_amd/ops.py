@@ -860,6 +860,39 @@ def logits_template(logits, state, cls, tape):
          tape.shape[1], tape.shape[2], _stream())
 
 
+CLOCK_WORDS = 8   # int32 words of one request's bar clock: T, P, A, G | S << 1, seen, three unused
+
+
+def bar_clock(logits, state, targets, out_tok, cls, units, bar_len, clock, *, eos):
+    """The bar clock ahead of a grammar step (smer_bar_clock; after logits_ban
+    and logprob_stage, before logits_template): for every request r that is
+    not done, clock[r] follows the token the step before emitted (out_tok[r,
+    count - 1]; cleared at the start of a span), and a request with bar_len[r]
+    > 0 that is drawing a note span gets -100 in logits row 2r + 1 at every
+    candidate that would pass the bar line or end the span beside it
+    (generation._BarClock.banned).  logits float32 [>= 2R, V <= 512] (rows
+    contiguous), state int32 [R, nst], targets int8 [R, max_masks], out_tok
+    int32 [R, cap], cls uint8 [V] (the grammar step's own tables), units uint8
+    [V] (sixteenths per token), bar_len int32 [R] (0: no clock), clock int32
+    [R, CLOCK_WORDS] (zeroed by the caller once per decode)."""
+    R, nst = state.shape
+    V = logits.shape[1]
+    for t, dt in ((logits, torch.float32), (state, torch.int32), (targets, torch.int8), (out_tok, torch.int32),
+                  (cls, torch.uint8), (units, torch.uint8), (bar_len, torch.int32), (clock, torch.int32)):
+        if t.dtype != dt or t.device != logits.device:
+            raise RuntimeError("bar_clock: expected %s on the logits' device" % dt)
+    if not all(t.is_contiguous() for t in (state, targets, out_tok, cls, units, bar_len, clock)) or \
+            logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError("bar_clock: expected contiguous tables and logits rows")
+    if logits.shape[0] < 2 * R or targets.dim() != 2 or targets.shape[0] != R or targets.shape[1] < 1 or \
+            out_tok.dim() != 2 or out_tok.shape[0] != R or out_tok.shape[1] < 1 or \
+            tuple(cls.shape) != (V,) or tuple(units.shape) != (V,) or tuple(bar_len.shape) != (R,) or \
+            tuple(clock.shape) != (R, CLOCK_WORDS) or not 1 <= V <= 512 or nst < 9:
+        raise RuntimeError("bar_clock: shape mismatch")
+    call("smer_bar_clock", R, V, _p(logits), _ld(logits), _p(state), nst, _p(targets), targets.shape[1],
+         _p(out_tok), out_tok.shape[1], _p(cls), _p(units), int(eos), _p(bar_len), _p(clock), _stream())
+
+
 # ---------------------------------------------------------------------------
 def layernorm(x, gamma, beta, y, mean, rstd, eps=1e-5):
     M, N = x.shape
