@@ -48,6 +48,8 @@ the numpy RNG consumption are the reference's, so with the same
 from __future__ import annotations
 
 import time
+import weakref
+from collections import namedtuple
 from typing import NamedTuple
 
 import numpy as np
@@ -120,20 +122,69 @@ def _choice1(a, p, rng=np.random):
 _FLAG_NAMES = ("no_pitch", "no_duration", "no_rest", "no_whole_duration", "no_eos",
                "no_continue", "no_sep", "is_density", "is_polyphony", "is_occupation",
                "is_tensile", "no_control")
-_MASK_CACHE = {}
+
+
+# --------------------------------------------------------------------------
+# the tables of one vocabulary
+# --------------------------------------------------------------------------
+class _VocabTables(dict):
+    """What the host path derives from ONE vocabulary, built on first use:
+    (flags..) `allowed_ids`' keep rows, ('spec', code), ('grammar', controls),
+    'pitch', 'units', 'reject', and 'midi', the MIDI number -> pitch id map.
+    The vocabulary is held weakly (`owner`) and no entry refers to it: the
+    tables die with it, and `_tables` serves them to that very object alone
+    (another vocabulary at a reused address gets tables of its own)."""
+
+    def __init__(self, vocab):
+        super().__init__()
+        store, key = _TABLES, id(vocab)
+
+        def drop(ref):  # (closes over locals only: it may run while the interpreter shuts down)
+            t = store.get(key)
+            if t is not None and t.owner is ref:
+                del store[key]
+        self.owner = weakref.ref(vocab, drop)
+
+
+_TABLES = {}  # id(vocab) -> _VocabTables, for the vocabularies that are alive
+
+
+def _tables(vocab):
+    t = _TABLES.get(id(vocab))
+    if t is None or t.owner() is not vocab:
+        t = _TABLES[id(vocab)] = _VocabTables(vocab)
+    return t
+
+
+def _table(vocab, key, build):
+    """Entry `key` of the vocabulary's tables; build(vocab) makes it once."""
+    t = _tables(vocab)
+    hit = t.get(key)
+    if hit is None:
+        hit = t[key] = build(vocab)
+    return hit
+
+
+def _frozen(a):
+    a.setflags(write=False)
+    return a
 
 
 def allowed_ids(vocab, **flags):
-    """Boolean [V]: logits `sampling` keeps (others become -100).  The
+    """Boolean [V]: logits `sampling` keeps (others are masked).  The
     reference's `no_control` test (`i in dict.values()`) never matches
     (SURVEY Q1), so it is a no-op here too."""
-    key = (id(vocab),) + tuple(map(bool, map(flags.get, _FLAG_NAMES)))
-    hit = _MASK_CACHE.get(key)
-    if hit is not None:
-        return hit
+    g = flags.get
+    t, key = _tables(vocab), tuple(map(bool, map(g, _FLAG_NAMES)))  # (every draw comes here: no _table() detour)
+    hit = t.get(key)
+    if hit is None:
+        hit = t[key] = _allowed_ids(vocab, g)
+    return hit
+
+
+def _allowed_ids(vocab, g):
     V = vocab.vocab_size
     keep = np.ones(V, dtype=bool)
-    g = flags.get
     if g("no_pitch"):
         keep[vocab.pitch_indices] = False
     if g("no_duration"):
@@ -156,9 +207,7 @@ def allowed_ids(vocab, **flags):
             keep &= only
     keep[vocab.program_indices + vocab.structure_indices + vocab.time_signature_indices +
          vocab.tempo_indices] = False
-    keep.setflags(write=False)
-    _MASK_CACHE[key] = keep
-    return keep
+    return _frozen(keep)
 
 
 class _AnyPitch:
@@ -172,23 +221,21 @@ class _AnyPitch:
 # A template item (`template=`): any pitch token, and only a pitch token.
 ANY_PITCH = _AnyPitch()
 
-_PITCH_MASKS = {}
+
+def _pitch_row(vocab):
+    m = np.zeros(vocab.vocab_size, dtype=bool)
+    m[vocab.pitch_indices] = True
+    return _frozen(m)
 
 
 def _pitch_mask(vocab):
     """Boolean [V]: the pitch tokens."""
-    hit = _PITCH_MASKS.get(id(vocab))
-    if hit is None or hit[0] is not vocab:
-        m = np.zeros(vocab.vocab_size, dtype=bool)
-        m[vocab.pitch_indices] = True
-        m.setflags(write=False)
-        hit = _PITCH_MASKS[id(vocab)] = (vocab, m)
-    return hit[1]
+    return _table(vocab, "pitch", _pitch_row)
 
 
 def _forced(x, vocab, item):
-    """A template item applied to the masked row x (`where(keep, logit,
-    -100)`, float64 or float32) ahead of the division by t.  A token id: 0.0
+    """A template item applied to the masked row x (`masked_row` up to the
+    clock ban, float64 or float32) ahead of the division by t.  A token id: 0.0
     at the token and -100.0 at every other entry.  TPL_PITCH: -100.0 at every
     entry that is no pitch token; the pitch entries keep what the grammar mask
     and the pitch ban gave them."""
@@ -199,12 +246,30 @@ def _forced(x, vocab, item):
     return out
 
 
+def masked_row(logit, keep, clock_ban=None, force=None, vocab=None, dtype=np.float64):
+    """THE masked row of a draw; every host path builds it here, in this
+    order: 1. the float32 logits widened to `dtype`; 2. -100 wherever `keep`
+    (boolean [V]: the state's grammar keep less the pitch ban, `_state_keep`)
+    is False -- THE SCORE READS THIS ROW (`token_logprobs(logit, keep)`), so
+    neither clock nor template shows in it; 3. -100 wherever the bar clock
+    bans (clock_ban, boolean [V]); 4. the template item (force: a token id,
+    TPL_PITCH or ANY_PITCH; needs vocab).  The division by t is the caller's.
+    Steps 1-2 also take stacked rows [n, V]; a row that has passed them takes
+    3-4 alone with keep=True (the greedy batched loop)."""
+    x = np.where(keep, np.asarray(logit, dtype=np.float32).astype(dtype), dtype(-100.0))
+    if clock_ban is not None:
+        x[clock_ban] = -100.0
+    if force is not None:
+        x = _forced(x, vocab, TPL_PITCH if force is ANY_PITCH else int(force))
+    return x
+
+
 def sampling(logit, vocab, p=None, t=1.0, greedy=False, rng=np.random, ban=None, force=None, **flags):
     """`generation.py:41-95` with vectorised masking.  rng: the stream the
     draw comes from (np.random: the global one, as the reference).  ban
     (boolean [V], True = banned; None: nothing): `keep &= ~ban`, a banned
-    token's logit becomes -100.0 exactly as a masked class's does.  force (a
-    template item: a token id, or ANY_PITCH; None: nothing): the masked row is
+    token's logit is masked exactly as a masked class's is.  force (a template
+    item: a token id, or ANY_PITCH; None: nothing): the masked row is
     rewritten by `_forced` before the softmax; the draw itself, and what it
     takes from rng, is the draw of any other row."""
     if isinstance(logit, torch.Tensor):
@@ -212,10 +277,7 @@ def sampling(logit, vocab, p=None, t=1.0, greedy=False, rng=np.random, ban=None,
     keep = allowed_ids(vocab, **flags)
     if ban is not None:
         keep = keep & ~np.asarray(ban, dtype=bool)
-    lg = np.where(keep, np.asarray(logit, dtype=np.float32).astype(np.float64), -100.0)
-    if force is not None:
-        lg = _forced(lg, vocab, TPL_PITCH if force is ANY_PITCH else int(force))
-    probs = softmax_with_temperature(lg, t)
+    probs = softmax_with_temperature(masked_row(logit, keep, None, force, vocab), t)
     if greedy:
         return int(np.argmax(probs))
     if p is not None:
@@ -226,13 +288,13 @@ def sampling(logit, vocab, p=None, t=1.0, greedy=False, rng=np.random, ban=None,
 def token_logprobs(logit, keep):
     """float64 [V]: the log of the distribution `sampling()` builds from the
     float32 row `logit` at t = 1, before any nucleus cut or redraw: x =
-    where(keep, float64(float32(logit)), -100.0), x - logsumexp(x).  keep
-    (boolean [V]) is what the draw used: `allowed_ids` of the grammar state,
-    `& ~ban` under a pitch constraint.  The maximum is subtracted before the
-    exp, so a row of large logits stays finite where the softmax itself
-    overflows.  A masked entry scores from its -100 like any other."""
-    x = np.where(np.asarray(keep, dtype=bool), np.asarray(logit, dtype=np.float32).astype(np.float64),
-                 -100.0)
+    masked_row(logit, keep) = where(keep, float64(float32(logit)), -100.0),
+    x - logsumexp(x).  keep (boolean [V]) is what the draw used: `allowed_ids`
+    of the grammar state, `& ~ban` under a pitch constraint.  The maximum is
+    subtracted before the exp, so a row of large logits stays finite where
+    the softmax itself overflows.  A masked entry scores from its -100 like
+    any other."""
+    x = masked_row(logit, np.asarray(keep, dtype=bool))
     m = np.max(x)
     return x - (m + np.log(np.sum(np.exp(x - m))))
 
@@ -256,21 +318,27 @@ def _rank_order(logps):
     return sorted(range(len(logps)), key=lambda k: (-mean[k], k))
 
 
+def _per_request(x, n, one, name, what, here=None):
+    """The 'one value, or one per request' rule of a keyword: x is one value
+    for all n requests or a list, tuple or array of n; each goes through one().
+    n None (the plugin call): a sequence is an error, one(x) comes back."""
+    if isinstance(x, (list, tuple, np.ndarray)):
+        if n is None:
+            raise ValueError(here or "%s is one %s here" % (name, what))
+        if len(x) != n:
+            raise ValueError("%s: one %s, or one per request (%d)" % (name, what, n))
+        return [one(y) for y in x]
+    return one(x) if n is None else [one(x)] * n
+
+
 def _check_tp(t, p, n=None):
     """Validated (t, p) of a call; with n, one pair per request (scalars are
     repeated, sequences must have n entries).  t finite and > 0; p None, or
     finite and >= 0.  Raises ValueError; draws nothing."""
-    def seq(x):
-        return isinstance(x, (list, tuple, np.ndarray))
+    ts, ps = (_per_request(x, n, lambda y: y, "t and p", "value", here="t and p are scalars here")
+              for x in (t, p))
     if n is None:
-        if seq(t) or seq(p):
-            raise ValueError("t and p are scalars here")
-        ts, ps = [t], [p]
-    else:
-        ts = list(t) if seq(t) else [t] * n
-        ps = list(p) if seq(p) else [p] * n
-        if len(ts) != n or len(ps) != n:
-            raise ValueError("t and p: one value, or one per request (%d)" % n)
+        ts, ps = [ts], [ps]
     out = []
     for a, b in zip(ts, ps):
         try:
@@ -294,13 +362,7 @@ def _check_variations(variations, n=None):
         if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or x < 1:
             raise ValueError("variations must be an int >= 1 (got %r)" % (x,))
         return int(x)
-    if isinstance(variations, (list, tuple, np.ndarray)):
-        if n is None:
-            raise ValueError("variations is one int here")
-        if len(variations) != n:
-            raise ValueError("variations: one int, or one per request (%d)" % n)
-        return [one(x) for x in variations]
-    return one(variations) if n is None else [one(variations)] * n
+    return _per_request(variations, n, one, "variations", "int")
 
 
 SEED_MAX = 2 ** 32 - 1
@@ -326,14 +388,9 @@ def _check_seed(seed, n=None, takes=None):
                 not 0 <= x <= SEED_MAX:
             raise ValueError("seed must be an int in [0, 2**32 - 1] (got %r)" % (x,))
         return int(x)
-    if isinstance(seed, (list, tuple, np.ndarray)):
-        if n is None:
-            raise ValueError("seed is one int here")
-        if len(seed) != n:
-            raise ValueError("seed: one int, or one per request (%d)" % n)
-        seeds = [one(x) for x in seed]
-    else:
-        seeds = [one(seed)] * (1 if n is None else n)
+    seeds = _per_request(seed, n, one, "seed", "int")
+    if n is None:
+        seeds = [seeds]
     if takes is None:
         return seeds
     counts = [takes] * len(seeds) if isinstance(takes, (int, np.integer)) else list(takes)
@@ -433,7 +490,7 @@ def _request_bans(vocab, events, tracks_to_generate, bars_to_generate, allowed):
     if not allowed:
         return None
     order = sorted(allowed)
-    midi = {int(vocab.index2char(i)[2:]): i for i in vocab.pitch_indices}
+    midi = _table(vocab, "midi", lambda v: {int(v.index2char(i)[2:]): i for i in v.pitch_indices})
     rows = np.zeros((len(order), vocab.vocab_size), dtype=bool)
     for k, trk in enumerate(order):
         rows[k, vocab.pitch_indices] = True
@@ -486,56 +543,67 @@ def _target_code(tc):
     return {'r': 0, 'd': 1, 'o': 2, 'p': 3}.get(tc, 4)
 
 
-_SPEC_CACHE = {}
-
-
 def grammar_spec(v, code):
     """(sampling flags, redraw check, failure message) of grammar state
     `code`, built once per (vocab, code) (the per-token host replay of the
     device decode calls this for every emitted id)."""
-    key = (id(v), code)
-    hit = _SPEC_CACHE.get(key)
-    if hit is None or hit[0] is not v:
-        hit = (v, _grammar_spec(v, code))
-        _SPEC_CACHE[key] = hit
-    return hit[1]
+    t = _tables(v)
+    hit = t.get(("spec", code))
+    if hit is None:
+        hit = t["spec", code] = _grammar_spec(v, code)
+    return hit
 
 
 def _grammar_spec(v, code):
     """(sampling flags, redraw check, failure message) of grammar state
     `code` (generation.py:549-630):
     0 sep, 1 continue, 2/3 pitch, 4/5 rest (+no_whole), 6-9 first token of a
-    d/o/p/t control span, 10 first token of a note span, 11/12 free."""
+    d/o/p/t control span, 10 first token of a note span, 11/12 free.  The
+    checks read the vocabulary's index lists, not the vocabulary (its tables
+    must not keep it alive)."""
+    rest, eos, pitch, dur = v.rest_indices, v.eos_index, v.pitch_indices, v.duration_only_indices
     if code == 0:
         return (dict(no_rest=True, no_sep=True, no_eos=True, no_whole_duration=True,
                      no_control=True),
-                lambda i: i in v.rest_indices or i == v.eos_index or
-                i == v.duration_only_indices[0], "in sep failed")
+                lambda i: i in rest or i == eos or i == dur[0], "in sep failed")
     if code == 1:
         return (dict(no_rest=True, no_sep=True, no_duration=True, no_continue=True,
                      no_eos=True, no_control=True),
-                lambda i: i not in v.pitch_indices, 'in continue failed')
+                lambda i: i not in pitch, 'in continue failed')
     if code in (2, 3):
         return (dict(no_rest=True, no_sep=True, no_continue=True,
                      no_whole_duration=code == 3, no_eos=True, no_control=True),
-                lambda i: i not in v.duration_only_indices and i not in v.pitch_indices,
-                'in pitch failed')
+                lambda i: i not in dur and i not in pitch, 'in pitch failed')
     if code in (4, 5):
         return (dict(no_pitch=True, no_rest=True, no_sep=True, no_continue=True,
                      no_whole_duration=code == 5, no_eos=True, no_control=True),
-                lambda i: i not in v.duration_only_indices, 'in rest failed')
+                lambda i: i not in dur, 'in rest failed')
     if 6 <= code <= 9:
         return {('is_density', 'is_occupation', 'is_polyphony', 'is_tensile')[code - 6]: True}, None, ''
     if code == 10:
-        return (dict(no_duration=True, no_control=True),
-                lambda i: i in v.duration_only_indices, 'start failed')
+        return (dict(no_duration=True, no_control=True), lambda i: i in dur, 'start failed')
     return dict(no_whole_duration=code == 12, no_control=True), None, ''
+
+
+def _state_keep(vocab, code, ban=None):
+    """Boolean [V]: what grammar state `code` keeps, with the pitch-ban row
+    `ban` (boolean [V], or None) removed: the `keep` of `masked_row`."""
+    keep = allowed_ids(vocab, **grammar_spec(vocab, code)[0])
+    return keep if ban is None else keep & ~np.asarray(ban, dtype=bool)
 
 
 def grammar_tables(vocab, all_controls):
     """Device tables of the greedy grammar kernel: keep uint8 [13, V]
     (allowed_ids of every state) and token classes cls uint8 [V]
-    (1 continue, 2 pitch, 4 duration-only, 8 'sep', 16 'rest', 32 control)."""
+    (1 continue, 2 pitch, 4 duration-only, 8 'sep', 16 'rest', 32 control).
+    Built once per (vocabulary, control set); every call gets copies of its
+    own (a few KB), as ever, so a caller that writes into one harms no other."""
+    ctrl = tuple(sorted({int(c) for c in all_controls}))
+    keep, cls = _table(vocab, ("grammar", ctrl), lambda v: _grammar_tables(v, ctrl))
+    return keep.copy(), cls.copy()
+
+
+def _grammar_tables(vocab, all_controls):
     V = vocab.vocab_size
     keep = np.stack([allowed_ids(vocab, **grammar_spec(vocab, c)[0])
                      for c in range(N_GRAMMAR_STATES)]).astype(np.uint8)
@@ -551,32 +619,26 @@ def grammar_tables(vocab, all_controls):
         if ch == 'rest':
             cls[i] |= 16
     cls[[int(c) for c in all_controls]] |= 32
-    return keep, cls
+    return _frozen(keep), _frozen(cls)
 
 
 # --------------------------------------------------------------------------
 # the bar clock (`fill_bar=`): how much of its bar a note span has filled
 # --------------------------------------------------------------------------
 BAR_UNITS = {'whole': 16, 'half': 8, 'quarter': 4, 'eighth': 2, 'sixteenth': 1}  # in sixteenths
-_UNIT_CACHE = {}
+
+
+def _unit_row(vocab):
+    u = np.zeros(vocab.vocab_size, dtype=np.uint8)
+    for i in vocab.duration_only_indices:
+        u[i] = BAR_UNITS.get(vocab.index2char(i), 0)
+    return _frozen(u)
 
 
 def unit_table(vocab):
     """uint8 [V]: the length of every token in sixteenths (BAR_UNITS for the
     duration tokens, 0 for every other token)."""
-    hit = _UNIT_CACHE.get(id(vocab))
-    if hit is None or hit[0] is not vocab:
-        u = np.zeros(vocab.vocab_size, dtype=np.uint8)
-        for i in vocab.duration_only_indices:
-            u[i] = BAR_UNITS.get(vocab.index2char(i), 0)
-        u.setflags(write=False)
-        hit = _UNIT_CACHE[id(vocab)] = (vocab, u)
-    return hit[1]
-
-
-def _class_table(vocab, all_controls):
-    """grammar_tables' cls uint8 [V] alone."""
-    return grammar_tables(vocab, all_controls)[1]
+    return _table(vocab, "units", _unit_row)
 
 
 def bar_units(events):
@@ -681,13 +743,7 @@ def _check_fill_bar(fill_bar, n=None):
         if not isinstance(x, (bool, np.bool_)):
             raise ValueError("fill_bar must be True or False (got %r)" % (x,))
         return bool(x)
-    if isinstance(fill_bar, (list, tuple, np.ndarray)):
-        if n is None:
-            raise ValueError("fill_bar is one bool here")
-        if len(fill_bar) != n:
-            raise ValueError("fill_bar: one bool, or one per request (%d)" % n)
-        return [one(x) for x in fill_bar]
-    return one(fill_bar) if n is None else [one(fill_bar)] * n
+    return _per_request(fill_bar, n, one, "fill_bar", "bool")
 
 
 class _Span:
@@ -702,6 +758,7 @@ class _Span:
         # pitch constraints (_request_bans): the ban row of each mask (-1:
         # none) and the boolean rows; None: an unconstrained request
         self.ban_of_mask, self.ban_rows = bans if bans is not None else (None, None)
+        self._keeps = {}  # (state code, ban row) -> the keep of governs()
         # take scores: with `score`, logp receives token_logprobs(..)[id] of
         # every emitted id, in draw order (the host draws append it, a device
         # path assigns its own); without, nothing is computed
@@ -714,7 +771,7 @@ class _Span:
         # (0: off); the clock follows the tokens of the note span being drawn,
         # and `fill` receives (cursor, bar_len) of every note span that ends
         self.bar_len = int(bar_len)
-        self.clock = _BarClock(bar_len, _class_table(vocab, all_controls), unit_table(vocab)) \
+        self.clock = _BarClock(bar_len, grammar_tables(vocab, all_controls)[1], unit_table(vocab)) \
             if self.bar_len else None
         self.fill = []
         self.src = src
@@ -745,8 +802,7 @@ class _Span:
         return self.mask_idx < len(self.mask_target) and _target_code(self.mask_target[self.mask_idx]) == 0
 
     def clock_ban(self):
-        """Boolean [V]: what the bar clock bans for the draw about to be made
-        (note spans only), or None."""
+        """Boolean [V]: what the bar clock bans for the next draw (note spans only), or None."""
         if self.clock is None or self.done or not self._note_span():
             return None
         return self.clock.banned(self.v)
@@ -760,19 +816,16 @@ class _Span:
     def prefix(self):
         return self.tgt_inp + self.this_in
 
+    def _ban_index(self):
+        """The ban row of the mask being drawn, or -1."""
+        if self.ban_of_mask is None or self.mask_idx >= len(self.ban_of_mask):
+            return -1
+        return self.ban_of_mask[self.mask_idx]
+
     def ban(self):
         """Boolean [V] ban of the mask being drawn, or None."""
-        if self.ban_of_mask is None or self.mask_idx >= len(self.ban_of_mask):
-            return None
-        k = self.ban_of_mask[self.mask_idx]
+        k = self._ban_index()
         return None if k < 0 else self.ban_rows[k]
-
-    def device_bans(self):
-        """(ban_of_mask row, bit rows uint32 [k, 16]) for DecodeSession's
-        `bans=`, or None."""
-        if self.ban_of_mask is None:
-            return None
-        return self.ban_of_mask, ban_bits(self.ban_rows)
 
     def forced(self):
         """The template item that governs the draw about to be made (a token
@@ -782,44 +835,45 @@ class _Span:
         row, i = self.tpl[self.mask_idx], len(self.this_in) - 1
         return None if row is None or i >= len(row) else row[i]
 
-    def _score(self, logit, flags, ban, idx):
-        """The emitted id's log-probability (t = 1, the whole distribution,
-        the redraws not counted) from the draw's own keep; draws nothing."""
-        if isinstance(logit, torch.Tensor):
-            logit = logit.squeeze().detach().cpu().numpy()
-        keep = allowed_ids(self.v, **flags)
-        if ban is not None:
-            keep = keep & ~np.asarray(ban, dtype=bool)
-        self.logp.append(token_logprobs(logit, keep)[int(idx)])
+    def governs(self):
+        """What governs the draw about to be made, `masked_row`'s arguments:
+        (keep, clock_ban, force).  keep: the grammar keep of spec() less the
+        mask's pitch ban -- what the score reads; the other two may be None."""
+        return self._governs(self.state_code(), self._ban_index())
 
-    def _draw(self, logit, check, failmsg, flags):
-        idx = self._draw_id(logit, check, failmsg, flags)
+    def _governs(self, code, k):
+        """governs() for state `code` and ban row k (-1: none), which the
+        caller has read; the keep of a (state, ban row) pair is built once."""
+        keep = self._keeps.get((code, k))
+        if keep is None:
+            keep = self._keeps[code, k] = _state_keep(self.v, code, None if k < 0 else self.ban_rows[k])
+        return keep, self.clock_ban(), self.forced()
+
+    def scored(self, logit, keep, idx):
+        """With `score`: the emitted id's log-probability (t = 1, the redraws not
+        counted) under the `keep` of the governs() tuple its draw was made from."""
         if self.score:
-            self._score(logit, flags, self.ban(), idx)
-        return idx
+            if isinstance(logit, torch.Tensor):
+                logit = logit.squeeze().detach().cpu().numpy()
+            self.logp.append(token_logprobs(logit, keep)[int(idx)])
 
-    def _draw_id(self, logit, check, failmsg, flags):
-        ban = self.ban()
-        cb = self.clock_ban()
-        if cb is not None:  # (_draw scores from the unclocked ban: what score_infill gives)
-            ban = cb if ban is None else ban | cb
-        if ban is not None:  # (an unconstrained draw is the call it always was)
-            flags = dict(flags, ban=ban)
-        force = self.forced()
-        if force is not None:  # (after the ban; _draw scores from the flags it was given: the row before this)
+    def _draw_id(self, logit, check, failmsg, flags, gov, pb):
+        """The draw of `gov` through sampling(), whose own keep is that of
+        `flags`: the pitch-ban row pb that gov's keep was built from, and the
+        clock ban, go in as `ban` (an unconstrained draw is the call it always
+        was).  The reference's loop: the draw, then up to 11 redraws while
+        `check` rejects; the 12th id stands unchecked and the failure is logged."""
+        _, cb, force = gov
+        if cb is not None or pb is not None:
+            flags = dict(flags, ban=pb if cb is None else cb if pb is None else pb | cb)
+        if force is not None:
             flags = dict(flags, force=force)
-        idx = sampling(logit, self.v, p=self.p, t=self.t, greedy=self.greedy, rng=self.rng, **flags)
-        if check is None:
-            return idx
-        n = 0
-        while check(idx):
-            idx = sampling(logit, self.v, p=self.p, t=self.t, greedy=self.greedy, rng=self.rng,
-                           **flags)
-            n += 1
-            if n > 10:
-                if self.logger is not None:
-                    self.logger.info(failmsg)
-                break
+        for n in range(12):
+            idx = sampling(logit, self.v, p=self.p, t=self.t, greedy=self.greedy, rng=self.rng, **flags)
+            if n < 11 and (check is None or not check(idx)):
+                return idx
+        if self.logger is not None:
+            self.logger.info(failmsg)
         return idx
 
     def state_code(self):
@@ -846,8 +900,12 @@ class _Span:
 
     def advance(self, logit):
         """Consume the logits of the current prefix's last position."""
-        flags, check, failmsg = self.spec()
-        return self.commit(self._draw(logit, check, failmsg, flags))
+        code, k = self.state_code(), self._ban_index()  # (read once: spec and tuple come from the same pair)
+        flags, check, failmsg = grammar_spec(self.v, code)
+        gov = self._governs(code, k)
+        idx = self._draw_id(logit, check, failmsg, flags, gov, None if k < 0 else self.ban_rows[k])
+        self.scored(logit, gov[0], idx)
+        return self.commit(idx)
 
     def commit_greedy(self, idx, check, failmsg):
         """Greedy draw already taken (argmax over the masked logits): the
@@ -862,28 +920,9 @@ class _Span:
         redraw logger): the same tgt_inp / total / mask_idx / done, without
         the per-token flag updates (only spec() reads them, and a finished
         request never calls it again)."""
-        i2c = self.v.index2char
-        eos, ctrl = self.eos, self.all_controls
-        this_in, this_ev = self.this_in, self.this_ev
+        i2c, push = self.v.index2char, self._push
         for idx in seq:
-            if self.clock is not None:
-                self.clock.advance_id(idx)
-            if idx in ctrl:
-                this_in += [idx, eos]
-                this_ev += [i2c(idx), '<eos>']
-            else:
-                this_in.append(idx)
-                this_ev.append(i2c(idx))
-            if this_in[-1] == eos or len(this_in) >= 100:
-                self._span_ends()
-                self.tgt_inp.extend(this_in[:-1])
-                self.total.extend(this_ev[:-1])
-                self.mask_idx += 1
-                if self.mask_idx >= self.n_masks:
-                    self.done = True
-                else:
-                    self._start_span()
-                    this_in, this_ev = self.this_in, self.this_ev
+            push(idx, i2c(idx))
 
     def commit(self, idx):
         v = self.v
@@ -899,24 +938,31 @@ class _Span:
             self.in_sep = True
         if ev == 'rest':
             self.in_rest = True
+        self._push(idx, ev)
+        return idx
+
+    def _push(self, idx, ev):
+        """Push one emitted id (ev: its token), and end the span where it ends:
+        a control token brings its <eos>; at <eos> or the 100-token cap the span
+        goes to tgt_inp / total without its last token and the next mask starts."""
         if self.clock is not None:
             self.clock.advance_id(idx)
+        this_in, this_ev = self.this_in, self.this_ev
         if idx in self.all_controls:
-            self.this_in += [idx, self.eos]
-            self.this_ev += [ev, '<eos>']
+            this_in += [idx, self.eos]
+            this_ev += [ev, '<eos>']
         else:
-            self.this_in.append(idx)
-            self.this_ev.append(ev)
-        if self.this_in[-1] == self.eos or len(self.this_in) >= 100:
+            this_in.append(idx)
+            this_ev.append(ev)
+        if this_in[-1] == self.eos or len(this_in) >= 100:
             self._span_ends()
-            self.tgt_inp.extend(self.this_in[:-1])
-            self.total.extend(self.this_ev[:-1])
+            self.tgt_inp.extend(this_in[:-1])
+            self.total.extend(this_ev[:-1])
             self.mask_idx += 1
             if self.mask_idx >= self.n_masks:
                 self.done = True
             else:
                 self._start_span()
-        return idx
 
 
 def _src_tokens(vocab, src):
@@ -938,6 +984,82 @@ def _prepare(events, vocab, tracks_to_generate, bars_to_generate):
     src, mtn, mbn = mask_bar_and_track(events, vocab, tracks, bars_to_generate)
     no_whole = not (int(events[0][0]) >= 4 and int(events[0][2]) == 4)
     return src, mtn, mbn, target, no_whole
+
+
+class _Slot(namedtuple("_Slot", "src mask_track_names mask_bar_names target no_whole t p seed bans tpl bar_len")):
+    """One decode slot (a request, or one take of it), immutable: `_prepare`'s
+    five values and the request's validated keywords -- t, p, the effective
+    seed (None: the global stream), `_request_bans`' pair, `_check_template`'s
+    rows and the bar length in sixteenths (0: no clock)."""
+    __slots__ = ()
+
+    def span(self, vocab, all_controls, greedy, logger, score):
+        """A fresh `_Span` of the slot; a seeded one starts its stream anew."""
+        rng = np.random if self.seed is None else np.random.RandomState(self.seed)
+        return _Span(vocab, self.src, self.target, all_controls, self.no_whole, greedy, logger, self.t,
+                     self.p, rng, self.bans, score, self.tpl, self.bar_len)
+
+
+# A call's requests, resolved: the slots in decode order (request i takes[i] times in a row; takes None:
+# no variations), and what `stats` reports: the seed per slot (or None), the pitches per request
+_Resolved = namedtuple("_Resolved", "slots takes seeds allowed score rank")
+
+
+class _Unprepared(Exception):
+    """`_prepare` / `_request_bans` failed on the plugin call's request: the
+    call prints the cause and returns None (generation.py:695-696)."""
+
+
+def _masked_request(vocab, events, tracks_to_generate, bars_to_generate, allowed=None):
+    """(`_prepare`'s five values, the ban rows) of one request; `events` is
+    the masked song afterwards (fill_empty_bars appends to its argument)."""
+    bans = _request_bans(vocab, events, tracks_to_generate, bars_to_generate, allowed)
+    return _prepare(events, vocab, tracks_to_generate, bars_to_generate), bans
+
+
+def _resolve(requests, vocab, all_controls, n, *, t, p, variations, seed, pitches, logprobs, rank,
+             template, fill_bar, checked=None):
+    """Validate a call's keywords and build its slots.  n: the number of
+    `requests` for generation_batch (a keyword is one value, or one per
+    request), None for the plugin call (one request, one value each).  Raises
+    ValueError in the order t/p, variations, seed, pitches, logprobs/rank,
+    fill_bar, template; touches neither the model nor np.random.
+    checked(seeds, allowed): the plugin call's own step between the keyword
+    checks and the decode (its stats, its use_kv_cache check); it has always
+    come before the request is prepared, and with a template after that."""
+    one = n is None
+
+    def each(x):
+        return [x] if one else x
+    tps = each(_check_tp(t, p, n))
+    takes = None if variations is None else each(_check_variations(variations, n))
+    seeds = _check_seed(seed, n, takes if takes is None or not one else takes[0])
+    allowed = each(_check_pitches(pitches, requests[0][1] if one else [tr for _, tr, _ in requests], n))
+    score = _check_score(logprobs, rank, variations)
+    bar_lens = [bar_units(ev) if fb else 0 for (ev, _, _), fb in zip(requests, each(_check_fill_bar(fill_bar, n)))]
+    if checked is not None and template is None:
+        checked(seeds, allowed)
+    try:
+        preps = [_masked_request(vocab, ev, tr, br, a) for (ev, tr, br), a in zip(requests, allowed)]
+    except Exception as e:
+        if one:
+            raise _Unprepared(e) from None
+        raise
+    if one:
+        template, had_template = [template], template is not None
+    elif template is None:
+        template = [None] * n
+    elif not isinstance(template, (list, tuple)) or len(template) != n:
+        raise ValueError("template: None, or one value per request (%d)" % n)
+    slots = [_Slot(*q, a, b, None, bn, _check_template(x, vocab, q[0], q[3], all_controls, q[4], bn, bl), bl)
+             for (q, bn), (a, b), x, bl in zip(preps, tps, template, bar_lens)]
+    if checked is not None and had_template:
+        checked(seeds, allowed)
+    if takes is not None:  # the expanded list: take k of request i is a slot of its own
+        slots = [s for s, k in zip(slots, takes) for _ in range(k)]
+    if seeds is not None:
+        slots = [s._replace(seed=x) for s, x in zip(slots, seeds)]
+    return _Resolved(slots, takes, seeds, allowed, score, bool(rank))
 
 
 class _Precision:
@@ -1097,42 +1219,31 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
     the keyword replays the graphs it always did.  Anything but a bool, or a
     bar whose length is no integer in 1..255 sixteenths, raises ValueError
     before the model or np.random is touched."""
-    t, p = _check_tp(t, p)
-    n = None if variations is None else _check_variations(variations)
-    seeds = _check_seed(seed, None, n)
-    allowed = _check_pitches(pitches, tracks_to_generate)
-    score = _check_score(logprobs, rank, variations)
-    bar_len = bar_units(events) if _check_fill_bar(fill_bar) else 0
-    tpl = None
-    if template is not None:
-        try:
-            q = _prepare(list(events), vocab, tracks_to_generate, bars_to_generate)
-            bans = _request_bans(vocab, list(events), tracks_to_generate, bars_to_generate, allowed)
-        except Exception as e:  # reference behaviour (generation.py:695-696): what the call itself would print
-            print(e)
-            return None
-        tpl = _check_template(template, vocab, q[0], q[3], all_controls, q[4], bans, bar_len)
-    if stats is not None:
-        stats["seeds"] = seeds
-        stats["pitches"] = allowed
-    if variations is not None:
-        if not use_kv_cache:
+    t0 = time.perf_counter()
+
+    def checked(seeds, allowed):
+        if stats is not None:
+            stats["seeds"] = seeds
+            stats["pitches"] = allowed[0]
+        if variations is not None and not use_kv_cache:
             raise ValueError("variations needs the KV-cached path (use_kv_cache=True)")
+    try:
+        rq = _resolve([(events if variations is None else list(events), tracks_to_generate, bars_to_generate)],
+                      vocab, all_controls, None, t=t, p=p, variations=variations, seed=seed, pitches=pitches,
+                      logprobs=logprobs, rank=rank, template=template, fill_bar=fill_bar, checked=checked)
+    except _Unprepared as e:  # reference behaviour (generation.py:695-696)
+        print(e.args[0])
+        return None
+    if variations is not None:
         with _Precision(model, precision):
             try:
-                out, st = generation_batch(model, [(events, tracks_to_generate, bars_to_generate)],
-                                           vocab, all_controls, greedy=greedy, logger=logger,
-                                           return_stats=True, device_grammar=device_grammar, warm=warm,
-                                           t=t, p=p, variations=[n],
-                                           seed=None if seeds is None else [seeds[0]],
-                                           pitches=[allowed], logprobs=score, rank=bool(rank),
-                                           template=None if template is None else [template],
-                                           fill_bar=[bool(bar_len)])
+                out, st = _decode_batch(model, rq, vocab, all_controls, greedy=greedy, logger=logger,
+                                        device_grammar=device_grammar, warm=warm, t0=t0)
                 if stats is not None:
                     stats["steps"] = st["steps"]
-                    if bar_len:
+                    if rq.slots[0].bar_len:
                         stats["bar_fill"] = st["bar_fill"]
-                    if score:
+                    if rq.score:
                         stats["logprobs"], stats["scores"] = st["logprobs"], st["scores"]
                     if rank:
                         stats["order"] = st["order"][0]
@@ -1141,51 +1252,36 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
                 print(e)
                 return None
     with _Precision(model, precision):
-        return _generation_all(model, events, device, vocab, logger, all_controls,
-                               tracks_to_generate, bars_to_generate, greedy, use_kv_cache, stats,
-                               warm, device_grammar, t, p, None if seeds is None else seeds[0],
-                               allowed, score, tpl, bar_len)
+        return _generation_all(model, device, vocab, logger, all_controls, rq.slots[0], greedy, use_kv_cache,
+                               stats, warm, device_grammar, rq.score)
 
 
-_REJECT_CACHE = {}
+def _reject_rows(vocab):
+    rej = np.zeros((N_GRAMMAR_STATES, vocab.vocab_size), dtype=np.uint8)
+    for c in range(N_GRAMMAR_STATES):
+        chk = grammar_spec(vocab, c)[1]
+        if chk is not None:
+            rej[c] = [bool(chk(i)) for i in range(vocab.vocab_size)]
+    return rej
 
 
 def reject_table(vocab):
     """uint8 [13, V]: the redraw checks of the grammar states
     (generation.py:556-615; grammar_spec's check), 1 = redraw."""
-    hit = _REJECT_CACHE.get(id(vocab))
-    if hit is not None and hit[0] is vocab:
-        return hit[1]
-    V = vocab.vocab_size
-    rej = np.zeros((N_GRAMMAR_STATES, V), dtype=np.uint8)
-    for c in range(N_GRAMMAR_STATES):
-        chk = grammar_spec(vocab, c)[1]
-        if chk is not None:
-            rej[c] = [bool(chk(i)) for i in range(V)]
-    _REJECT_CACHE[id(vocab)] = (vocab, rej)
-    return rej
+    return _table(vocab, "reject", _reject_rows)
 
 
-def _device_bans(spans):
-    """`bans=` of DecodeSession.greedy_decode / sampled_decode: per span None
-    or (ban_of_mask row, bit rows); None when no span is constrained (the
-    call then replays the graphs without the ban kernel)."""
-    bans = [sp.device_bans() for sp in spans]
-    return bans if any(b is not None for b in bans) else None
-
-
-def _device_templates(spans):
-    """`templates=` of DecodeSession.greedy_decode / sampled_decode: per span
-    None or its rows; None when no span has a template (the call then replays
-    the graphs without the template kernel)."""
-    tpls = [sp.tpl for sp in spans]
-    return tpls if any(x is not None for x in tpls) else None
+def _device_rows(rows):
+    """`bans=` (per span None or (ban_of_mask row, bit rows uint32 [k, 16])) or
+    `templates=` (per span None or its rows) of the device decodes: the list,
+    or None when every entry is None (the graphs without that kernel replay)."""
+    rows = list(rows)
+    return rows if any(x is not None for x in rows) else None
 
 
 def _device_bars(spans):
-    """`bars=` of DecodeSession.greedy_decode / sampled_decode: per span its
-    bar length in sixteenths (0: no clock); None when no span has one (the
-    call then replays the graphs without the clock kernel)."""
+    """`bars=` of the device decodes: per span its bar length in sixteenths (0:
+    no clock); None when no span has one (the graphs without the clock replay)."""
     bars = [sp.bar_len for sp in spans]
     return bars if any(bars) else None
 
@@ -1221,41 +1317,40 @@ def _replay(spans, res, logger, sampled=True):
     return sum(len(seq) for seq in res.ids)
 
 
-def _sampled_on_device(sess, st, vocab, all_controls, logger, seed=None):
-    """One request's sampled span loop on device (DecodeSession.
-    sampled_decode), then the emitted ids replayed through the host span
-    (event lists, the redraw-failure log lines).  Returns the steps, or None
-    when a row's probabilities missed 1 by more than 1e-9 (np.random.choice
-    territory): the RNG is then rewound and the caller decodes on the host
-    (a seeded call touches no global state: the caller starts a fresh
-    RandomState(seed))."""
+def _decode_on_device(sess, spans, vocab, all_controls, logger, greedy, seeds, score):
+    """The span loop of `spans` on the device, then its ids replayed through
+    the host spans (event lists, redraw-failure log lines).  Returns (tokens,
+    DecodeResult, start, end of the device call), or None -- redo on the host
+    with fresh spans -- when a row's probabilities missed 1 by more than 1e-9
+    (np.random.choice territory); np.random is then rewound (a seeded call
+    touches no global state: fresh spans start fresh RandomStates)."""
     keep, cls = grammar_tables(vocab, all_controls)
-    rng0 = np.random.get_state() if seed is None else None
-    res = sess.sampled_decode([st], keep, reject_table(vocab), cls, eos=vocab.eos_index,
-                              m0=vocab.char2index('m_0'), t=st.t, p=st.p,
-                              seeds=None if seed is None else [seed], bans=_device_bans([st]),
-                              score=st.score, templates=_device_templates([st]), bars=_device_bars([st]))
-    if res.err[0] & 2:
-        if seed is None:
+    kw = dict(eos=vocab.eos_index, m0=vocab.char2index('m_0'), score=score, bars=_device_bars(spans),
+              templates=_device_rows(sp.tpl for sp in spans),
+              bans=_device_rows(None if sp.ban_of_mask is None else (sp.ban_of_mask, ban_bits(sp.ban_rows))
+                                for sp in spans))
+    rng0 = np.random.get_state() if seeds is None and not greedy else None
+    ts = time.perf_counter()
+    if greedy:
+        res = sess.greedy_decode(spans, keep, cls, **kw)
+    else:
+        res = sess.sampled_decode(spans, keep, reject_table(vocab), cls, t=[sp.t for sp in spans],
+                                  p=[sp.p for sp in spans], seeds=seeds, **kw)
+    te = time.perf_counter()
+    if not greedy and np.any(res.err & 2):
+        if seeds is None:
             np.random.set_state(rng0)
         return None
-    if res.err[0] & 1:
+    if np.any(res.err if greedy else res.err & 1):
         raise ValueError("decoder prefix exceeds session max_tgt %d" % (sess.Tmax - 1))
-    return _replay([st], res, logger)
+    return _replay(spans, res, logger, sampled=not greedy), res, ts, te
 
 
-def _generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
-                    bars_to_generate, greedy, use_kv_cache, stats, warm=True, device_grammar=True,
-                    t=1.0, p=None, seed=None, allowed=None, score=False, tpl=None, bar_len=0):
-    def fresh_span():  # a seeded request starts its own stream (anew after a device redo)
-        rng = np.random if seed is None else np.random.RandomState(seed)
-        return _Span(vocab, src, target, all_controls, no_whole, greedy, logger, t, p, rng, bans, score,
-                     tpl, bar_len)
+def _generation_all(model, device, vocab, logger, all_controls, slot, greedy, use_kv_cache, stats,
+                    warm=True, device_grammar=True, score=False):
     try:
-        bans = _request_bans(vocab, events, tracks_to_generate, bars_to_generate, allowed)
-        src, mtn, mbn, target, no_whole = _prepare(events, vocab, tracks_to_generate,
-                                                   bars_to_generate)
-        st = fresh_span()
+        src = slot.src
+        st = slot.span(vocab, all_controls, greedy, logger, score)
         if st.n_masks == 0:
             return None
         model.eval()
@@ -1269,11 +1364,12 @@ def _generation_all(model, events, device, vocab, logger, all_controls, tracks_t
                                       warm=warm)
                 sess.prefill([0], [src])
                 if device_grammar and not greedy and vocab.vocab_size <= 512:
-                    n = _sampled_on_device(sess, st, vocab, all_controls, logger, seed)
-                    if n is not None:
-                        steps = n
+                    done = _decode_on_device(sess, [st], vocab, all_controls, logger, False,
+                                             None if slot.seed is None else [slot.seed], score)
+                    if done is not None:
+                        steps = done[0]
                     else:  # fresh span, same RNG start: the host loop below
-                        st = fresh_span()
+                        st = slot.span(vocab, all_controls, greedy, logger, score)
                         sess.prefill([0], [src])
                 fed = 0
                 while not st.done:
@@ -1293,9 +1389,9 @@ def _generation_all(model, events, device, vocab, logger, all_controls, tracks_t
                 if score:
                     stats["logprobs"] = [np.asarray(st.logp, dtype=np.float64)]
                     stats["scores"] = [float(np.sum(stats["logprobs"][0]))]
-                if bar_len:
+                if slot.bar_len:
                     stats["bar_fill"] = [list(st.fill)]
-        return restore_marked_input(_src_tokens(vocab, src), st.total), mtn, mbn
+        return restore_marked_input(_src_tokens(vocab, src), st.total), slot.mask_track_names, slot.mask_bar_names
     except Exception as e:  # reference behaviour (generation.py:695-696)
         print(e)
 
@@ -1466,37 +1562,26 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
     None unseeded), 'pitches' (per request, None or the effective {track
     number: sorted tuple}), ..}."""
     t0 = time.perf_counter()
-    tps = _check_tp(t, p, len(requests))
-    takes = None if variations is None else _check_variations(variations, len(requests))
-    seeds = _check_seed(seed, len(requests), takes)
-    allowed = _check_pitches(pitches, [tr for _, tr, _ in requests], len(requests))
-    score = _check_score(logprobs, rank, variations)
-    bar_lens = [bar_units(ev) if fb else 0
-                for (ev, _, _), fb in zip(requests, _check_fill_bar(fill_bar, len(requests)))]
-    bans = [_request_bans(vocab, list(ev), tr, br, a) for (ev, tr, br), a in zip(requests, allowed)]
-    preps = [_prepare(list(ev), vocab, tr, br) for ev, tr, br in requests]
-    srcs = [q[0] for q in preps]
-    if template is None:
-        tpls = [None] * len(requests)
-    elif not isinstance(template, (list, tuple)) or len(template) != len(requests):
-        raise ValueError("template: None, or one value per request (%d)" % len(requests))
-    else:
-        tpls = [_check_template(x, vocab, q[0], q[3], all_controls, q[4], bn, bl)
-                for x, q, bn, bl in zip(template, preps, bans, bar_lens)]
-    if takes is not None:  # the expanded list: take k of request i is a request of its own
-        bar_lens = [x for x, n in zip(bar_lens, takes) for _ in range(n)]
-        tpls = [x for x, n in zip(tpls, takes) for _ in range(n)]
-        preps = [q for q, n in zip(preps, takes) for _ in range(n)]
-        tps = [x for x, n in zip(tps, takes) for _ in range(n)]
-        bans = [x for x, n in zip(bans, takes) for _ in range(n)]
+    rq = _resolve([(list(ev), tr, br) for ev, tr, br in requests], vocab, all_controls, len(requests), t=t,
+                  p=p, variations=variations, seed=seed, pitches=pitches, logprobs=logprobs, rank=rank,
+                  template=template, fill_bar=fill_bar)
+    out, stats = _decode_batch(model, rq, vocab, all_controls, greedy=greedy, logger=logger, max_tgt=max_tgt,
+                               precision=precision, device_grammar=device_grammar, warm=warm, t0=t0)
+    return (out, stats) if return_stats else out
+
+
+def _decode_batch(model, rq, vocab, all_controls, *, greedy, logger, device_grammar, warm, t0, max_tgt=None,
+                  precision=None):
+    """generation_batch on resolved requests (`_resolve`): (results, stats)."""
+    slots, takes, seeds, score = rq.slots, rq.takes, rq.seeds, rq.score
 
     def fresh_spans():  # seeded: every request's stream starts (again) at its seed
-        rngs = [np.random] * len(preps) if seeds is None else [np.random.RandomState(x) for x in seeds]
-        return [_Span(vocab, q[0], q[3], all_controls, q[4], greedy, logger, a, b, g, bn, score, tp, bl)
-                for q, (a, b), g, bn, tp, bl in zip(preps, tps, rngs, bans, tpls, bar_lens)]
+        return [s.span(vocab, all_controls, greedy, logger, score) for s in slots]
     spans = fresh_spans()
-    R = len(preps)
-    Smax = max(len(q[0]) for q in preps)
+    R = len(slots)
+    # one source per request: its takes sit in a row and share it
+    srcs = [slots[k].src for k in (range(R) if takes is None else np.cumsum([0] + takes[:-1]))]
+    Smax = max(len(s.src) for s in slots)
     Tmax = max_tgt or max(128, 100 * max(s.n_masks for s in spans) + 8)
     model.eval()
     tokens = steps = 0
@@ -1519,56 +1604,29 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
         kv_reads = None
         # (the template and clock kernels serve vocabularies up to 512 tokens, as the sampler
         # does: a templated or clocked greedy call above that runs the host loop below)
-        if greedy and device_grammar and (vocab.vocab_size <= 512 or (
-                _device_templates(spans) is None and _device_bars(spans) is None)):
-            keep, cls = grammar_tables(vocab, all_controls)
-            m0 = vocab.char2index('m_0')
-            ts = time.perf_counter()
-            res = sess.greedy_decode(spans, keep, cls, eos=vocab.eos_index, m0=m0,
-                                     bans=_device_bans(spans), score=score,
-                                     templates=_device_templates(spans), bars=_device_bars(spans))
-            t_dev = time.perf_counter() - ts
-            seqs, steps = res.ids, res.steps
-            # completion time of each request from the call's start: host
-            # preparation + prefill, then the GPU end time of its last step
-            latency = [(ts - t0) + (res.step_ms[len(q) - 1] / 1000.0 if q else 0.0) for q in seqs]
-            if np.any(res.err):
-                raise ValueError("decoder prefix exceeds session max_tgt %d" % (sess.Tmax - 1))
-            # key rows the decode steps attended to (SURVEY §8d infill bytes):
-            # request r's i-th step reads its S_r memory rows and i+1 prefix rows
-            # (a memory shared by several takes is read once per step in
-            # which one of them is live)
-            kv_reads = int(sum(len(q) * (len(q) + 1) // 2 for q in seqs))
-            k0 = 0
-            for src, n in zip(srcs, takes or [1] * R):
-                kv_reads += max(len(q) for q in seqs[k0:k0 + n]) * len(src)
-                k0 += n
-            tokens += _replay(spans, res, logger, sampled=False)
-        elif device_grammar and vocab.vocab_size <= 512:
-            keep, cls = grammar_tables(vocab, all_controls)
-            rng0 = np.random.get_state() if seeds is None else None
-            ts = time.perf_counter()
-            res = sess.sampled_decode(
-                spans, keep, reject_table(vocab), cls, eos=vocab.eos_index,
-                m0=vocab.char2index('m_0'), t=[a for a, _ in tps], p=[b for _, b in tps],
-                seeds=seeds, bans=_device_bans(spans), score=score, templates=_device_templates(spans),
-                bars=_device_bars(spans))
-            t_dev = time.perf_counter() - ts
-            if np.any(res.err & 2):
-                # some row's probabilities missed 1 by more than 1e-9
-                # (np.random.choice territory): same RNG start, fresh spans,
-                # and the whole batch goes through the host loop below
-                # (seeded: fresh_spans starts fresh RandomStates instead)
-                if seeds is None:
-                    np.random.set_state(rng0)
+        if device_grammar and (vocab.vocab_size <= 512 or (
+                greedy and all(sp.tpl is None for sp in spans) and _device_bars(spans) is None)):
+            done = _decode_on_device(sess, spans, vocab, all_controls, logger, greedy, seeds, score)
+            if done is None:  # same RNG start, fresh spans: the whole batch goes through the host loop below
                 spans = fresh_spans()
                 prefill()
-                t_dev = 0.0
             else:
-                if np.any(res.err & 1):
-                    raise ValueError("decoder prefix exceeds session max_tgt %d" % (sess.Tmax - 1))
-                steps = res.steps
-                tokens += _replay(spans, res, logger)
+                n, res, ts, te = done
+                tokens, steps, t_dev = tokens + n, res.steps, te - ts
+            if done is not None and greedy:
+                seqs = res.ids
+                # completion time of each request from the call's start: host
+                # preparation + prefill, then the GPU end time of its last step
+                latency = [(ts - t0) + (res.step_ms[len(q) - 1] / 1000.0 if q else 0.0) for q in seqs]
+                # key rows the decode steps attended to (SURVEY §8d infill bytes):
+                # request r's i-th step reads its S_r memory rows and i+1 prefix rows
+                # (a memory shared by several takes is read once per step in
+                # which one of them is live)
+                kv_reads = int(sum(len(q) * (len(q) + 1) // 2 for q in seqs))
+                k0 = 0
+                for src, n in zip(srcs, takes or [1] * R):
+                    kv_reads += max(len(q) for q in seqs[k0:k0 + n]) * len(src)
+                    k0 += n
         while True:
             live = [i for i in range(R) if not spans[i].done]
             if not live:
@@ -1582,26 +1640,18 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
             lg = sess.step(feeds)
             t_dev += time.perf_counter() - ts
             if greedy:
-                # one masked argmax over all live rows (same ids as the
-                # per-row float64 softmax argmax: exp/normalise is monotone)
-                specs = [spans[i].spec() for i in live]
-                keep = np.stack([allowed_ids(vocab, **f) for f, _, _ in specs])
-                for k, i in enumerate(live):
-                    ban = spans[i].ban()
-                    if ban is not None:
-                        keep[k] &= ~ban
-                x = np.where(keep, lg, np.float32(-100.0))
-                for k, i in enumerate(live):  # the bar clock and the template rewrite the masked row; the score below reads lg and keep
-                    cb = spans[i].clock_ban()
-                    if cb is not None:
-                        x[k][cb] = np.float32(-100.0)
-                    force = spans[i].forced()
-                    if force is not None:
-                        x[k] = _forced(x[k], vocab, force)
+                # one masked argmax over all live rows, in float32 (same ids as
+                # the per-row float64 softmax argmax: exp/normalise is monotone)
+                codes = [spans[i].state_code() for i in live]
+                specs = [grammar_spec(vocab, c) for c in codes]
+                govs = [spans[i]._governs(c, spans[i]._ban_index()) for i, c in zip(live, codes)]
+                x = masked_row(lg, np.stack([g[0] for g in govs]), dtype=np.float32)  # steps 1-2, all rows at once
+                for k, (_, cb, force) in enumerate(govs):
+                    if cb is not None or force is not None:  # steps 3-4 of the rows that have them
+                        x[k] = masked_row(x[k], True, cb, force, vocab, np.float32)
                 ids = np.argmax(x, axis=1)
                 for k, i in enumerate(live):
-                    if score:  # the argmax is taken outside _draw: score it from the same keep row
-                        spans[i].logp.append(token_logprobs(lg[k], keep[k])[ids[k]])
+                    spans[i].scored(lg[k], govs[k][0], ids[k])  # (the argmax is taken outside advance())
                     spans[i].commit_greedy(ids[k], specs[k][1], specs[k][2])
             else:
                 for k, i in enumerate(live):
@@ -1609,37 +1659,36 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
             tokens += len(live)
             steps += 1
     out = []
-    for q, st in zip(preps, spans):
+    for s, st in zip(slots, spans):
         if st.n_masks == 0:
             out.append(None)
             continue
-        out.append((restore_marked_input(_src_tokens(vocab, q[0]), st.total), q[1], q[2]))
+        out.append((restore_marked_input(_src_tokens(vocab, s.src), st.total), s.mask_track_names,
+                    s.mask_bar_names))
     lp_all = [np.asarray(st.logp, dtype=np.float64) for st in spans] if score else None
     order = None
     if takes is not None:  # entry i: the list of request i's takes
         nested, order, k0 = [], [], 0
         for n in takes:
-            ks = _rank_order(lp_all[k0:k0 + n]) if rank else list(range(n))
+            ks = _rank_order(lp_all[k0:k0 + n]) if rq.rank else list(range(n))
             order.append(ks)
             nested.append(None if out[k0] is None else [out[k0 + k] for k in ks])
             k0 += n
         out = nested
-    if return_stats:
-        t3 = time.perf_counter()
-        extra = {}
-        if score:
-            extra = {"logprobs": lp_all, "scores": [float(np.sum(a)) for a in lp_all]}
-        if rank:
-            extra["order"] = order
-        if any(bar_lens):
-            extra["bar_fill"] = [list(st.fill) if st.bar_len else None for st in spans]
-        return out, {**extra, "tokens": tokens, "steps": steps, "prepare_s": t1 - t0,
-                     "prefill_s": t2 - t1, "decode_s": t3 - t2, "step_call_s": t_dev,
-                     "request_latency_s": latency, "kv_row_reads": kv_reads,
-                     "generated": [list(st.total) for st in spans],
-                     "seeds": seeds, "pitches": allowed, "sources": len(srcs), "prefill_rows": int(sess.prefill_rows),
-                     "decode_phases_s": dict(sess.phase_s)}
-    return out
+    t3 = time.perf_counter()
+    extra = {}
+    if score:
+        extra = {"logprobs": lp_all, "scores": [float(np.sum(a)) for a in lp_all]}
+    if rq.rank:
+        extra["order"] = order
+    if any(s.bar_len for s in slots):
+        extra["bar_fill"] = [list(st.fill) if st.bar_len else None for st in spans]
+    return out, {**extra, "tokens": tokens, "steps": steps, "prepare_s": t1 - t0,
+                 "prefill_s": t2 - t1, "decode_s": t3 - t2, "step_call_s": t_dev,
+                 "request_latency_s": latency, "kv_row_reads": kv_reads,
+                 "generated": [list(st.total) for st in spans],
+                 "seeds": seeds, "pitches": rq.allowed, "sources": len(srcs), "prefill_rows": int(sess.prefill_rows),
+                 "decode_phases_s": dict(sess.phase_s)}
 
 
 # --------------------------------------------------------------------------
@@ -1769,17 +1818,16 @@ def _forced_plan(vocab, src, target, all_controls, no_whole, bodies, bans=None):
                        None if sp.ban_rows is None else np.asarray(sp.ban_rows, dtype=bool))
 
 
-def _score_plan(vocab, events, tracks_to_generate, bars_to_generate, all_controls, content, allowed):
-    """The plan of one request from its events: `_prepare`'s masked source
-    and, with content None, the events' own content at the masked positions
-    (`decoder_targets` of the events `_prepare` masked, empty bars filled in
-    where it fills them).  Host only."""
+def _request_bodies(vocab, events, tracks_to_generate, bars_to_generate, content, allowed, what):
+    """(src, target, no_whole, ban rows, bodies) of one request: its masked
+    form, and `content` as a list of bodies -- with None the events' own content
+    at the masked positions (`decoder_targets` of the events `_prepare` masked,
+    empty bars filled in where it fills them).  Host only."""
     events = list(events)
     if len(bars_to_generate) == 0 or len(tracks_to_generate) == 0:
-        raise ValueError("nothing is masked: there is nothing to score")
-    bans = _request_bans(vocab, events, tracks_to_generate, bars_to_generate, allowed)
-    # (fill_empty_bars appends to the list it is given: `events` is the masked song afterwards)
-    src, _, _, target, no_whole = _prepare(events, vocab, tracks_to_generate, bars_to_generate)
+        raise ValueError("nothing is masked: there is nothing to %s" % what)
+    (src, _, _, target, no_whole), bans = _masked_request(vocab, events, tracks_to_generate, bars_to_generate,
+                                                          allowed)
     if content is None:
         _, tracks = mask_targets(events, tracks_to_generate, bars_to_generate)
         bodies = _split_targets(vocab, decoder_targets(events, vocab, tracks, bars_to_generate))
@@ -1787,14 +1835,14 @@ def _score_plan(vocab, events, tracks_to_generate, bars_to_generate, all_control
         if isinstance(content, (str, bytes)) or not hasattr(content, "__len__"):
             raise ValueError("content: one token sequence per mask (got %r)" % (content,))
         bodies = list(content)
+    return src, target, no_whole, bans, bodies
+
+
+def _score_plan(vocab, events, tracks_to_generate, bars_to_generate, all_controls, content, allowed):
+    """The plan of one request from its events."""
+    src, target, no_whole, bans, bodies = _request_bodies(vocab, events, tracks_to_generate, bars_to_generate,
+                                                          content, allowed, "score")
     return _forced_plan(vocab, src, target, all_controls, no_whole, _content_ids(vocab, bodies), bans)
-
-
-def _plan_keep(vocab, plan, n):
-    """The boolean keep of entry n: allowed_ids of its state, & ~ban."""
-    keep = allowed_ids(vocab, **grammar_spec(vocab, int(plan.code[n]))[0])
-    k = int(plan.ban_idx[n])
-    return keep if k < 0 else keep & ~plan.ban_rows[k]
 
 
 def _host_scores(vocab, plan, logits):
@@ -1804,10 +1852,11 @@ def _host_scores(vocab, plan, logits):
     lp = np.empty(len(plan.ids), dtype=np.float64)
     arg = np.empty(len(plan.ids), dtype=np.int64)
     for n in range(len(plan.ids)):
-        keep = _plan_keep(vocab, plan, n)
+        k = int(plan.ban_idx[n])
+        keep = _state_keep(vocab, int(plan.code[n]), None if k < 0 else plan.ban_rows[k])
         r = logits[int(plan.row[n])]
         lp[n] = token_logprobs(r, keep)[plan.ids[n]]
-        arg[n] = np.argmax(np.where(keep, np.asarray(r, dtype=np.float32).astype(np.float64), -100.0))
+        arg[n] = np.argmax(masked_row(r, keep))
     return lp, arg
 
 
@@ -2033,12 +2082,8 @@ def _check_template(template, vocab, src, target, all_controls, no_whole, bans=N
                     raise ValueError("template: '<eos>' only as the last item of a note span's row (row %d)" % k)
             if i >= MAX_BODY and x != sp.eos:
                 raise ValueError("template: row %d holds more than %d body items" % (k, MAX_BODY))
-            flags, check, _ = sp.spec()
-            keep = allowed_ids(vocab, **flags)
-            ban = sp.ban()
-            if ban is not None:
-                keep = keep & ~ban
-            cb = sp.clock_ban()
+            check, ban = sp.spec()[1], sp.ban()
+            keep, cb, _ = sp.governs()
             if cb is not None:
                 if cb[sp.v.pitch_indices[0]] if x is ANY_PITCH else cb[x]:
                     raise ValueError("template: row %d, item %d: fill_bar does not allow %s there (the bar holds "
@@ -2071,18 +2116,8 @@ def _template_bodies(events, vocab, tracks_to_generate, bars_to_generate, conten
     """(bodies as id lists, target codes) of a request for the template
     builders: `content` in score_infill's format, or with None the events' own
     content at the masked positions."""
-    events = list(events)
-    if len(bars_to_generate) == 0 or len(tracks_to_generate) == 0:
-        raise ValueError("nothing is masked: there is nothing to build a template from")
-    # (fill_empty_bars appends to the list it is given: `events` is the masked song afterwards)
-    src, _, _, target, _ = _prepare(events, vocab, tracks_to_generate, bars_to_generate)
-    if content is None:
-        _, tracks = mask_targets(events, tracks_to_generate, bars_to_generate)
-        bodies = _split_targets(vocab, decoder_targets(events, vocab, tracks, bars_to_generate))
-    else:
-        if isinstance(content, (str, bytes)) or not hasattr(content, "__len__"):
-            raise ValueError("content: one token sequence per mask (got %r)" % (content,))
-        bodies = list(content)
+    src, target, _, _, bodies = _request_bodies(vocab, events, tracks_to_generate, bars_to_generate, content,
+                                                None, "build a template from")
     n = int(np.sum(np.asarray(src) == vocab.char2index('m_0')))
     if len(bodies) != n or len(target) < n:
         raise ValueError("content: %d spans for %d masks" % (len(bodies), n))
