@@ -192,6 +192,40 @@ int smer_gemm_plan(int dtype, int a_kcontig, int b_kcontig, int M, int N, int K,
                    long ldcf, size_t ws_bytes, int max_workgroups, int cus, int* plan);
 const char* smer_gemm_kernel_name(int kernel);
 
+/* Diagnostics: what smer_attn_fwd / _bwd (and their _fp8 forms) and the six
+ * decode-attention entries would launch for a call, from the same decision
+ * the launchers run (csrc/attn_plan.h), without launching and without a HIP
+ * call.  facts: the SMER_ATTN_PLAN_* bits that hold for the call (the 7-bit
+ * drop threshold is not 0, a keep-word buffer is passed, drop_mask_in, the
+ * e4m3 copy is asked for, fp32: q, k 16-B aligned with ldq, ldk % 4 == 0,
+ * causal).
+ *  fwd plan: family (0 bf16 flash, 1 fp32 MFMA, 2 fp32 VALU, -1 none), D, QG,
+ *   DROP, MIN, Q8, grid x, grid y, block, LDS bytes, mask generator first.
+ *  bwd plan: family, dQ first, separate delta pass, block, then D, G, DROP,
+ *   MSK, CAUSAL, grid x, grid y of the dQ and of the dK/dV kernel, then the
+ *   four grids of the fp32 sequence (delta, P / dS, dK / dV, dQ).
+ *  decode plan: entry 0 decode, 1 qln, 2 shared, 3 shared_qln, 4 split_f32,
+ *   5 split_qln_f32; vec_ok: smer_attn_decode's 16-B layout holds (pointers
+ *   and strides).  kind (0 generic, 1 vec, 2 shared), fp32, LPK, UNR, NW,
+ *   PIPE, QP, NS, grid x, y, z, block, LDS bytes, odd rows first.
+ *  smer_linear_decode_ln_plan: UNR, NC, KF of smer_linear_decode_ln's kernel;
+ *   skinny_kf 0 / 1, or -1 for the process's SMER_SKINNY_KF.
+ * Used by the attention and decode edge tests. */
+#define SMER_ATTN_PLAN_DROP 0x1
+#define SMER_ATTN_PLAN_MASK 0x2
+#define SMER_ATTN_PLAN_MASK_IN 0x4
+#define SMER_ATTN_PLAN_Q8 0x8
+#define SMER_ATTN_PLAN_F32_ALIGNED 0x10
+#define SMER_ATTN_PLAN_CAUSAL 0x20
+#define SMER_ATTN_FWD_PLAN_INTS 11
+#define SMER_ATTN_BWD_PLAN_INTS 22
+#define SMER_ATTN_DECODE_PLAN_INTS 14
+int smer_attn_fwd_plan(int dtype, int B, int H, int Lq, int Lk, int D, unsigned facts, int* plan);
+int smer_attn_bwd_plan(int dtype, int B, int H, int Lq, int Lk, int D, unsigned facts, int* plan);
+int smer_attn_decode_plan(int entry, int dtype, int D, int n_rows, int H, int n_groups, int dmodel,
+                          long row_stride, long req_stride, long head_stride, int vec_ok, int* plan);
+int smer_linear_decode_ln_plan(int K, int skinny_kf, int* plan);
+
 /* Flash attention over [B*L, *] token-row layouts (row = b*L + i), head h
  * at column h*D.  kpm: uint8 [B, Lk] (1 = padded key) or NULL.  causal:
  * key j visible to query i iff j <= i.  lse: fp32 [B, H, Lq] (natural log).

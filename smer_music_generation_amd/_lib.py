@@ -29,6 +29,11 @@ SIGNATURES = {
     "smer_gemm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint, c_long, c_size, c_int,
                                c_int, P]),
     "smer_gemm_kernel_name": (ctypes.c_char_p, [c_int]),
+    "smer_attn_fwd_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint, P]),
+    "smer_attn_bwd_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint, P]),
+    "smer_attn_decode_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_long, c_long, c_long,
+                                      c_int, P]),
+    "smer_linear_decode_ln_plan": (c_int, [c_int, c_int, P]),
     "smer_gemm_wgrad_bias": (c_int, [c_int, c_int, c_int, c_int, P, c_long, P, c_long, P, c_long,
                                      c_int, P, c_int, P, c_size, P]),
     "smer_embed_fwd_fp8": (c_int, [c_int, c_int, P, P, c_int, P, P, c_float, c_float, c_u32, P, c_long, P, c_long,

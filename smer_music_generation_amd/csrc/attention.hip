@@ -2191,43 +2191,29 @@ static void mask_gen_launch(int B, int H, int Lq, int Lk, uint32_t thr, uint32_t
 }
 
 // ---------------------------------------------------------------------------
-// C-ABI
+// C-ABI.  attn_plan.h decides the kernel instantiation, grid, block and LDS
+// bytes of a call from a query and the AttnSwitches; every entry validates,
+// fills its query, asks, and launches what the plan names.  smer_attn_fwd_plan
+// / _bwd_plan / _decode_plan return the same plans unlaunched.
 // ---------------------------------------------------------------------------
+#include <algorithm>
+
+#include "attn_plan.h"
+static_assert(ap::KVB == KVB && ap::DEC_SHARED_G == DEC_SHARED_G, "attn_plan.h: geometry differs from the kernels'");
+
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-template <int D>
-static void fwd_bf16_launch(int B, int H, int Lq, int Lk, const void* q, long ldq, const void* k,
-                            long ldk, const void* v, long ldv, void* o, long ldo, float* lse,
-                            const uint8_t* kpm, int causal, float scale, uint32_t thr,
-                            uint32_t seed, float ds, uint64_t* mask, int mask_in, const AttnQ8& q8,
-                            hipStream_t s) {
-  // two query groups per wave once there are enough blocks to fill the chip
-  const bool qg2 = (long)((Lq + 127) / 128) * B * H >= 512 && D <= 64;
-  dim3 grid(qg2 ? (Lq + 127) / 128 : (Lq + 63) / 64, B * H);
-  // a mask buffer: the keep words come from the generator (launched here
-  // first unless the caller already filled them) and the backward reads the
-  // same words; no buffer: the forward hashes them itself
-  // with a mask buffer the QG = 2 forward hashes the keep bits in its loop
-  // and publishes them (cheaper than the separate generator: C2 encoder
-  // forward + generator 125 + 29 us vs ~14x us hashing + publishing); a
-  // QG = 1 wave holds half a 32-query block, so there the generator fills
-  // the buffer and the forward reads it
-  const bool min_ = thr && mask && (mask_in || !qg2);
-  if (min_ && !mask_in) mask_gen_launch(B, H, Lq, Lk, thr, seed, mask, s);
-  auto kern = qg2 ? (min_ ? attn_fwd_bf16<D, 2, true, true>
-                          : (thr ? attn_fwd_bf16<D, 2, true> : attn_fwd_bf16<D, 2, false>))
-                  : (min_ ? attn_fwd_bf16<D, 1, true, true>
-                          : (thr ? attn_fwd_bf16<D, 1, true> : attn_fwd_bf16<D, 1, false>));
-  if constexpr (D == 64) {
-    if (q8.dq)
-      kern = qg2 ? (min_ ? attn_fwd_bf16<D, 2, true, true, true>
-                         : (thr ? attn_fwd_bf16<D, 2, true, false, true> : attn_fwd_bf16<D, 2, false, false, true>))
-                 : (min_ ? attn_fwd_bf16<D, 1, true, true, true>
-                         : (thr ? attn_fwd_bf16<D, 1, true, false, true> : attn_fwd_bf16<D, 1, false, false, true>));
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, B, H, Lq, Lk, (const bf16*)q, ldq,
-                     (const bf16*)k, ldk, (const bf16*)v, ldv, (bf16*)o, ldo, lse, kpm, causal,
-                     scale, thr, seed, ds, thr ? (uint64_t*)mask : nullptr, q8);
+// The one reader of the environment for the dispatch: the switches in
+// `which` are read (per call), the others keep their defaults, so no entry
+// reads a switch it does not use.
+enum { SW_F32_MFMA = 1, SW_PIPE_SMALL = 2, SW_ODD_FIRST = 4 };
+static AttnSwitches attn_switches(int which) {
+  auto on = [](const char* e) { return !(e && e[0] == '0'); };
+  AttnSwitches sw;
+  if (which & SW_F32_MFMA) sw.f32_mfma = on(getenv("SMER_ATTN_F32_MFMA"));
+  if (which & SW_PIPE_SMALL) sw.dec_pipe_small = on(getenv("SMER_DEC_PIPE_SMALL"));
+  if (which & SW_ODD_FIRST) sw.dec_odd_first = on(getenv("SMER_DECODE_ODD_FIRST"));
+  return sw;
 }
 
 // [bh][query 32-block][key 64-tile][64 lanes] u32 words (attn_mask_word):
@@ -2247,11 +2233,21 @@ extern "C" int smer_attn_drop_mask_gen(int B, int H, int Lq, int Lk, float drop_
   return SMER_OK;
 }
 
-// SMER_ATTN_F32_MFMA=0 keeps the fp32 forward on attn_fwd_f32 (A/B, tests)
-static bool smer_attn_f32_mfma() {
-  const char* e = getenv("SMER_ATTN_F32_MFMA");
-  return !(e && e[0] == '0');
+// attn_fwd_bf16<D, QG, DROP, MIN, Q8> of a plan (Q8 at D = 64 only)
+typedef decltype(&attn_fwd_bf16<64, 1, false>) FwdKernel;
+template <int D, int QG, bool Q8>
+static FwdKernel fwd_variant(const AttnFwdPlan& p) {
+  return p.MIN ? attn_fwd_bf16<D, QG, true, true, Q8>
+               : p.DROP ? attn_fwd_bf16<D, QG, true, false, Q8> : attn_fwd_bf16<D, QG, false, false, Q8>;
 }
+template <int D>
+static FwdKernel fwd_kernel(const AttnFwdPlan& p) {
+  if constexpr (D == 64)
+    if (p.Q8) return p.QG == 2 ? fwd_variant<D, 2, true>(p) : fwd_variant<D, 1, true>(p);
+  return p.QG == 2 ? fwd_variant<D, 2, false>(p) : fwd_variant<D, 1, false>(p);
+}
+
+static AttnFwdPlan fwd_plan_of(const AttnQuery& q) { return attn_fwd_plan(q, attn_switches(q.f32 ? SW_F32_MFMA : 0)); }
 
 static int attn_fwd_impl(int dtype, int B, int H, int Lq, int Lk, int D, const void* q, long ldq,
                          const void* k, long ldk, const void* v, long ldv, void* o, long ldo,
@@ -2267,27 +2263,33 @@ static int attn_fwd_impl(int dtype, int B, int H, int Lq, int Lk, int D, const v
   hipStream_t s = (hipStream_t)stream;
   uint32_t thr = smer_attn_thr7(drop_p);
   float ds = smer_attn_scale7(thr);
+  AttnQuery fq;
+  fq.f32 = dtype == SMER_F32; fq.B = B; fq.H = H; fq.Lq = Lq; fq.Lk = Lk; fq.D = D;
+  fq.drop = thr != 0; fq.mask = drop_mask != nullptr; fq.mask_in = drop_mask_in != 0; fq.q8 = q8.dq != nullptr;
+  fq.f32_aligned = al16(q) && al16(k) && ldq % 4 == 0 && ldk % 4 == 0;
+  const AttnFwdPlan p = fwd_plan_of(fq);
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
   if (dtype == SMER_BF16) {
     SMER_REQUIRE(al16(q) && al16(k) && al16(v), "smer_attn_fwd: 16-B alignment");
     SMER_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0,
                  "smer_attn_fwd: row strides must be multiples of 8");
-    if (D == 32) fwd_bf16_launch<32>(B, H, Lq, Lk, q, ldq, k, ldk, v, ldv, o, ldo, lse, kpm, causal, scale, thr, seed, ds, (uint64_t*)drop_mask, drop_mask_in, q8, s);
-    else if (D == 64) fwd_bf16_launch<64>(B, H, Lq, Lk, q, ldq, k, ldk, v, ldv, o, ldo, lse, kpm, causal, scale, thr, seed, ds, (uint64_t*)drop_mask, drop_mask_in, q8, s);
-    else if (D == 128) fwd_bf16_launch<128>(B, H, Lq, Lk, q, ldq, k, ldk, v, ldv, o, ldo, lse, kpm, causal, scale, thr, seed, ds, (uint64_t*)drop_mask, drop_mask_in, q8, s);
-    else return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_attn_fwd(bf16): head dim must be 32, 64 or 128");
+    if (p.family != AF_BF16_FLASH)
+      return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_attn_fwd(bf16): head dim must be 32, 64 or 128");
+    if (p.mask_gen) mask_gen_launch(B, H, Lq, Lk, thr, seed, drop_mask, s);
+    const FwdKernel kern = p.D == 32 ? fwd_kernel<32>(p) : p.D == 64 ? fwd_kernel<64>(p) : fwd_kernel<128>(p);
+    hipLaunchKernelGGL(kern, grid, block, 0, s, B, H, Lq, Lk, (const bf16*)q, ldq, (const bf16*)k, ldk,
+                       (const bf16*)v, ldv, (bf16*)o, ldo, lse, kpm, causal, scale, thr, seed, ds,
+                       thr ? (uint64_t*)drop_mask : nullptr, q8);
   } else if (dtype == SMER_F32) {
-    if (D == 64 && thr == 0 && al16(q) && al16(k) && ldq % 4 == 0 && ldk % 4 == 0 && smer_attn_f32_mfma()) {
-      dim3 grid((Lq + 63) / 64, B * H);
-      hipLaunchKernelGGL(attn_fwd_f32_mfma, grid, dim3(256), 0, s, B, H, Lq, Lk, (const float*)q, ldq,
+    if (p.family == AF_F32_MFMA) {
+      hipLaunchKernelGGL(attn_fwd_f32_mfma, grid, block, 0, s, B, H, Lq, Lk, (const float*)q, ldq,
                          (const float*)k, ldk, (const float*)v, ldv, (float*)o, ldo, lse, kpm, causal, scale);
-      SMER_CHECK_LAUNCH("smer_attn_fwd");
-      return SMER_OK;
+    } else {
+      SMER_REQUIRE(p.lds <= ap::FWD_F32_LDS_MAX, "smer_attn_fwd(f32): Lk too large");
+      hipLaunchKernelGGL(attn_fwd_f32, grid, block, p.lds, s, B, H, Lq, Lk, D, (const float*)q, ldq,
+                         (const float*)k, ldk, (const float*)v, ldv, (float*)o, ldo, lse, kpm, causal,
+                         scale, thr, seed, ds);
     }
-    SMER_REQUIRE((size_t)Lk * 16 <= 160 * 1024, "smer_attn_fwd(f32): Lk too large");
-    dim3 grid((Lq + 3) / 4, B * H);
-    hipLaunchKernelGGL(attn_fwd_f32, grid, dim3(256), (size_t)Lk * 16, s, B, H, Lq, Lk, D,
-                       (const float*)q, ldq, (const float*)k, ldk, (const float*)v, ldv,
-                       (float*)o, ldo, lse, kpm, causal, scale, thr, seed, ds);
   } else {
     return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_attn_fwd: dtype");
   }
@@ -2325,44 +2327,30 @@ extern "C" size_t smer_attn_bwd_workspace(int dtype, int B, int H, int Lq, int L
 }
 
 #ifndef SMER_DQ_DELTA
-#define SMER_DQ_DELTA 1
+#define SMER_DQ_DELTA 1  // 0 (A/B builds): separate delta pass, dK / dV kernel first
 #endif
-template <int D>
-static void bwd_bf16_launch(int B, int H, int Lq, int Lk, const void* q, long ldq, const void* k,
-                            long ldk, const void* v, long ldv, const void* dout, long lddo,
-                            const float* lse, float* delta, const uint8_t* kpm, int causal,
-                            float scale, uint32_t thr, uint32_t seed, float ds, void* dq,
-                            long lddq, void* dk, long lddk, void* dv, long lddv,
-                            const uint64_t* mask, const void* o, long ldo, const AttnQ8& q8,
-                            hipStream_t s) {
-  if (!thr) mask = nullptr;
-  // two key groups per wave once there are enough blocks to fill the chip
-  const bool kg2 = (long)((Lk + 127) / 128) * B * H >= 512 && D <= 64;
-  // dropout variants: recompute the keep bits by hashing, or read the
-  // forward's stored bits (MSK); causal and non-causal instances
-#define SMER_BWD_PICK(K, G, C)                                                        \
-  (!thr ? K<D, false, G, false, C> : mask ? K<D, true, G, true, C> : K<D, true, G, false, C>)
-  const bool cz = causal != 0;
-  auto kdkdv = kg2 ? (cz ? SMER_BWD_PICK(attn_bwd_dkdv_bf16, 2, true) : SMER_BWD_PICK(attn_bwd_dkdv_bf16, 2, false))
-                   : (cz ? SMER_BWD_PICK(attn_bwd_dkdv_bf16, 1, true) : SMER_BWD_PICK(attn_bwd_dkdv_bf16, 1, false));
-  const bool qg2 = (long)((Lq + 127) / 128) * B * H >= 512 && D <= 64;
-  auto kdq = qg2 ? (cz ? SMER_BWD_PICK(attn_bwd_dq_bf16, 2, true) : SMER_BWD_PICK(attn_bwd_dq_bf16, 2, false))
-                 : (cz ? SMER_BWD_PICK(attn_bwd_dq_bf16, 1, true) : SMER_BWD_PICK(attn_bwd_dq_bf16, 1, false));
-#undef SMER_BWD_PICK
-  // o != null: the dQ kernel forms delta = rowsum(dO * O) itself and runs
-  // first (no separate delta pass); else delta was written beforehand
-  auto launch_dq = [&] {
-    hipLaunchKernelGGL(kdq, dim3(qg2 ? (Lq + 127) / 128 : (Lq + 63) / 64, B * H), dim3(256), 0, s, B, H,
-                       Lq, Lk, (const bf16*)q, ldq, (const bf16*)k, ldk, (const bf16*)v, ldv,
-                       (const bf16*)dout, lddo, lse, delta, kpm, causal, scale, thr, seed, ds,
-                       (bf16*)dq, lddq, mask, (const bf16*)o, ldo, q8);
-  };
-  if (o) launch_dq();
-  hipLaunchKernelGGL(kdkdv, dim3(kg2 ? (Lk + 127) / 128 : (Lk + 63) / 64, B * H), dim3(256), 0, s, B, H, Lq,
-                     Lk, (const bf16*)q, ldq, (const bf16*)k, ldk, (const bf16*)v, ldv,
-                     (const bf16*)dout, lddo, lse, delta, kpm, causal, scale, thr, seed, ds,
-                     (bf16*)dk, lddk, (bf16*)dv, lddv, mask, q8);
-  if (!o) launch_dq();
+// attn_bwd_dq_bf16 / attn_bwd_dkdv_bf16<D, DROP, G, MSK, CAUSAL> of a plan
+struct DqKernel {
+  template <int D, bool DROP, int G, bool MSK, bool C>
+  static auto get() { return &attn_bwd_dq_bf16<D, DROP, G, MSK, C>; }
+};
+struct DkdvKernel {
+  template <int D, bool DROP, int G, bool MSK, bool C>
+  static auto get() { return &attn_bwd_dkdv_bf16<D, DROP, G, MSK, C>; }
+};
+template <class K, int D, int G, bool C>
+static auto bwd_variant(const AttnBwdKernel& k) {
+  return !k.DROP ? K::template get<D, false, G, false, C>()
+                 : k.MSK ? K::template get<D, true, G, true, C>() : K::template get<D, true, G, false, C>();
+}
+template <class K, int D>
+static auto bwd_kernel_d(const AttnBwdKernel& k) {
+  return k.G == 2 ? (k.CAUSAL ? bwd_variant<K, D, 2, true>(k) : bwd_variant<K, D, 2, false>(k))
+                  : (k.CAUSAL ? bwd_variant<K, D, 1, true>(k) : bwd_variant<K, D, 1, false>(k));
+}
+template <class K>
+static auto bwd_kernel(const AttnBwdKernel& k) {
+  return k.D == 32 ? bwd_kernel_d<K, 32>(k) : k.D == 64 ? bwd_kernel_d<K, 64>(k) : bwd_kernel_d<K, 128>(k);
 }
 
 static int attn_bwd_impl(int dtype, int B, int H, int Lq, int Lk, int D, const void* q,
@@ -2382,34 +2370,44 @@ static int attn_bwd_impl(int dtype, int B, int H, int Lq, int Lk, int D, const v
   uint32_t thr = smer_attn_thr7(drop_p);
   float ds = smer_attn_scale7(thr);
   float* delta = (float*)workspace;
-  long nrow = (long)B * H * Lq;
+  AttnQuery bq;
+  bq.f32 = dtype == SMER_F32; bq.B = B; bq.H = H; bq.Lq = Lq; bq.Lk = Lk; bq.D = D;
+  bq.drop = thr != 0; bq.mask = drop_mask != nullptr; bq.causal = causal != 0; bq.dq_delta = SMER_DQ_DELTA;
+  const AttnBwdPlan p = attn_bwd_plan(bq, AttnSwitches{});
+  const dim3 block(p.block);
   if (dtype == SMER_BF16) {
     SMER_REQUIRE(al16(q) && al16(k) && al16(v) && al16(dout), "smer_attn_bwd: 16-B alignment");
     SMER_REQUIRE(al16(o) && ldo % 8 == 0 && lddo % 8 == 0, "smer_attn_bwd: O/dO alignment");
-    // SMER_DQ_DELTA=0 (A/B builds): separate delta pass, dK / dV kernel first
-    const void* of = SMER_DQ_DELTA ? o : nullptr;
-    if (!of) launch_delta<bf16>(B, H, Lq, D, o, ldo, dout, lddo, delta, s);
-    if (D == 32) bwd_bf16_launch<32>(B, H, Lq, Lk, q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, kpm, causal, scale, thr, seed, ds, dq, lddq, dk, lddk, dv, lddv, (const uint64_t*)drop_mask, of, ldo, q8, s);
-    else if (D == 64) bwd_bf16_launch<64>(B, H, Lq, Lk, q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, kpm, causal, scale, thr, seed, ds, dq, lddq, dk, lddk, dv, lddv, (const uint64_t*)drop_mask, of, ldo, q8, s);
-    else if (D == 128) bwd_bf16_launch<128>(B, H, Lq, Lk, q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, kpm, causal, scale, thr, seed, ds, dq, lddq, dk, lddk, dv, lddv, (const uint64_t*)drop_mask, of, ldo, q8, s);
-    else return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_attn_bwd(bf16): head dim must be 32, 64 or 128");
+    if (p.delta_pass) launch_delta<bf16>(B, H, Lq, D, o, ldo, dout, lddo, delta, s);
+    if (p.family != AF_BF16_FLASH)
+      return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_attn_bwd(bf16): head dim must be 32, 64 or 128");
+    const uint64_t* mask = thr ? (const uint64_t*)drop_mask : nullptr;
+    auto launch_dq = [&] {  // (given O, it forms delta itself)
+      hipLaunchKernelGGL(bwd_kernel<DqKernel>(p.dq), dim3(p.dq.grid_x, p.dq.grid_y), block, 0, s, B, H, Lq, Lk,
+                         (const bf16*)q, ldq, (const bf16*)k, ldk, (const bf16*)v, ldv, (const bf16*)dout, lddo,
+                         lse, delta, kpm, causal, scale, thr, seed, ds, (bf16*)dq, lddq, mask,
+                         (const bf16*)(p.dq_first ? o : nullptr), ldo, q8);
+    };
+    if (p.dq_first) launch_dq();
+    hipLaunchKernelGGL(bwd_kernel<DkdvKernel>(p.dkdv), dim3(p.dkdv.grid_x, p.dkdv.grid_y), block, 0, s, B, H, Lq,
+                       Lk, (const bf16*)q, ldq, (const bf16*)k, ldk, (const bf16*)v, ldv, (const bf16*)dout,
+                       lddo, lse, delta, kpm, causal, scale, thr, seed, ds, (bf16*)dk, lddk, (bf16*)dv, lddv,
+                       mask, q8);
+    if (!p.dq_first) launch_dq();
   } else if (dtype == SMER_F32) {
-    hipLaunchKernelGGL(attn_delta_scalar<float>, dim3((nrow + 255) / 256), dim3(256), 0, s, B, H,
-                       Lq, D, (const float*)o, ldo, (const float*)dout, lddo, delta);
-    size_t doff = ((size_t)nrow * sizeof(float) + 255) & ~(size_t)255;
+    hipLaunchKernelGGL(attn_delta_scalar<float>, dim3(p.f32_grid[0]), block, 0, s, B, H, Lq, D,
+                       (const float*)o, ldo, (const float*)dout, lddo, delta);
+    size_t doff = ((size_t)B * H * Lq * sizeof(float) + 255) & ~(size_t)255;
     float* ws_p = (float*)((char*)workspace + doff);
     float* ws_s = ws_p + (size_t)B * H * Lq * Lk;
-    long tot = (long)B * H * Lq * Lk;
-    hipLaunchKernelGGL(attn_bwd_ps_f32, dim3((tot + 255) / 256), dim3(256), 0, s, B, H, Lq, Lk, D,
+    hipLaunchKernelGGL(attn_bwd_ps_f32, dim3(p.f32_grid[1]), block, 0, s, B, H, Lq, Lk, D,
                        (const float*)q, ldq, (const float*)k, ldk, (const float*)v, ldv,
                        (const float*)dout, lddo, lse, delta, kpm, causal, scale, thr, seed, ds,
                        ws_p, ws_s);
-    long tk = (long)B * H * Lk * D;
-    hipLaunchKernelGGL(attn_bwd_kv_f32, dim3((tk + 255) / 256), dim3(256), 0, s, B, H, Lq, Lk, D,
+    hipLaunchKernelGGL(attn_bwd_kv_f32, dim3(p.f32_grid[2]), block, 0, s, B, H, Lq, Lk, D,
                        (const float*)q, ldq, (const float*)dout, lddo, ws_p, ws_s, scale,
                        (float*)dk, lddk, (float*)dv, lddv);
-    long tq = (long)B * H * Lq * D;
-    hipLaunchKernelGGL(attn_bwd_q_f32, dim3((tq + 255) / 256), dim3(256), 0, s, B, H, Lq, Lk, D,
+    hipLaunchKernelGGL(attn_bwd_q_f32, dim3(p.f32_grid[3]), block, 0, s, B, H, Lq, Lk, D,
                        (const float*)k, ldk, ws_s, scale, (float*)dq, lddq);
   } else {
     return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_attn_bwd: dtype");
@@ -2472,15 +2470,93 @@ extern "C" int smer_attn_weights(int dtype, int B, int H, int Lq, int Lk, int D,
   return SMER_OK;
 }
 
-// SMER_DECODE_ODD_FIRST=0: blocks in plain row order (A/B)
-// SMER_DEC_PIPE_SMALL=0: grids of <= 128 blocks take the unpipelined form
-static bool smer_dec_pipe_small() {
-  const char* e = getenv("SMER_DEC_PIPE_SMALL");
-  return !(e && e[0] == '0');
+// ---- decode.  The plan of an entry (the switches it reads: reads[entry]),
+// the arguments the vec and shared kernels share, and one launch per family
+static DecPlan dec_plan_of(int entry, bool f32, int D, int n_rows, int H, int n_groups, int dmodel,
+                           long row_stride, long req_stride, long head_stride, bool vec_ok) {
+  static const int reads[DE_COUNT] = {SW_PIPE_SMALL | SW_ODD_FIRST, SW_ODD_FIRST, SW_PIPE_SMALL, 0, 0, 0};
+  DecQuery q;
+  q.entry = entry; q.f32 = f32; q.D = D; q.n_rows = n_rows; q.H = H; q.n_groups = n_groups; q.dmodel = dmodel;
+  q.row_stride = row_stride; q.req_stride = req_stride; q.head_stride = head_stride; q.vec_ok = vec_ok;
+  return attn_decode_plan(q, attn_switches(reads[entry]));
 }
-static int smer_dec_odd_first() {
-  const char* e = getenv("SMER_DECODE_ODD_FIRST");
-  return (e && e[0] == '0') ? 0 : 1;
+
+struct DecArgs {
+  const void* q;  // null with a query prologue (dq)
+  long ldq;
+  const void *kc, *vc;
+  long row_stride, req_stride, head_stride;
+  const int32_t *row_req, *row_nkeys;
+  void* o;
+  long ldo;
+  float scale;
+  DecQ dq;
+  float* part;  // the split entries' records
+  int n_rows;   // the shared kernel's: rows, group table
+  const int32_t* group_tab;
+  int n_groups;
+};
+
+// the two kernel families' launches (the shared kernel is bf16 only)
+struct DecVec {
+  template <typename T, int L, int U, int W, bool P, int QP = 0, int NS = 0>
+  static bool go(const DecPlan& p, const DecArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL((attn_decode_vec_kernel<T, L, U, W, P, QP, NS>), dim3(p.grid_x, p.grid_y, p.grid_z),
+                       dim3(p.block), 0, s, (const T*)a.q, a.ldq, (const T*)a.kc, (const T*)a.vc, a.row_stride,
+                       a.req_stride, a.head_stride, a.row_req, a.row_nkeys, (T*)a.o, a.ldo, a.scale, a.dq, p.odd,
+                       a.part);
+    return true;
+  }
+};
+struct DecShared {
+  template <typename T, int L, int U, int W, bool P, int QP = 0>
+  static bool go(const DecPlan& p, const DecArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL((attn_decode_shared_kernel<L, U, W, P, QP, DEC_SHARED_G>), dim3(p.grid_x, p.grid_y),
+                       dim3(p.block), 0, s, a.n_rows, (const T*)a.q, a.ldq, (const T*)a.kc, (const T*)a.vc,
+                       a.row_stride, a.req_stride, a.head_stride, a.row_req, a.row_nkeys, a.group_tab, a.n_groups,
+                       (T*)a.o, a.ldo, a.scale, a.dq);
+    return true;
+  }
+};
+
+// the compiled instantiations; false: the plan names none of them
+template <class K, typename T, int L>
+static bool dec_form(const DecPlan& p, const DecArgs& a, hipStream_t s) {
+  if (p.UNR == 4 && p.NW == 8)
+    return p.PIPE ? K::template go<T, L, 4, 8, true>(p, a, s) : K::template go<T, L, 4, 8, false>(p, a, s);
+  return p.UNR == 2 && p.NW == 4 && !p.PIPE && K::template go<T, L, 2, 4, false>(p, a, s);
+}
+template <class K, bool P>  // the query-prologue forms
+static bool dec_qln(const DecPlan& p, const DecArgs& a, hipStream_t s) {
+  if (p.f32 || p.LPK != 8 || p.UNR != 4 || p.NW != 8) return false;
+  return p.QP == 512 ? K::template go<bf16, 8, 4, 8, P, 512>(p, a, s)
+                     : p.QP == 768 ? K::template go<bf16, 8, 4, 8, P, 768>(p, a, s)
+                                   : p.QP == 1024 && K::template go<bf16, 8, 4, 8, P, 1024>(p, a, s);
+}
+template <typename T>
+static bool dec_vec_lpk(const DecPlan& p, const DecArgs& a, hipStream_t s) {
+  return p.LPK == 4 ? dec_form<DecVec, T, 4>(p, a, s)
+                    : p.LPK == 8 ? dec_form<DecVec, T, 8>(p, a, s) : p.LPK == 16 && dec_form<DecVec, T, 16>(p, a, s);
+}
+
+static int dec_launch(const DecPlan& p, const DecArgs& a, smer_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const bool sh = p.kind == DK_SHARED;
+  bool ok;
+  if (p.NS)  // the split forms
+    ok = !sh && p.f32 && p.LPK == 16 && p.UNR == 2 && p.NW == 4 && p.PIPE && p.NS == ap::DEC_SPLITS &&
+         (p.QP == 0 ? DecVec::go<float, 16, 2, 4, true, 0, ap::DEC_SPLITS>(p, a, s)
+                    : p.QP == 512 && DecVec::go<float, 16, 2, 4, true, 512, ap::DEC_SPLITS>(p, a, s));
+  else if (p.QP)
+    ok = sh ? (p.PIPE ? dec_qln<DecShared, true>(p, a, s) : dec_qln<DecShared, false>(p, a, s))
+            : (p.PIPE ? dec_qln<DecVec, true>(p, a, s) : dec_qln<DecVec, false>(p, a, s));
+  else if (sh)
+    ok = p.LPK == 4 ? dec_form<DecShared, bf16, 4>(p, a, s) : p.LPK == 8 && dec_form<DecShared, bf16, 8>(p, a, s);
+  else
+    ok = p.kind == DK_VEC && (p.f32 ? dec_vec_lpk<float>(p, a, s) : dec_vec_lpk<bf16>(p, a, s));
+  if (!ok) return smer_set_error(SMER_ERR_UNSUPPORTED, "attention decode: the plan names no compiled kernel");
+  SMER_CHECK_LAUNCH("smer_attn_decode*");
+  return SMER_OK;
 }
 
 // fp32 decode attention over NS = 8 key slices per (row, head): partial
@@ -2492,24 +2568,14 @@ extern "C" int smer_attn_decode_split_f32(int n_rows, int H, int D, const void* 
                                           float scale, smer_stream_t stream) {
   SMER_REQUIRE(D == 64 && H > 0, "smer_attn_decode_split_f32: head dim 64");
   SMER_REQUIRE(q && kcache && vcache && row_req && row_nkeys && part, "smer_attn_decode_split_f32: null pointer");
-  auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  SMER_REQUIRE(al(q) && al(kcache) && al(vcache) && al(part) && ldq % 4 == 0 && row_stride % 4 == 0 &&
+  SMER_REQUIRE(al16(q) && al16(kcache) && al16(vcache) && al16(part) && ldq % 4 == 0 && row_stride % 4 == 0 &&
                    req_stride % 4 == 0 && (head_stride <= 0 || head_stride % 4 == 0),
                "smer_attn_decode_split_f32: alignment / strides");
   if (n_rows == 0) return SMER_OK;
   if (head_stride <= 0) head_stride = D;
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(H, n_rows, 8);
-  // pipelined key loads (the next key step requested before this step's
-  // math; the same arithmetic as the unpipelined form, so the same bits):
-  // batch-1 plugin call 2,621 vs 2,534 tokens/s (two rounds,
-  // tools/batch1_bench.py env SMER_DEC_SPLIT_CFG; 8-wave and 4-step forms
-  // 2,558-2,607)
-  hipLaunchKernelGGL((attn_decode_vec_kernel<float, 16, 2, 4, true, 0, 8>), grid, dim3(256), 0, s, (const float*)q,
-                     ldq, (const float*)kcache, (const float*)vcache, row_stride, req_stride, head_stride, row_req,
-                     row_nkeys, (float*)nullptr, 0L, scale, DecQ{}, 0, part);
-  SMER_CHECK_LAUNCH("smer_attn_decode_split_f32");
-  return SMER_OK;
+  const DecPlan p = dec_plan_of(DE_SPLIT_F32, true, D, n_rows, H, 0, 0, row_stride, req_stride, head_stride, true);
+  return dec_launch(p, DecArgs{q, ldq, kcache, vcache, row_stride, req_stride, head_stride, row_req, row_nkeys,
+                               nullptr, 0L, scale, DecQ{}, part, n_rows, nullptr, 0}, stream);
 }
 
 // smer_attn_decode_split_f32 with the cross-attention query projection and
@@ -2528,21 +2594,16 @@ extern "C" int smer_attn_decode_split_qln_f32(int n_rows, int H, int D, const fl
   SMER_REQUIRE(dmodel == 512, "smer_attn_decode_split_qln_f32: d_model 512 (else: Linear + split attention)");
   SMER_REQUIRE(y && gamma && beta && wq && bq && kcache && vcache && row_req && row_nkeys && part,
                "smer_attn_decode_split_qln_f32: null pointer");
-  auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  SMER_REQUIRE(al(y) && al(gamma) && al(beta) && al(wq) && al(kcache) && al(vcache) && al(part) &&
-                   (!x_out || al(x_out)) && ldy % 4 == 0 && ldw % 4 == 0 && ldx % 4 == 0 && row_stride % 4 == 0 &&
+  SMER_REQUIRE(al16(y) && al16(gamma) && al16(beta) && al16(wq) && al16(kcache) && al16(vcache) && al16(part) &&
+                   (!x_out || al16(x_out)) && ldy % 4 == 0 && ldw % 4 == 0 && ldx % 4 == 0 && row_stride % 4 == 0 &&
                    req_stride % 4 == 0 && (head_stride <= 0 || head_stride % 4 == 0),
                "smer_attn_decode_split_qln_f32: 16-B alignment / strides");
   if (n_rows == 0) return SMER_OK;
   if (head_stride <= 0) head_stride = D;
-  DecQ dq{y, ldy, gamma, beta, eps, wq, ldw, bq, x_out, ldx, dmodel};
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(H, n_rows, 8);
-  hipLaunchKernelGGL((attn_decode_vec_kernel<float, 16, 2, 4, true, 512, 8>), grid, dim3(256), 0, s,
-                     (const float*)nullptr, 0L, (const float*)kcache, (const float*)vcache, row_stride, req_stride,
-                     head_stride, row_req, row_nkeys, (float*)nullptr, 0L, scale, dq, 0, part);
-  SMER_CHECK_LAUNCH("smer_attn_decode_split_qln_f32");
-  return SMER_OK;
+  const DecQ dq{y, ldy, gamma, beta, eps, wq, ldw, bq, x_out, ldx, dmodel};
+  const DecPlan p = dec_plan_of(DE_SPLIT_QLN_F32, true, D, n_rows, H, 0, dmodel, row_stride, req_stride, head_stride, true);
+  return dec_launch(p, DecArgs{nullptr, 0L, kcache, vcache, row_stride, req_stride, head_stride, row_req, row_nkeys,
+                               nullptr, 0L, scale, dq, part, n_rows, nullptr, 0}, stream);
 }
 
 extern "C" int smer_attn_decode_qln(int n_rows, int H, int D, const void* y, long ldy,
@@ -2557,38 +2618,16 @@ extern "C" int smer_attn_decode_qln(int n_rows, int H, int D, const void* y, lon
                "smer_attn_decode_qln: d_model 512 / 768 / 1024 (else: Linear + smer_attn_decode)");
   SMER_REQUIRE(y && gamma && beta && wq && bq && kcache && vcache && o && row_req && row_nkeys,
                "smer_attn_decode_qln: null pointer");
-  auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  SMER_REQUIRE(al(y) && al(wq) && al(kcache) && al(vcache) && al(o) && (!x_out || al(x_out)) &&
+  SMER_REQUIRE(al16(y) && al16(wq) && al16(kcache) && al16(vcache) && al16(o) && (!x_out || al16(x_out)) &&
                    ldy % 8 == 0 && ldw % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0 && row_stride % 8 == 0 &&
                    req_stride % 8 == 0 && head_stride % 8 == 0,
                "smer_attn_decode_qln: 16-B alignment / strides");
   if (n_rows == 0) return SMER_OK;
   if (head_stride <= 0) head_stride = D;
-  DecQ dq{y, ldy, gamma, beta, eps, wq, ldw, bq, x_out, ldx, dmodel};
-  const int odd = smer_dec_odd_first();
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(H, n_rows);
-  // long memories (>= 2048 key rows of capacity): next key step's loads
-  // issued before the current step's math, as smer_attn_decode
-  const long cap_rows = head_stride != D ? head_stride / (row_stride > 0 ? row_stride : 1)
-                                         : req_stride / (row_stride > 0 ? row_stride : 1);
-  const bool pipe = cap_rows >= 2048;
-#define SMER_DEC_QLN(P, DM)                                                                        \
-  hipLaunchKernelGGL((attn_decode_vec_kernel<bf16, 8, 4, 8, P, DM>), grid, dim3(512), 0, s,        \
-                     (const bf16*)nullptr, 0L, (const bf16*)kcache, (const bf16*)vcache, row_stride, \
-                     req_stride, head_stride, row_req, row_nkeys, (bf16*)o, ldo, scale, dq, odd)
-  if (pipe) {
-    if (dmodel == 512) SMER_DEC_QLN(true, 512);
-    else if (dmodel == 768) SMER_DEC_QLN(true, 768);
-    else SMER_DEC_QLN(true, 1024);
-  } else {
-    if (dmodel == 512) SMER_DEC_QLN(false, 512);
-    else if (dmodel == 768) SMER_DEC_QLN(false, 768);
-    else SMER_DEC_QLN(false, 1024);
-  }
-#undef SMER_DEC_QLN
-  SMER_CHECK_LAUNCH("smer_attn_decode_qln");
-  return SMER_OK;
+  const DecQ dq{y, ldy, gamma, beta, eps, wq, ldw, bq, x_out, ldx, dmodel};
+  const DecPlan p = dec_plan_of(DE_QLN, false, D, n_rows, H, 0, dmodel, row_stride, req_stride, head_stride, true);
+  return dec_launch(p, DecArgs{nullptr, 0L, kcache, vcache, row_stride, req_stride, head_stride, row_req, row_nkeys,
+                               o, ldo, scale, dq, nullptr, n_rows, nullptr, 0}, stream);
 }
 
 extern "C" int smer_attn_decode(int dtype, int n_rows, int H, int D, const void* q, long ldq,
@@ -2599,62 +2638,23 @@ extern "C" int smer_attn_decode(int dtype, int n_rows, int H, int D, const void*
   SMER_REQUIRE(D <= 256, "smer_attn_decode: head dim <= 256");
   if (n_rows == 0) return SMER_OK;
   if (head_stride <= 0) head_stride = D;  // heads side by side within a key row
-  {
-    // vectorised path: 16-B aligned rows, LPK = D / (16 / elem) in {4, 8, 16}
-    const int es = dtype == SMER_BF16 ? 2 : 4, vec = 16 / es;
-    auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-    const bool ok = (dtype == SMER_BF16 || dtype == SMER_F32) && D % vec == 0 && al(q) &&
-                    al(kcache) && al(vcache) && al(o) && ldq % vec == 0 && ldo % vec == 0 &&
-                    row_stride % vec == 0 && req_stride % vec == 0 && head_stride % vec == 0;
-    const int lpk = D / vec;
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid(H, n_rows);  // the H blocks of a row read the same K/V rows together
-    // key capacity of a request (cache rows): long memories get 8 waves x
-    // 4 steps of loads in flight per block, short self-attention caches 4 x 2
-    const long cap_rows = head_stride != D ? head_stride / (row_stride > 0 ? row_stride : 1)
-                                           : req_stride / (row_stride > 0 ? row_stride : 1);
-    // pipelined loads also for few blocks (the batch-1 plugin step: 16
-    // blocks stream a ~1k-key memory each); the same arithmetic as the
-    // unpipelined 8-wave form, so the logits do not depend on the batch
-    const bool big = cap_rows >= 512;
-    const bool pipe = cap_rows >= 2048 || (big && (long)n_rows * H <= 128 && smer_dec_pipe_small());
-    const int odd = smer_dec_odd_first();
-#define SMER_DEC_VEC(T, L)                                                                        \
-  if (pipe)                                                                                       \
-    hipLaunchKernelGGL((attn_decode_vec_kernel<T, L, 4, 8, true>), grid, dim3(512), 0, s,         \
-                       (const T*)q, ldq, (const T*)kcache, (const T*)vcache, row_stride,          \
-                       req_stride, head_stride, row_req, row_nkeys, (T*)o, ldo, scale, DecQ{}, odd); \
-  else if (big)                                                                                   \
-    hipLaunchKernelGGL((attn_decode_vec_kernel<T, L, 4, 8>), grid, dim3(512), 0, s, (const T*)q,  \
-                       ldq, (const T*)kcache, (const T*)vcache, row_stride, req_stride,            \
-                       head_stride, row_req, row_nkeys, (T*)o, ldo, scale, DecQ{}, odd);          \
-  else                                                                                            \
-    hipLaunchKernelGGL((attn_decode_vec_kernel<T, L, 2, 4>), grid, dim3(256), 0, s, (const T*)q,  \
-                       ldq, (const T*)kcache, (const T*)vcache, row_stride, req_stride,            \
-                       head_stride, row_req, row_nkeys, (T*)o, ldo, scale, DecQ{}, odd)
-    if (ok && (lpk == 4 || lpk == 8 || lpk == 16)) {
-      if (dtype == SMER_BF16) {
-        if (lpk == 4) SMER_DEC_VEC(bf16, 4); else if (lpk == 8) SMER_DEC_VEC(bf16, 8); else SMER_DEC_VEC(bf16, 16);
-      } else {
-        if (lpk == 4) SMER_DEC_VEC(float, 4); else if (lpk == 8) SMER_DEC_VEC(float, 8); else SMER_DEC_VEC(float, 16);
-      }
-#undef SMER_DEC_VEC
-      SMER_CHECK_LAUNCH("smer_attn_decode");
-      return SMER_OK;
-    }
-  }
-  // key capacity bounded by req_stride / row_stride rows
-  long cap = (head_stride != D ? head_stride : req_stride) / (row_stride > 0 ? row_stride : 1);
-  SMER_REQUIRE(cap > 0 && cap * 4 <= 150 * 1024, "smer_attn_decode: cache capacity too large");
+  const int vec = dtype == SMER_BF16 ? 8 : 4;
+  const bool ok = (dtype == SMER_BF16 || dtype == SMER_F32) && al16(q) && al16(kcache) && al16(vcache) && al16(o) &&
+                  ldq % vec == 0 && ldo % vec == 0 && row_stride % vec == 0 && req_stride % vec == 0 &&
+                  head_stride % vec == 0;
+  const DecPlan p = dec_plan_of(DE_DECODE, dtype != SMER_BF16, D, n_rows, H, 0, 0, row_stride, req_stride, head_stride, ok);
+  if (p.kind == DK_VEC)
+    return dec_launch(p, DecArgs{q, ldq, kcache, vcache, row_stride, req_stride, head_stride, row_req, row_nkeys,
+                                 o, ldo, scale, DecQ{}, nullptr, n_rows, nullptr, 0}, stream);
+  SMER_REQUIRE(p.cap > 0 && p.lds <= ap::DEC_GENERIC_LDS_MAX, "smer_attn_decode: cache capacity too large");
   hipStream_t s = (hipStream_t)stream;
-  size_t shm = (size_t)cap * sizeof(float);
-  dim3 grid(n_rows, H);
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
   if (dtype == SMER_BF16)
-    hipLaunchKernelGGL(attn_decode_kernel<bf16>, grid, dim3(256), shm, s, H, D, (const bf16*)q, ldq,
+    hipLaunchKernelGGL(attn_decode_kernel<bf16>, grid, block, p.lds, s, H, D, (const bf16*)q, ldq,
                        (const bf16*)kcache, (const bf16*)vcache, row_stride, req_stride,
                        head_stride, row_req, row_nkeys, (bf16*)o, ldo, scale);
   else if (dtype == SMER_F32)
-    hipLaunchKernelGGL(attn_decode_kernel<float>, grid, dim3(256), shm, s, H, D, (const float*)q,
+    hipLaunchKernelGGL(attn_decode_kernel<float>, grid, block, p.lds, s, H, D, (const float*)q,
                        ldq, (const float*)kcache, (const float*)vcache, row_stride, req_stride,
                        head_stride, row_req, row_nkeys, (float*)o, ldo, scale);
   else
@@ -2665,8 +2665,7 @@ extern "C" int smer_attn_decode(int dtype, int n_rows, int H, int D, const void*
 
 // Decode cross attention over shared memories (attn_decode_shared_kernel):
 // the variant by cache capacity exactly as smer_attn_decode / _qln choose
-// theirs, so each row's bits are those entries'.  Grid: every group has at
-// most one partial chunk, so n_rows / G + n_groups chunks bound any split.
+// theirs, so each row's bits are those entries'.
 static bool dec_shared_args_ok(int n_rows, int n_groups, const int32_t* group_tab) {
   return n_rows >= 0 && n_groups >= 0 && (n_groups == 0 || group_tab);
 }
@@ -2682,30 +2681,12 @@ extern "C" int smer_attn_decode_shared(int dtype, int n_rows, int H, int D, cons
   if (n_rows == 0 || n_groups == 0) return SMER_OK;
   SMER_REQUIRE(q && kcache && vcache && o && row_req && row_nkeys, "smer_attn_decode_shared: null pointer");
   if (head_stride <= 0) head_stride = D;
-  auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  SMER_REQUIRE(al(q) && al(kcache) && al(vcache) && al(o) && ldq % 8 == 0 && ldo % 8 == 0 &&
+  SMER_REQUIRE(al16(q) && al16(kcache) && al16(vcache) && al16(o) && ldq % 8 == 0 && ldo % 8 == 0 &&
                    row_stride % 8 == 0 && req_stride % 8 == 0 && head_stride % 8 == 0,
                "smer_attn_decode_shared: 16-B alignment / strides");
-  hipStream_t s = (hipStream_t)stream;
-  constexpr int G = DEC_SHARED_G;
-  dim3 grid(H, n_rows / G + n_groups);
-  const long cap_rows = head_stride != D ? head_stride / (row_stride > 0 ? row_stride : 1)
-                                         : req_stride / (row_stride > 0 ? row_stride : 1);
-  const bool big = cap_rows >= 512;
-  const bool pipe = cap_rows >= 2048 || (big && (long)n_rows * H <= 128 && smer_dec_pipe_small());
-#define SMER_DEC_SH(L, U, W, P)                                                                      \
-  hipLaunchKernelGGL((attn_decode_shared_kernel<L, U, W, P, 0, G>), grid, dim3(64 * W), 0, s, n_rows, \
-                     (const bf16*)q, ldq, (const bf16*)kcache, (const bf16*)vcache, row_stride,      \
-                     req_stride, head_stride, row_req, row_nkeys, group_tab, n_groups, (bf16*)o, ldo, \
-                     scale, DecQ{})
-  if (D == 32) {
-    if (pipe) SMER_DEC_SH(4, 4, 8, true); else if (big) SMER_DEC_SH(4, 4, 8, false); else SMER_DEC_SH(4, 2, 4, false);
-  } else {
-    if (pipe) SMER_DEC_SH(8, 4, 8, true); else if (big) SMER_DEC_SH(8, 4, 8, false); else SMER_DEC_SH(8, 2, 4, false);
-  }
-#undef SMER_DEC_SH
-  SMER_CHECK_LAUNCH("smer_attn_decode_shared");
-  return SMER_OK;
+  const DecPlan p = dec_plan_of(DE_SHARED, false, D, n_rows, H, n_groups, 0, row_stride, req_stride, head_stride, true);
+  return dec_launch(p, DecArgs{q, ldq, kcache, vcache, row_stride, req_stride, head_stride, row_req, row_nkeys,
+                               o, ldo, scale, DecQ{}, nullptr, n_rows, group_tab, n_groups}, stream);
 }
 
 extern "C" int smer_attn_decode_shared_qln(int n_rows, int H, int D, const void* y, long ldy,
@@ -2724,34 +2705,54 @@ extern "C" int smer_attn_decode_shared_qln(int n_rows, int H, int D, const void*
   SMER_REQUIRE(y && gamma && beta && wq && bq && kcache && vcache && o && row_req && row_nkeys,
                "smer_attn_decode_shared_qln: null pointer");
   if (head_stride <= 0) head_stride = D;
-  auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  SMER_REQUIRE(al(y) && al(gamma) && al(beta) && al(wq) && al(kcache) && al(vcache) && al(o) &&
-                   (!x_out || al(x_out)) && ldy % 8 == 0 && ldw % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0 &&
+  SMER_REQUIRE(al16(y) && al16(gamma) && al16(beta) && al16(wq) && al16(kcache) && al16(vcache) && al16(o) &&
+                   (!x_out || al16(x_out)) && ldy % 8 == 0 && ldw % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0 &&
                    row_stride % 8 == 0 && req_stride % 8 == 0 && head_stride % 8 == 0,
                "smer_attn_decode_shared_qln: 16-B alignment / strides");
-  DecQ dq{y, ldy, gamma, beta, eps, wq, ldw, bq, x_out, ldx, dmodel};
-  hipStream_t s = (hipStream_t)stream;
-  constexpr int G = DEC_SHARED_G;
-  dim3 grid(H, n_rows / G + n_groups);
-  const long cap_rows = head_stride != D ? head_stride / (row_stride > 0 ? row_stride : 1)
-                                         : req_stride / (row_stride > 0 ? row_stride : 1);
-  const bool pipe = cap_rows >= 2048;
-#define SMER_DEC_SHQ(P, DM)                                                                          \
-  hipLaunchKernelGGL((attn_decode_shared_kernel<8, 4, 8, P, DM, G>), grid, dim3(512), 0, s, n_rows,  \
-                     (const bf16*)nullptr, 0L, (const bf16*)kcache, (const bf16*)vcache, row_stride, \
-                     req_stride, head_stride, row_req, row_nkeys, group_tab, n_groups, (bf16*)o, ldo, \
-                     scale, dq)
-  if (pipe) {
-    if (dmodel == 512) SMER_DEC_SHQ(true, 512);
-    else if (dmodel == 768) SMER_DEC_SHQ(true, 768);
-    else SMER_DEC_SHQ(true, 1024);
-  } else {
-    if (dmodel == 512) SMER_DEC_SHQ(false, 512);
-    else if (dmodel == 768) SMER_DEC_SHQ(false, 768);
-    else SMER_DEC_SHQ(false, 1024);
-  }
-#undef SMER_DEC_SHQ
-  SMER_CHECK_LAUNCH("smer_attn_decode_shared_qln");
+  const DecQ dq{y, ldy, gamma, beta, eps, wq, ldw, bq, x_out, ldx, dmodel};
+  const DecPlan p = dec_plan_of(DE_SHARED_QLN, false, D, n_rows, H, n_groups, dmodel, row_stride, req_stride, head_stride, true);
+  return dec_launch(p, DecArgs{nullptr, 0L, kcache, vcache, row_stride, req_stride, head_stride, row_req, row_nkeys,
+                               o, ldo, scale, dq, nullptr, n_rows, group_tab, n_groups}, stream);
+}
+
+// The plans of the entries above, unlaunched (include/smer_hip.h; no HIP call)
+extern "C" int smer_attn_fwd_plan(int dtype, int B, int H, int Lq, int Lk, int D, unsigned facts, int* plan) {
+  SMER_REQUIRE((dtype == SMER_BF16 || dtype == SMER_F32) && plan, "smer_attn_fwd_plan: dtype / null plan");
+  AttnQuery q;
+  q.f32 = dtype == SMER_F32; q.B = B; q.H = H; q.Lq = Lq; q.Lk = Lk; q.D = D;
+  q.drop = facts & SMER_ATTN_PLAN_DROP; q.mask = facts & SMER_ATTN_PLAN_MASK; q.mask_in = facts & SMER_ATTN_PLAN_MASK_IN;
+  q.q8 = facts & SMER_ATTN_PLAN_Q8; q.f32_aligned = facts & SMER_ATTN_PLAN_F32_ALIGNED;
+  const AttnFwdPlan p = fwd_plan_of(q);
+  const int out[SMER_ATTN_FWD_PLAN_INTS] = {p.family, p.D, p.QG, p.DROP, p.MIN, p.Q8, p.grid_x, p.grid_y,
+                                            p.block, (int)p.lds, p.mask_gen};
+  std::copy(out, out + SMER_ATTN_FWD_PLAN_INTS, plan);
+  return SMER_OK;
+}
+
+extern "C" int smer_attn_bwd_plan(int dtype, int B, int H, int Lq, int Lk, int D, unsigned facts, int* plan) {
+  SMER_REQUIRE((dtype == SMER_BF16 || dtype == SMER_F32) && plan, "smer_attn_bwd_plan: dtype / null plan");
+  AttnQuery q;
+  q.f32 = dtype == SMER_F32; q.B = B; q.H = H; q.Lq = Lq; q.Lk = Lk; q.D = D;
+  q.drop = facts & SMER_ATTN_PLAN_DROP; q.mask = facts & SMER_ATTN_PLAN_MASK; q.causal = facts & SMER_ATTN_PLAN_CAUSAL;
+  q.dq_delta = SMER_DQ_DELTA;
+  const AttnBwdPlan p = attn_bwd_plan(q, AttnSwitches{});
+  const AttnBwdKernel &a = p.dq, &b = p.dkdv;
+  const int out[SMER_ATTN_BWD_PLAN_INTS] = {
+      p.family, p.dq_first, p.delta_pass, p.block, a.D, a.G, a.DROP, a.MSK, a.CAUSAL, a.grid_x, a.grid_y,
+      b.D, b.G, b.DROP, b.MSK, b.CAUSAL, b.grid_x, b.grid_y, p.f32_grid[0], p.f32_grid[1], p.f32_grid[2], p.f32_grid[3]};
+  std::copy(out, out + SMER_ATTN_BWD_PLAN_INTS, plan);
+  return SMER_OK;
+}
+
+extern "C" int smer_attn_decode_plan(int entry, int dtype, int D, int n_rows, int H, int n_groups, int dmodel,
+                                     long row_stride, long req_stride, long head_stride, int vec_ok, int* plan) {
+  SMER_REQUIRE(entry >= 0 && entry < DE_COUNT && (dtype == SMER_BF16 || dtype == SMER_F32) && plan,
+               "smer_attn_decode_plan: entry / dtype / null plan");
+  const DecPlan p = dec_plan_of(entry, dtype == SMER_F32, D, n_rows, H, n_groups, dmodel, row_stride, req_stride,
+                                head_stride, vec_ok != 0);
+  const int out[SMER_ATTN_DECODE_PLAN_INTS] = {p.kind, p.f32, p.LPK, p.UNR, p.NW, p.PIPE, p.QP, p.NS,
+                                               p.grid_x, p.grid_y, p.grid_z, p.block, (int)p.lds, p.odd};
+  std::copy(out, out + SMER_ATTN_DECODE_PLAN_INTS, plan);
   return SMER_OK;
 }
 

@@ -22,7 +22,7 @@ OUT = os.path.join(PKG, "libsmer_hip.so")
 DATA_OUT = os.path.join(PKG, "libsmer_data.so")
 OBJ = os.path.join(HERE, "_build")
 SOURCES = ["abi.cpp", "gemm.hip", "attention.hip", "norm_embed.hip", "train_ops.hip", "decode_ops.hip"]
-HEADERS = ["common.h", "gemm_plan.h", os.path.join("..", "..", "include", "smer_hip.h")]
+HEADERS = ["common.h", "gemm_plan.h", "attn_plan.h", os.path.join("..", "..", "include", "smer_hip.h")]
 ARCH = os.environ.get("SMER_OFFLOAD_ARCH", "gfx950")
 
 

@@ -2159,7 +2159,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(int M, int N, int K,
 static_assert(gp::BM == GBM && gp::BN == GBN && gp::BK == GBK && gp::TILE_BYTES == TILE_BYTES &&
                   gp::G64_STAGE == G64_STAGE && gp::G2 == G2 && gp::G2K == G2K && gp::G2_STAGE == G2_STAGE &&
                   gp::G2_LDS == G2_LDS && gp::GS_KS == GS_KS && gp::GS_SLOT == GS_SLOT &&
-                  gp::SK_BM == SK_BM && gp::SK_BN == SK_BN,
+                  gp::SK_BM == SK_BM && gp::SK_BN == SK_BN && gp::LNR_MAXC == LNR_MAXC,
               "gemm_plan.h: tile geometry differs from the kernels'");
 
 // The one reader of the environment for the dispatch: a single pass over
@@ -2841,17 +2841,25 @@ extern "C" int smer_linear_decode_ln(int M, int N, int K, const void* Y, long ld
 #define SKLN(U, NC, KF)                                                                                  \
   hipLaunchKernelGGL((gemm_skinny_ln_kernel<8, U, NC, KF>), grid, dim3(512), lds, s, M, N, K, (const bf16*)Y, \
                      ldy, gamma, beta, eps, (bf16*)X, ldx, (const bf16*)W, ldw, e)
-  if (K % 32 == 0 && gemm_switches_once().skinny_kf) {
-    if (K <= 512) SKLN(2, 1, true);
-    else if (K <= 1024) SKLN(4, 2, true);
+  const SklnPlan p = skln_plan(K, gemm_switches_once().skinny_kf);
+  if (p.KF) {
+    if (p.NC == 1) SKLN(2, 1, true);
+    else if (p.NC == 2) SKLN(4, 2, true);
     else SKLN(4, 4, true);
-  } else if ((K + 31) / 32 > 16) {
+  } else if (p.UNR == 4) {
     SKLN(4, LNR_MAXC, false);
   } else {
     SKLN(2, LNR_MAXC, false);
   }
 #undef SKLN
   SMER_CHECK_LAUNCH("smer_linear_decode_ln");
+  return SMER_OK;
+}
+
+extern "C" int smer_linear_decode_ln_plan(int K, int skinny_kf, int* plan) {
+  SMER_REQUIRE(K > 0 && plan, "smer_linear_decode_ln_plan: K / null plan");
+  const SklnPlan p = skln_plan(K, skinny_kf < 0 ? gemm_switches_once().skinny_kf : skinny_kf != 0);
+  plan[0] = p.UNR; plan[1] = p.NC; plan[2] = p.KF;
   return SMER_OK;
 }
 

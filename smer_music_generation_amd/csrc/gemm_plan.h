@@ -24,6 +24,7 @@ constexpr int GS_SLOT = 2 * G2 * GS_KS * 2;
 constexpr int SK_BM = 64, SK_BN = 16;             // skinny bf16
 constexpr int SKF_BN = 4, SKF_BM = 16, SKF_NW = 4, SKF_UNR = 8;  // skinny fp32
 constexpr size_t TICKET_BYTES = 64 * 1024;        // split-K tickets at the end of a workspace
+constexpr int LNR_MAXC = 4;                       // LayerNorm-prologue Linear: 16-B row chunks per lane
 }  // namespace gp
 
 // Every value the dispatch takes from the environment, at its default.
@@ -279,6 +280,15 @@ inline GemmPlan gemm_plan(const GemmQuery& q, const GemmSwitches& sw) {
   p.kernel = gl ? GK_G128_GLDS : GK_G128_REG;
   p.lds = 4 * TILE_BYTES;
   return p;
+}
+
+// smer_linear_decode_ln's gemm_skinny_ln_kernel<8, UNR, NC, KF>: the K-full
+// forms by row length, else the guarded loads with 4 k-steps in flight past
+// 16 steps (smer_linear_decode_ln_plan)
+struct SklnPlan { int UNR, NC; bool KF; };
+inline SklnPlan skln_plan(int K, bool skinny_kf) {
+  if (K % 32 == 0 && skinny_kf) return K <= 512 ? SklnPlan{2, 1, true} : K <= 1024 ? SklnPlan{4, 2, true} : SklnPlan{4, 4, true};
+  return SklnPlan{gp::cdiv(K, 32) > 16 ? 4 : 2, gp::LNR_MAXC, false};
 }
 
 #endif  // SMER_GEMM_PLAN_H

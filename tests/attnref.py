@@ -2,7 +2,10 @@
 attention kernels (csrc/attention.hip: smer_attn_fwd, smer_attn_bwd,
 smer_attn_weights).  Plain torch on the CPU; tests/test_attention_ref_cpu.py
 checks this file against torch.autograd and derives the bf16 constants below,
-tests/test_attention_edges_gpu.py holds the kernels to them.
+tests/test_attention_edges_gpu.py holds the kernels to them.  expected_fwd_plan
+and expected_bwd_plan state which kernels a call runs (the training dispatch
+of csrc/attn_plan.h, written independently); both test modules hold them
+against the library's own answer (smer_attn_fwd_plan / smer_attn_bwd_plan).
 
 Convention (the kernels' and this file's): a query with no visible key has
 O = 0, lse = +inf and contributes to no gradient; its dQ row is zero.  A
@@ -38,6 +41,7 @@ is what w bounds.
 """
 import functools
 import math
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -351,3 +355,115 @@ def f32_bounds(ref, Lq, Lk, D):
 def bf16_bounds(ref):
     return dict(O=ATTN_REL_O * ref.sO + UB * ref.O.abs(), dQ=ATTN_REL_DQ * ref.sdQ + UB * ref.dQ.abs(),
                 dK=ATTN_REL_DK * ref.sdK + UB * ref.dK.abs(), dV=ATTN_REL_DV * ref.sdV + UB * ref.dV.abs())
+
+
+# --------------------------------------------------------------- dispatch
+F32, BF16 = torch.float32, torch.bfloat16
+FAMILIES = ("bf16_flash", "f32_mfma", "f32_valu")   # smer_attn_fwd_plan's family ids
+FwdPlan = namedtuple("FwdPlan", "family D QG DROP MIN Q8 grid block lds mask_gen")
+BwdKernel = namedtuple("BwdKernel", "D G DROP MSK CAUSAL grid")
+BwdPlan = namedtuple("BwdPlan", "family dq dkdv dq_first delta_pass block f32_grids")
+PLAN_DROP, PLAN_MASK, PLAN_MASK_IN, PLAN_Q8, PLAN_F32_ALIGNED, PLAN_CAUSAL = 1, 2, 4, 8, 16, 32   # include/smer_hip.h
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def two_groups(L, B, H, D):
+    """Two query (or key) groups per wave: enough 128-row blocks to fill the
+    chip, head dim up to 64."""
+    return _cdiv(L, 128) * B * H >= 512 and D <= 64
+
+
+def expected_fwd_plan(dtype, B, H, Lq, Lk, D, drop=False, mask=False, mask_in=False, q8=False, aligned=True,
+                      f32_mfma=True):
+    """What smer_attn_fwd (q8: smer_attn_fwd_fp8) launches.  drop: the rate is
+    not 0; mask: a keep-word buffer is passed, mask_in: already filled;
+    aligned (fp32): q, k 16-B aligned with row strides % 4 == 0; f32_mfma: the
+    SMER_ATTN_F32_MFMA switch.  bf16: attn_fwd_bf16<D, QG, DROP, MIN, Q8> on
+    ceil(Lq / (64 QG)) x B H blocks, the mask generator first when the forward
+    reads a buffer (MIN) the caller did not fill."""
+    if dtype == F32:
+        if D == 64 and not drop and aligned and f32_mfma:
+            return FwdPlan("f32_mfma", D, 1, False, False, False, (_cdiv(Lq, 64), B * H), 256, 0, False)
+        return FwdPlan("f32_valu", D, 1, drop, False, False, (_cdiv(Lq, 4), B * H), 256, 16 * Lk, False)
+    QG = 2 if two_groups(Lq, B, H, D) else 1
+    MIN = drop and mask and (mask_in or QG == 1)
+    return FwdPlan("bf16_flash", D, QG, drop, MIN, q8 and D == 64, (_cdiv(Lq, 64 * QG), B * H), 256, 0,
+                   MIN and not mask_in)
+
+
+def expected_bwd_plan(dtype, B, H, Lq, Lk, D, drop=False, mask=False, causal=False):
+    """What smer_attn_bwd launches.  bf16: attn_bwd_dq_bf16<D, DROP, QG, MSK,
+    CAUSAL> first (it forms delta), then attn_bwd_dkdv_bf16<D, DROP, KG, MSK,
+    CAUSAL>, MSK when the forward's keep words are passed; fp32: delta, P / dS,
+    dK / dV, dQ on one thread per element."""
+    if dtype == F32:
+        n = (B * H * Lq, B * H * Lq * Lk, B * H * Lk * D, B * H * Lq * D)
+        return BwdPlan("f32_valu", None, None, False, False, 256, tuple(_cdiv(x, 256) for x in n))
+
+    def kernel(L):
+        G = 2 if two_groups(L, B, H, D) else 1
+        return BwdKernel(D, G, drop, drop and mask, causal, (_cdiv(L, 64 * G), B * H))
+    return BwdPlan("bf16_flash", kernel(Lq), kernel(Lk), True, False, 256, (0, 0, 0, 0))
+
+
+def _facts(drop, mask, mask_in=False, q8=False, aligned=False, causal=False):
+    return (PLAN_DROP * bool(drop) | PLAN_MASK * bool(mask) | PLAN_MASK_IN * bool(mask_in) | PLAN_Q8 * bool(q8)
+            | PLAN_F32_ALIGNED * bool(aligned) | PLAN_CAUSAL * bool(causal))
+
+
+def library_fwd_plan(lib, dtype, B, H, Lq, Lk, D, drop=False, mask=False, mask_in=False, q8=False, aligned=True):
+    """The library's own decision (smer_attn_fwd_plan: the attn_fwd_plan the
+    launcher runs; nothing launched, no HIP call; SMER_ATTN_F32_MFMA from the
+    environment) in the form of expected_fwd_plan."""
+    import ctypes
+    out = (ctypes.c_int * 11)()
+    rc = lib.smer_attn_fwd_plan(1 if dtype == BF16 else 0, B, H, Lq, Lk, D, _facts(drop, mask, mask_in, q8, aligned), out)
+    assert rc == 0, lib.smer_last_error()
+    fam, D_, QG, DROP, MIN, Q8, gx, gy, block, lds, gen = out
+    return FwdPlan(FAMILIES[fam], D_, QG, bool(DROP), bool(MIN), bool(Q8), (gx, gy), block, lds, bool(gen))
+
+
+def library_bwd_plan(lib, dtype, B, H, Lq, Lk, D, drop=False, mask=False, causal=False):
+    import ctypes
+    out = (ctypes.c_int * 22)()
+    rc = lib.smer_attn_bwd_plan(1 if dtype == BF16 else 0, B, H, Lq, Lk, D, _facts(drop, mask, causal=causal), out)
+    assert rc == 0, lib.smer_last_error()
+    o = list(out)
+    kern = lambda v: BwdKernel(v[0], v[1], bool(v[2]), bool(v[3]), bool(v[4]), (v[5], v[6]))  # noqa: E731
+    f32 = FAMILIES[o[0]] == "f32_valu"
+    return BwdPlan(FAMILIES[o[0]], None if f32 else kern(o[4:11]), None if f32 else kern(o[11:18]), bool(o[1]),
+                   bool(o[2]), o[3], tuple(o[18:22]))
+
+
+def plan_mismatches(lib, setenv):
+    """Every call of the table where library and mirror differ: SHAPES in
+    both dtypes, without dropout and at the shape's drop_rates, with no mask
+    buffer, one to fill and a filled one, the e4m3 copy on and off at
+    D = 64 (bf16), fp32 with SMER_ATTN_F32_MFMA on and off (through
+    `setenv(value or None)`) and with the alignment fact broken."""
+    bad = []
+    for mfma in (None, "1", "0"):
+        setenv(mfma)
+        for shape in SHAPES:
+            B, H, Lq, Lk, D, causal = shape
+            for dtype in (BF16, F32) if mfma is None else (F32,):
+                for drop in (False,) + tuple(bool(p) for p in drop_rates(*shape)):
+                    for mask, mask_in in ((False, False), (True, False), (True, True)):
+                        if mask and not drop:
+                            continue
+                        for q8 in (False, True) if dtype == BF16 and D == 64 else (False,):
+                            for al in (True, False) if dtype == F32 else (True,):
+                                kw = dict(drop=drop, mask=mask, mask_in=mask_in, q8=q8, aligned=al)
+                                m = expected_fwd_plan(dtype, B, H, Lq, Lk, D, f32_mfma=mfma != "0", **kw)
+                                l = library_fwd_plan(lib, dtype, B, H, Lq, Lk, D, **kw)
+                                if m != l:
+                                    bad.append(("fwd", shape, dtype, kw, m, l))
+                        kw = dict(drop=drop, mask=mask, causal=causal)
+                        m, l = expected_bwd_plan(dtype, B, H, Lq, Lk, D, **kw), library_bwd_plan(lib, dtype, B, H, Lq, Lk, D, **kw)
+                        if m != l:
+                            bad.append(("bwd", shape, dtype, kw, m, l))
+    setenv(None)
+    return bad

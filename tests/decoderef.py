@@ -53,9 +53,9 @@ a * b + c the emulation contracts.  It derives the constants and justifies
 the exact-input tests; no kernel is ever compared with it as a pass criterion.
 """
 import math
-import os
 import re
 import zlib
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -104,48 +104,93 @@ def label(kind, dtype=None, L=0, Un=0, W=0, pipe=False, qp=0, ns=0):
     return s
 
 
-def variant_of(entry, dtype, D, row_stride, req_stride, head_stride, ldq, ldo, cap, n_rows, H, dmodel=0):
-    """The kernel instantiation an entry point launches, as a label: a Python
-    mirror of the selection in smer_attn_decode, _qln, _shared, _shared_qln
-    and the two split entries of csrc/attention.hip.  The library has no plan
-    query for attention, so this mirror is checked by reading that code, not
-    by asking the library; test_decode_ref_cpu.py checks that its labels cover
-    every instantiation the dispatch macros name.
+ENTRIES = ("decode", "qln", "shared", "shared_qln", "split", "split_qln")   # smer_attn_decode_plan's entry ids
+ENTRY_DTYPE = dict(qln=BF16, shared=BF16, shared_qln=BF16, split=F32, split_qln=F32)   # (decode takes both)
+ENV_SWITCHES = ("SMER_DEC_PIPE_SMALL", "SMER_DECODE_ODD_FIRST", "SMER_SKINNY_KF")
+SWITCH_DEFAULTS = dict.fromkeys(ENV_SWITCHES, True)
+# what an entry launches: the instantiation as a label, the grid, the block,
+# the generic kernel's LDS bytes, the odd-rows-first argument
+Variant = namedtuple("Variant", "label grid block lds odd")
 
-    The selection also reads the environment: SMER_DEC_PIPE_SMALL=0 turns the
-    pipelined form off for small grids, SMER_DECODE_ODD_FIRST=0 the row
-    permutation, SMER_SKINNY_KF=0 the K-full forms of the LayerNorm-prologue
-    Linear (skln_label).  This mirror describes the defaults; the GPU module
-    asserts that the three variables are unset (ENV_SWITCHES)."""
+
+def variant_of(entry, dtype, D, row_stride, req_stride, head_stride, ldq, ldo, cap, n_rows, H, dmodel=0,
+               n_groups=0, switches=SWITCH_DEFAULTS, aligned=True):
+    """What an entry point launches: a Python mirror, written independently,
+    of the decode dispatch of csrc/attn_plan.h (attn_decode_plan: smer_attn_decode,
+    _qln, _shared, _shared_qln and the two split entries).  It is held against
+    the library's own answer (library_variant, smer_attn_decode_plan) at every
+    case and over decode_queries() by tests/test_decode_ref_cpu.py and, on the
+    device, tests/test_decode_edges_gpu.py.
+
+    `switches`: the values of ENV_SWITCHES (True = on, the default):
+    SMER_DEC_PIPE_SMALL=0 turns the pipelined form off for small grids,
+    SMER_DECODE_ODD_FIRST=0 the row permutation, SMER_SKINNY_KF=0 the K-full
+    forms of the LayerNorm-prologue Linear (skln_label).  `aligned`: q, the
+    caches and o are 16-B aligned."""
+    dtype = ENTRY_DTYPE.get(entry, dtype)
     if head_stride <= 0:
         head_stride = D
     cap_rows = (head_stride if head_stride != D else req_stride) // max(row_stride, 1)
     assert cap_rows == cap, (cap_rows, cap)
-    big = cap_rows >= 512
     if entry in ("split", "split_qln"):
-        return label("vec", F32, 16, 2, 4, True, 512 if entry == "split_qln" else 0, DEC_SPLITS)
+        return Variant(label("vec", F32, 16, 2, 4, True, 512 if entry == "split_qln" else 0, DEC_SPLITS),
+                       (H, n_rows, DEC_SPLITS), 256, 0, 0)
+    odd = int(switches["SMER_DECODE_ODD_FIRST"])
+    shared_grid = (H, n_rows // DEC_SHARED_G + n_groups)
     if entry == "qln":
-        return label("vec", BF16, 8, 4, 8, cap_rows >= 2048, dmodel)
+        return Variant(label("vec", BF16, 8, 4, 8, cap_rows >= 2048, dmodel), (H, n_rows), 512, 0, odd)
     if entry == "shared_qln":
-        return label("shared", None, 8, 4, 8, cap_rows >= 2048, dmodel)
-    pipe = cap_rows >= 2048 or (big and n_rows * H <= 128)
+        return Variant(label("shared", None, 8, 4, 8, cap_rows >= 2048, dmodel), shared_grid, 512, 0, 0)
+    big = cap_rows >= 512
+    pipe = cap_rows >= 2048 or (big and n_rows * H <= 128 and switches["SMER_DEC_PIPE_SMALL"])
+    Un, W = (4, 8) if big else (2, 4)
     if entry == "shared":
-        L = D // 8
-        return label("shared", None, L, 4 if big else 2, 8 if big else 4, pipe)
+        return Variant(label("shared", None, D // 8, Un, W, pipe), shared_grid, 64 * W, 0, 0)
     assert entry == "decode"
     vec = 8 if dtype == BF16 else 4
-    ok = (D % vec == 0 and ldq % vec == 0 and ldo % vec == 0 and row_stride % vec == 0
+    ok = (aligned and D % vec == 0 and ldq % vec == 0 and ldo % vec == 0 and row_stride % vec == 0
           and req_stride % vec == 0 and head_stride % vec == 0 and D // vec in (4, 8, 16))
     if not ok:
-        return label("generic", dtype)
-    return label("vec", dtype, D // vec, 4 if big else 2, 8 if big else 4, pipe)
+        return Variant(label("generic", dtype), (n_rows, H), 256, 4 * cap_rows, 0)
+    return Variant(label("vec", dtype, D // vec, Un, W, pipe), (H, n_rows), 64 * W, 0, odd)
 
 
-def skln_label(K):
+def library_variant(lib, entry, dtype, D, row_stride, req_stride, head_stride, ldq, ldo, cap, n_rows, H, dmodel=0,
+                    n_groups=0, aligned=True):
+    """The library's own decision for the same call (smer_attn_decode_plan:
+    the attn_decode_plan the launchers run; nothing is launched, no HIP call),
+    in the form of variant_of; the switches are the environment's.  The plan
+    query takes smer_attn_decode's "vector layout ok" fact as a flag: it is
+    formed here from the strides and `aligned` as the launcher forms it from
+    the call's strides and pointers."""
+    import ctypes
+    dtype = ENTRY_DTYPE.get(entry, dtype)
+    vec = 8 if dtype == BF16 else 4
+    vec_ok = aligned and all(x % vec == 0 for x in (ldq, ldo, row_stride, req_stride, max(head_stride, 0)))
+    out = (ctypes.c_int * 14)()
+    rc = lib.smer_attn_decode_plan(ENTRIES.index(entry), 1 if dtype == BF16 else 0, D, n_rows, H, n_groups, dmodel,
+                                   row_stride, req_stride, head_stride, int(vec_ok), out)
+    assert rc == 0, lib.smer_last_error()
+    kind, f32_, L, Un, W, pipe, qp, ns, gx, gy, gz, block, lds, odd = out
+    lab = label(("generic", "vec", "shared")[kind], F32 if f32_ else BF16, L, Un, W, bool(pipe), qp, ns)
+    return Variant(lab, (gx, gy) if gz == 1 else (gx, gy, gz), block, lds, odd)
+
+
+def skln_label(K, skinny_kf=True):
     """smer_linear_decode_ln's instantiation of gemm_skinny_ln_kernel."""
-    if K % 32 == 0:
+    if K % 32 == 0 and skinny_kf:
         return "skln U2 NC1 kf" if K <= 512 else "skln U4 NC2 kf" if K <= 1024 else "skln U4 NC4 kf"
     return "skln U4 NC4" if (K + 31) // 32 > 16 else "skln U2 NC4"
+
+
+def library_skln_label(lib, K, skinny_kf):
+    """smer_linear_decode_ln_plan as a label; skinny_kf True / False, or None
+    for the switch as the process read it."""
+    import ctypes
+    out = (ctypes.c_int * 3)()
+    rc = lib.smer_linear_decode_ln_plan(K, -1 if skinny_kf is None else int(skinny_kf), out)
+    assert rc == 0, lib.smer_last_error()
+    return "skln U%d NC%d%s" % (out[0], out[1], " kf" if out[2] else "")
 
 
 def parse_label(lab):
@@ -155,37 +200,6 @@ def parse_label(lab):
         return None
     ns = re.search(r"ns(\d+)", lab)
     return int(m.group(1)), int(m.group(2)), int(m.group(3)), int(ns.group(1)) if ns else 0
-
-
-def dispatch_labels(csrc_dir):
-    """Every instantiation named by the decode dispatch of attention.hip and
-    by smer_linear_decode_ln in gemm.hip, as labels (read from the source)."""
-    a = open(os.path.join(csrc_dir, "attention.hip")).read()
-    out = set()
-    body = re.search(r"#define SMER_DEC_VEC\(T, L\)(.*?)#undef SMER_DEC_VEC", a, re.S).group(1)
-    forms = re.findall(r"attn_decode_vec_kernel<T, L, (\d+), (\d+)(, true)?>", body)
-    assert len(forms) == 3, forms
-    for t, L in set(re.findall(r"SMER_DEC_VEC\((bf16|float), (\d+)\);", body)):
-        for un, w, p in forms:
-            out.add(label("vec", BF16 if t == "bf16" else F32, int(L), int(un), int(w), bool(p)))
-    for t in re.findall(r"attn_decode_kernel<(bf16|float)>", a):
-        out.add(label("generic", BF16 if t == "bf16" else F32))
-    m = re.search(r"attn_decode_vec_kernel<bf16, (\d+), (\d+), (\d+), P, DM>", a)
-    for p, dm in set(re.findall(r"SMER_DEC_QLN\((true|false), (\d+)\);", a)):
-        out.add(label("vec", BF16, int(m.group(1)), int(m.group(2)), int(m.group(3)), p == "true", int(dm)))
-    for L, un, w, p, qp, ns in re.findall(
-            r"attn_decode_vec_kernel<float, (\d+), (\d+), (\d+), (true|false), (\d+), (\d+)>", a):
-        out.add(label("vec", F32, int(L), int(un), int(w), p == "true", int(qp), int(ns)))
-    for L, un, w, p in set(re.findall(r"SMER_DEC_SH\((\d+), (\d+), (\d+), (true|false)\);", a)):
-        out.add(label("shared", None, int(L), int(un), int(w), p == "true"))
-    m = re.search(r"attn_decode_shared_kernel<(\d+), (\d+), (\d+), P, DM, G>", a)
-    for p, dm in set(re.findall(r"SMER_DEC_SHQ\((true|false), (\d+)\);", a)):
-        out.add(label("shared", None, int(m.group(1)), int(m.group(2)), int(m.group(3)), p == "true", int(dm)))
-    g = open(os.path.join(csrc_dir, "gemm.hip")).read()
-    ln = re.search(r"#define SKLN\(U, NC, KF\)(.*?)#undef SKLN", g, re.S).group(1)
-    for un, nc, kf in set(re.findall(r"SKLN\((\d+), (\w+), (true|false)\);", ln)):
-        out.add("skln U%s NC%s%s" % (un, "4" if nc == "LNR_MAXC" else nc, " kf" if kf == "true" else ""))
-    return out
 
 
 # --------------------------------------------------------------------- cases
@@ -251,6 +265,94 @@ SKLN_K = (512, 1024, 2048, 264, 520)   # smer_linear_decode_ln: the three K-full
 
 def case_by_id(cid):
     return next(c for c in CASES if c.id == cid)
+
+
+# The query grid of the dispatch: every value on either side of a threshold
+GRID_D = (16, 24, 32, 64, 128)
+GRID_CAP = (40, 511, 512, 600, 2047, 2048, 2100)
+GRID_BLOCKS = ((64, 2), (43, 3))   # (n_rows, H): 128 and 129 blocks
+GRID_DMODEL = (512, 768, 1024)
+
+
+def entry_accepts(entry, dtype, D, dmodel):
+    """The entry point's own argument checks: what it refuses never reaches
+    the dispatch."""
+    if entry == "decode":
+        return dmodel == 0
+    if dtype != ENTRY_DTYPE[entry]:
+        return False
+    if entry == "shared":
+        return D in (32, 64) and dmodel == 0
+    if entry == "split":
+        return D == 64 and dmodel == 0
+    return D == 64 and (dmodel == 512 if entry == "split_qln" else dmodel in GRID_DMODEL)
+
+
+def query(entry, dtype, D, cap, n_rows, H, dmodel=0, ok=True, n_groups=3):
+    """The arguments of variant_of / library_variant (without the switches) of
+    a call on the side-by-side layout, or with `ok` False on the skewed one
+    (a row stride that is no multiple of 16 B)."""
+    case = SimpleNamespace(H=H, D=D, cap=cap, dtype=dtype, lay="side" if ok else "skew")
+    lay = make_layout(case, 3)
+    ld = H * D + 8
+    shared = entry in ("shared", "shared_qln")
+    return (entry, dtype, D, lay.row_stride, lay.req_stride, 0, ld, ld, cap, n_rows, H, dmodel, n_groups if shared else 0)
+
+
+def decode_queries():
+    """[(key, query)] over the grid, key = (entry, dtype, D, cap, blocks,
+    dmodel, layout ok); the skewed layout for smer_attn_decode alone (the
+    other entries refuse it)."""
+    out = []
+    for entry in ENTRIES:
+        for dtype in (BF16, F32):
+            for D in GRID_D:
+                for dm in (0,) + GRID_DMODEL:
+                    if not entry_accepts(entry, dtype, D, dm):
+                        continue
+                    for cap in GRID_CAP:
+                        for n_rows, H in GRID_BLOCKS:
+                            for ok in (True, False) if entry == "decode" else (True,):
+                                out.append(((entry, dtype, D, cap, n_rows * H, dm, ok),
+                                            query(entry, dtype, D, cap, n_rows, H, dm, ok)))
+    return out
+
+
+def case_query(case, n_rows=None, pad=8):
+    """The query of a launch of the case (rows_of's row count by default)."""
+    nk, req, tab, live, n_slots = rows_of(case)
+    lay = make_layout(case, n_slots)
+    ld = case.H * case.D + pad
+    return (case.entry, case.dtype, case.D, lay.row_stride, lay.req_stride, lay.head_stride if lay.kind == "head" else 0,
+            ld, ld, case.cap, len(nk) if n_rows is None else n_rows, case.H, case.dmodel, 0 if tab is None else len(tab))
+
+
+SWITCH_SETS = [{}] + [{name: "0"} for name in ENV_SWITCHES]   # the defaults, then each switch off
+
+
+def plan_mismatches(lib, setenv, skln_process=False):
+    """Every point where the library's plan and this module's mirror differ:
+    the cases and decode_queries() and, for smer_linear_decode_ln, every
+    K % 8 == 0 up to 2048, under each of SWITCH_SETS (applied to the
+    environment through `setenv(env)`; the read-once SMER_SKINNY_KF is passed
+    to the query explicitly, and with skln_process also asked as the process
+    read it, which must be the default)."""
+    bad = []
+    queries = [(c.id, case_query(c)) for c in CASES] + decode_queries()
+    for env in SWITCH_SETS:
+        setenv(env)
+        sw = {name: name not in env for name in ENV_SWITCHES}
+        for key, q in queries:
+            m, l = variant_of(*q, switches=sw), library_variant(lib, *q)
+            if m != l:
+                bad.append((env, key, m, l))
+        kf = sw["SMER_SKINNY_KF"]
+        for K in range(8, 2049, 8):
+            got = {library_skln_label(lib, K, kf)} | ({library_skln_label(lib, K, None)} if skln_process and kf else set())
+            if got != {skln_label(K, kf)}:
+                bad.append((env, "skln K=%d" % K, skln_label(K, kf), got))
+    setenv({})
+    return bad
 
 
 def kpb_unr(case):
@@ -472,7 +574,6 @@ def _tree(s):
     return s[..., 0]
 
 
-ENV_SWITCHES = ("SMER_DEC_PIPE_SMALL", "SMER_DECODE_ODD_FIRST", "SMER_SKINNY_KF")
 MUTATIONS = ("le_nk", "lt_nkm1", "drop_wave", "rescale_per_key", "odd_first_q")
 
 

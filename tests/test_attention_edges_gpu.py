@@ -77,6 +77,24 @@ class Call:
         self.kw = dict(B=B, H=H, Lq=Lq, Lk=Lk, D=D, kpm=self.kpm, causal=causal, scale=A.scale_of(D))
         self.what = "%s %s %s" % (A.shape_id(shape), str(dtype)[6:], "/".join(kinds))
 
+    def check_plan(self, which, what, kw):
+        """The library's plan for the call about to be launched (nothing is
+        launched by asking) equals attnref's mirror, under the environment's
+        SMER_ATTN_F32_MFMA."""
+        import os
+        from smer_music_generation_amd import _lib as L
+        B, H, Lq, Lk, D, causal = self.shape
+        drop, mask = bool(kw.get("drop_p")), kw.get("drop_mask") is not None
+        if which == "bwd":
+            a = (self.dtype, B, H, Lq, Lk, D, drop, mask, causal)
+            m, l = A.expected_bwd_plan(*a), A.library_bwd_plan(L.load(), *a)
+        else:
+            al = all(t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 for t in (self.q, self.k))
+            a = (self.dtype, B, H, Lq, Lk, D, drop, mask, bool(kw.get("drop_mask_in")), False, al)
+            m = A.expected_fwd_plan(*a, f32_mfma=os.environ.get("SMER_ATTN_F32_MFMA", "1")[:1] != "0")
+            l = A.library_fwd_plan(L.load(), *a)
+        assert m == l, (what, which, m, l)
+
     def fwd(self, what, **kw):
         """O [B*Lq, H*D] and lse [B, H, Lq] of a forward, written into
         sentinel-framed buffers that are checked afterwards."""
@@ -84,6 +102,7 @@ class Call:
         obuf = torch.full((B * Lq + 2, self.HD + 16), SENT, dtype=self.dtype, device=dev)
         lbuf = torch.full((B * H * Lq + 16,), SENT, dtype=F32, device=dev)
         o, lse = obuf[:B * Lq, :self.HD], lbuf[:B * H * Lq].view(B, H, Lq)
+        self.check_plan("fwd", what, kw)
         ops().attn_fwd(self.q, self.k, self.v, o, lse, **self.kw, **kw)
         torch.cuda.synchronize()
         pads_intact(obuf[:B * Lq], self.HD, SENT, what + " O")
@@ -96,6 +115,7 @@ class Call:
         HD = self.HD
         g = torch.full((B * max(Lq, Lk) + 3, 3 * HD + 8), SENT, dtype=self.dtype, device=dev)
         dq, dk, dv = g[:B * Lq, :HD], g[:B * Lk, HD:2 * HD], g[:B * Lk, 2 * HD:3 * HD]
+        self.check_plan("bwd", what, kw)
         ops().attn_bwd(self.q, self.k, self.v, o, self.do, lse, dq, dk, dv, **self.kw, **kw)
         torch.cuda.synchronize()
         pads_intact(g, 3 * HD, SENT, what + " gradients")

@@ -119,3 +119,77 @@ def test_mask_sets_carry_every_kind():
         assert {kd for s in sets for kd in s} == set(A.mask_kinds(Lk))
     assert set(A.mask_kinds(200)) == set(A.MASK_KINDS)
     assert A.make_kpm(["first64"], 130)[0, :64].all() and not A.make_kpm(["first64"], 130)[0, 64:].any()
+
+
+# ---------------------------------------------------------------- dispatch
+TWO_GROUP = [s for s in A.SHAPES if s[0] * s[1] >= 256 and s[4] <= 64]
+
+
+def test_shape_table_reaches_the_two_group_kernels():
+    """What the shape table is there for: its B*H >= 256 shapes with D <= 64
+    (drop_rates' two_group class) run the QG = 2 forward and dQ kernels and
+    the KG = 2 dK/dV kernel, (64, 8, 70, 70, 128) does not; the rule flips
+    between 511 and 512 blocks and between D = 64 and 128."""
+    assert TWO_GROUP and all(A.drop_rates(*s) for s in TWO_GROUP)
+    for s in TWO_GROUP:
+        B, H, Lq, Lk, D, causal = s
+        assert A.expected_fwd_plan(A.BF16, B, H, Lq, Lk, D).QG == 2, s
+        b = A.expected_bwd_plan(A.BF16, B, H, Lq, Lk, D, causal=causal)
+        assert b.dq.G == 2 and b.dkdv.G == 2 and b.dq.CAUSAL == b.dkdv.CAUSAL == causal, s
+    assert (64, 8, 70, 70, 128, False) in A.SHAPES
+    assert A.expected_fwd_plan(A.BF16, 64, 8, 70, 70, 128).QG == 1
+    b = A.expected_bwd_plan(A.BF16, 64, 8, 70, 70, 128)
+    assert b.dq.G == 1 and b.dkdv.G == 1
+    # 511 | 512 blocks: by B*H, and by a second 128-row block
+    for H, L, QG in ((511, 70, 1), (512, 70, 2), (256, 128, 1), (256, 129, 2)):
+        f = A.expected_fwd_plan(A.BF16, 1, H, L, L, 64)
+        assert f.QG == QG and f.grid == (-(-L // (64 * QG)), H)
+        b = A.expected_bwd_plan(A.BF16, 1, H, L, 3, 64)
+        # (the key side has one 128-row block: two groups from B*H = 512 on)
+        assert b.dq.G == QG and b.dkdv.G == (2 if H == 512 else 1) and b.dq.grid == f.grid and b.dkdv.grid == (1, H)
+    assert A.expected_fwd_plan(A.BF16, 1, 512, 70, 70, 64).QG == 2 and A.expected_fwd_plan(A.BF16, 1, 512, 70, 70, 128).QG == 1
+
+
+def test_mask_and_family_rules():
+    """MIN (the forward reads the keep words) exactly when a mask buffer is
+    passed and (it is filled or the wave holds one group), the generator first
+    exactly when it is not filled; the fp32 MFMA forward needs D = 64, no
+    dropout, the alignment fact and the switch."""
+    for B, QG in ((2, 1), (64, 2)):
+        for drop in (False, True):
+            for mask, mask_in in ((False, False), (True, False), (True, True)):
+                f = A.expected_fwd_plan(A.BF16, B, 8, 70, 70, 64, drop=drop, mask=mask and drop, mask_in=mask_in and drop)
+                assert f.QG == QG and f.DROP == drop
+                assert f.MIN == (drop and mask and (mask_in or QG == 1))
+                assert f.mask_gen == (f.MIN and not mask_in)
+                b = A.expected_bwd_plan(A.BF16, B, 8, 70, 70, 64, drop=drop, mask=mask)
+                assert b.dq.MSK == b.dkdv.MSK == (drop and mask) and b.dq_first and not b.delta_pass
+    ok = dict(drop=False, aligned=True, f32_mfma=True)
+    assert A.expected_fwd_plan(A.F32, 2, 3, 70, 130, 64, **ok).family == "f32_mfma"
+    for D, change in ((32, {}), (64, dict(drop=True)), (64, dict(aligned=False)), (64, dict(f32_mfma=False))):
+        f = A.expected_fwd_plan(A.F32, 2, 3, 70, 130, D, **dict(ok, **change))
+        assert f.family == "f32_valu" and f.lds == 16 * 130 and f.grid == (18, 6)
+
+
+def test_plan_matches_mirror(monkeypatch):
+    """The library's dispatch (smer_attn_fwd_plan / smer_attn_bwd_plan: no HIP
+    call, nothing launched) and the mirror agree over attnref.plan_mismatches'
+    table.  Skips only where libsmer_hip.so is not built or cannot be loaded
+    without a GPU; tests/test_attention_edges_gpu.py compares every call it
+    launches on the device."""
+    import os
+    from smer_music_generation_amd import _lib as L
+    if not os.path.exists(L.LIB_PATH):
+        pytest.skip("libsmer_hip.so is not built")
+    try:
+        lib = L.load()
+    except OSError as e:
+        if torch.cuda.is_available():
+            raise
+        pytest.skip("libsmer_hip.so does not load without a GPU: %s" % e)
+
+    def setenv(v):
+        monkeypatch.delenv("SMER_ATTN_F32_MFMA", raising=False) if v is None else monkeypatch.setenv("SMER_ATTN_F32_MFMA", v)
+
+    bad = A.plan_mismatches(lib, setenv)
+    assert not bad, bad[:10]

@@ -206,6 +206,7 @@ def test_decode_attention_edges(case, kind):
     decoderef; x_out within the float64 LayerNorm bound; rows of no group
     (shared entries) keep their NaN prefill."""
     d = launch_data(case, kind)
+    assert launch_variant(case, len(d.nk), 0 if d.tab is None else len(d.tab)).label == case.label
     out, xo, (kc, vc, lay) = run(case, None if case.dmodel else d.q, d.K, d.V, d.nk, d.req, d.tab, d.n_slots, d.scale, d.qln)
     n = len(d.nk)
     qref = d.q.float()
@@ -230,11 +231,27 @@ def test_decode_attention_edges(case, kind):
         within(xo[lv], xr[lv], xb[lv], case.id + " x_out")
 
 
-def launch_label(case, n_rows):
-    lay = R.make_layout(case, 3)
-    ld = case.H * case.D + PAD
-    return R.variant_of(case.entry, case.dtype, case.D, lay.row_stride, lay.req_stride,
-                        lay.head_stride if lay.kind == "head" else 0, ld, ld, case.cap, n_rows, case.H, case.dmodel)
+def launch_variant(case, n_rows, n_groups=0):
+    """The mirror's variant of a launch of `n_rows` rows of the case, asserted
+    equal to the library's own plan for it (nothing is launched)."""
+    q = R.case_query(case, n_rows, PAD)[:12] + (n_groups,)
+    from smer_music_generation_amd import _lib as L
+    m, l = R.variant_of(*q), R.library_variant(L.load(), *q)
+    assert m == l, (case.id, n_rows, m, l)
+    return m
+
+
+def test_plan_matches_mirror(monkeypatch):
+    """decoderef.plan_mismatches on the device's library: every case and the
+    whole query grid, at the defaults and with each switch off."""
+    from smer_music_generation_amd import _lib as L
+
+    def setenv(env):
+        for k in R.ENV_SWITCHES:
+            monkeypatch.setenv(k, env[k]) if k in env else monkeypatch.delenv(k, raising=False)
+
+    bad = R.plan_mismatches(L.load(), setenv, skln_process=True)
+    assert not bad, bad[:10]
 
 
 @pytest.mark.parametrize("case", R.CASES, ids=lambda c: c.id)
@@ -250,9 +267,9 @@ def test_decode_attention_needle(case):
             pp = pos[b:b + R.needle_rows(case)]
             d = R.needle_launch(case, nk, pp)
             n = len(d.req)
-            assert launch_label(case, n) == case.label, (case.id, n)
             nkv = np.full(n, nk, np.int32)
             tab = d.tab if case.entry in ("shared", "shared_qln") else None
+            assert launch_variant(case, n, 0 if tab is None else len(tab)).label == case.label, (case.id, n)
             out, _, _ = run(case, d.q, d.K, d.V, nkv, d.req, tab, 3, d.scale, d.qln)
             if case.entry.startswith("split"):
                 out = R.split_merge_ref64(out).view(n, -1).float()
@@ -383,6 +400,8 @@ def test_linear_decode_ln_edges(K):
     K-full forms, 264 and 520 the guarded ones) over M in {1, 15, 16, 17, 64,
     256} and N in {16, 24, 309, 1536}: x_out against the float64 LayerNorm,
     the product against float64 at the stored x_out, epilogues in turn."""
+    from smer_music_generation_amd import _lib as L
+    assert R.library_skln_label(L.load(), K, None) == R.skln_label(K)
     epis = ["plain", "relu", "residual", "kv0", "kvlast"]
     i = 0
     for M in (1, 15, 16, 17, 64, 256):

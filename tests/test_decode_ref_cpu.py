@@ -14,7 +14,6 @@ import torch
 from tests import decoderef as R
 
 BF16, F32 = R.BF16, R.F32
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "smer_music_generation_amd", "csrc")
 
 # one case per distinct arithmetic (label, head dim, capacity): the shared
 # kernels and the query-prologue forms run attn_decode_vec_kernel's arithmetic
@@ -83,21 +82,65 @@ def test_reference_is_softmax(lay):
 
 
 def test_variant_coverage():
-    """Every instantiation the dispatch macros of attention.hip name (and
-    smer_linear_decode_ln's in gemm.hip) is the label of a case, and
-    variant_of gives every case its label."""
-    want = R.dispatch_labels(CSRC)
-    have = {c.label for c in R.CASES} | {R.skln_label(k) for k in R.SKLN_K}
-    assert want - have == set(), want - have
-    assert have - want == set(), have - want
+    """The mirror alone (no library): over decoderef.decode_queries() the
+    reachable instantiations are exactly the case labels (and skln_label's
+    over K exactly those of SKLN_K); variant_of gives every case its label and
+    every case holds its kernel's edge key counts; each threshold of the
+    dispatch flips the label exactly between its two neighbouring grid values."""
+    qs = R.decode_queries()
+    assert {R.variant_of(*q).label for _, q in qs} == {c.label for c in R.CASES}
+    assert ({R.skln_label(K, kf) for K in range(8, 2049, 8) for kf in (True, False)}
+            == {R.skln_label(K) for K in R.SKLN_K})
+    assert {R.skln_label(K, False) for K in range(8, 2049, 8)} == {"skln U2 NC4", "skln U4 NC4"}
     for c in R.CASES:
-        nk, req, tab, live, n_slots = R.rows_of(c)
-        L = R.make_layout(c, n_slots)
-        ld = c.H * c.D + 8
-        assert R.variant_of(c.entry, c.dtype, c.D, L.row_stride, L.req_stride,
-                            L.head_stride if L.kind == "head" else 0, ld, ld, c.cap, len(nk), c.H, c.dmodel) == c.label
+        nk = R.rows_of(c)[0]
+        assert R.variant_of(*R.case_query(c)).label == c.label, c.id
         # every launch holds every edge key count of its kernel
         assert set(R.edge_nkeys(c)) <= set(int(x) for x in nk), c.id
+    # thresholds: along each axis of the grid, the label changes between these
+    # neighbours and between no others
+    lab = {key: R.variant_of(*q).label for key, q in qs}
+    few_off = {key: R.variant_of(*q, switches=dict(R.SWITCH_DEFAULTS, SMER_DEC_PIPE_SMALL=False)).label for key, q in qs}
+    for (entry, dtype, D, cap, blocks, dm, ok), l in lab.items():
+        vec = ok and (D // (8 if dtype == BF16 else 4) in (4, 8, 16)) and D % (8 if dtype == BF16 else 4) == 0
+        split, qln = entry.startswith("split"), entry.endswith("qln")
+        i = R.GRID_CAP.index(cap)
+        if i:   # capacity: 511 | 512 (not the prologue entries), 2047 | 2048
+            flips = vec and not split and ((cap == 512 and not qln) or (cap == 2048 and (blocks > 128 or qln)))
+            assert (l != lab[(entry, dtype, D, R.GRID_CAP[i - 1], blocks, dm, ok)]) == flips, (entry, D, cap, blocks)
+        if blocks == 129:   # blocks: 128 | 129 for big caches below the pipelined capacity
+            flips = vec and not split and not qln and 512 <= cap < 2048
+            assert (l != lab[(entry, dtype, D, cap, 128, dm, ok)]) == flips, (entry, D, cap)
+            assert few_off[(entry, dtype, D, cap, 128, dm, ok)] == l   # the switch takes the few-blocks term out
+        if entry == "decode":   # the vector layout and the lanes per key
+            assert l.startswith("vec" if vec else "generic"), (dtype, D, ok)
+        if dm:
+            assert ("q%d" % dm) in l
+
+
+def test_plan_matches_mirror(monkeypatch):
+    """The library's dispatch (smer_attn_decode_plan, smer_linear_decode_ln_plan:
+    no HIP call, nothing launched) and the mirror agree on label, grid, block,
+    LDS bytes and the odd-rows-first flag at every case and grid point, at the
+    defaults and with each of the three switches off.  Skips only where
+    libsmer_hip.so is not built or cannot be loaded without a GPU;
+    tests/test_decode_edges_gpu.py runs the same comparison on the device."""
+    from smer_music_generation_amd import _lib as L
+    if not os.path.exists(L.LIB_PATH):
+        pytest.skip("libsmer_hip.so is not built")
+    try:
+        lib = L.load()
+    except OSError as e:
+        if torch.cuda.is_available():
+            raise
+        pytest.skip("libsmer_hip.so does not load without a GPU: %s" % e)
+
+    def setenv(env):
+        for k in R.ENV_SWITCHES:
+            monkeypatch.setenv(k, env[k]) if k in env else monkeypatch.delenv(k, raising=False)
+
+    bad = R.plan_mismatches(lib, setenv)
+    assert not bad, bad[:10]
 
 
 @functools.lru_cache(maxsize=None)
@@ -226,7 +269,7 @@ def _old_test_passes(mutate, cap, dtype):
     K, V = torch.randn(3, cap, H, D, generator=g), torch.randn(3, cap, H, D, generator=g)
     q = torch.randn(5, H * D, generator=g).to(dtype)
     case = R._mk("old", "decode", dtype, D, "side", cap, 5, H, R.variant_of(
-        "decode", dtype, D, H * D, cap * H * D, 0, H * D, H * D, cap, 5, H))
+        "decode", dtype, D, H * D, cap * H * D, 0, H * D, H * D, cap, 5, H).label)
     lay = R.make_layout(case, 3)
     kc, vc = R.pack_cache(K, V, lay, dtype)
     req, nk = np.array([0, 1, 1, 2, 2]), np.array([1, 17, 18, cap, 64])

@@ -1,7 +1,7 @@
 """the warm batch-1 (plugin) session rounds its cache
 capacities up to powers of two, but never across the 512-row boundary where
-smer_attn_decode switches to its 8-wave variant (csrc/attention.hip
-`big = cap_rows >= 512`), so a warm and a cold session of the same request
+smer_attn_decode switches to its 8-wave variant (csrc/attn_plan.h
+ap::DEC_BIG_ROWS), so a warm and a cold session of the same request
 run the same decode-attention kernels and give the same logits."""
 import pytest
 
