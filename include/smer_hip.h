@@ -617,6 +617,26 @@ int smer_layernorm_bwd_partials(int dtype, int M, int N, const void* dy, long ld
                                 size_t ws_bytes, smer_stream_t stream);
 int smer_layernorm_param_reduce(int M, int N, void* workspace, size_t ws_bytes, float* dgamma,
                                 float* dbeta, int accumulate, smer_stream_t stream);
+/* Rows of the [nblk][2N] fp32 partials that a LayerNorm backward over
+ * [M, N] writes.  With _partials (and _fp8 with partials_only) a workspace
+ * of nblk * 2N * 4 bytes is enough: the tail behind the partials is only
+ * the per-call reduction's scratch. */
+int smer_layernorm_bwd_nblk(int M, int N);
+/* Every deferred dgamma / dbeta reduction of a step in one launch.  One
+ * site = the partials of one LayerNorm backward and where its sums go
+ * (dgamma or dbeta may be null; accumulate=1: +=).  Each sum is taken in
+ * exactly the order of smer_layernorm_param_reduce, so the results are bit
+ * for bit those of the per-call reductions.  `sites` is read by the host
+ * (validation, grid size) and `sites_dev` is the same table in device
+ * memory, read by the kernel; nblk <= 4096 per site. */
+typedef struct smer_ln_reduce_site {
+  const float* part; /* [nblk][2N] */
+  float* dgamma;
+  float* dbeta;
+  int nblk, N, accumulate, reserved;
+} smer_ln_reduce_site;
+int smer_layernorm_param_reduce_batch(int nsites, const smer_ln_reduce_site* sites,
+                                      const smer_ln_reduce_site* sites_dev, smer_stream_t stream);
 
 /* out[t] = dropout(table[ids[t]] * scale + pe[pos(t)]), pos(t) = positions
  * ? positions[t] : t % L.  table/pe fp32; out activation dtype. */

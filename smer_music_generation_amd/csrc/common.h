@@ -150,6 +150,12 @@ size_t smer_col_reduce_scratch(int nblk, int N);
 void smer_col_reduce_launch(int nblk, int N, const float* part, long stride, long off, float* out,
                             int accumulate, float scale, float* scratch, hipStream_t s,
                             float* out2 = nullptr, int nsplit = 0);
+// The LayerNorm dgamma / dbeta reductions of `nsites` sites in one launch
+// (grid x sized by max_cols = the largest reduced width of the table), each
+// sum in smer_col_reduce_launch's order.  Defined in train_ops.hip.
+constexpr int SMER_LN_REDUCE_MAX_NBLK = 64 * 64;
+void smer_ln_param_reduce_batch_launch(int nsites, int max_cols, const smer_ln_reduce_site* sites_dev,
+                                       hipStream_t s);
 
 // Load 8 consecutive elements as floats (16-B vector when aligned & in range).
 template <typename T, bool VEC = true>

@@ -859,6 +859,12 @@ extern "C" size_t smer_layernorm_bwd_workspace(int M, int N) {
   return nblk * 2 * N * sizeof(float) + smer_col_reduce_scratch((int)nblk, 2 * N);
 }
 
+extern "C" int smer_layernorm_bwd_nblk(int M, int N) {
+  if (M <= 0 || N <= 0) return 0;
+  const int rpb = ln_bwd_rows(M, N);
+  return (M + rpb - 1) / rpb;
+}
+
 // reduce: 0 = write the per-block dgamma / dbeta partials only (reduced
 // later by smer_layernorm_param_reduce, e.g. on another stream)
 static int ln_bwd_impl(int dtype, int M, int N, const void* dy, long lddy, int dy_f32,
@@ -870,7 +876,10 @@ static int ln_bwd_impl(int dtype, int M, int N, const void* dy, long lddy, int d
                        unsigned* amax = nullptr) {
   SMER_REQUIRE(N % 8 == 0 && N <= 64 * 8 * LN_MAXC, "smer_layernorm_bwd: N % 8 == 0 and N <= 2048");
   SMER_REQUIRE(dx && dy && x && mean && rstd && gamma, "smer_layernorm_bwd: null pointer");
-  SMER_REQUIRE(!params || (workspace && ws_bytes >= smer_layernorm_bwd_workspace(M, N)),
+  // partials only: just the [nblk][2N] rows (the tail is the per-call reduction's scratch)
+  SMER_REQUIRE(!params || (workspace && ws_bytes >= (reduce ? smer_layernorm_bwd_workspace(M, N)
+                                                            : (size_t)smer_layernorm_bwd_nblk(M, N) * 2 * N *
+                                                                  sizeof(float))),
                "smer_layernorm_bwd: workspace too small");
   if (M == 0) return SMER_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -1015,6 +1024,26 @@ extern "C" int smer_layernorm_param_reduce(int M, int N, void* workspace, size_t
     smer_col_reduce_launch(nblk, N, part, (long)2 * N, (long)N, dbeta, accumulate, 1.f,
                            part + (size_t)nblk * 2 * N, s);
   SMER_CHECK_LAUNCH("smer_layernorm_param_reduce");
+  return SMER_OK;
+}
+
+extern "C" int smer_layernorm_param_reduce_batch(int nsites, const smer_ln_reduce_site* sites,
+                                                 const smer_ln_reduce_site* sites_dev,
+                                                 smer_stream_t stream) {
+  if (nsites == 0) return SMER_OK;
+  SMER_REQUIRE(nsites > 0 && nsites <= 65535 && sites && sites_dev,
+               "smer_layernorm_param_reduce_batch: 1..65535 sites, host and device table");
+  int max_cols = 0;
+  for (int i = 0; i < nsites; ++i) {
+    const smer_ln_reduce_site& t = sites[i];
+    SMER_REQUIRE(t.part && (t.dgamma || t.dbeta), "smer_layernorm_param_reduce_batch: null pointer in a site");
+    SMER_REQUIRE(t.nblk >= 1 && t.nblk <= SMER_LN_REDUCE_MAX_NBLK && t.N >= 1 && t.N <= 64 * 8 * LN_MAXC,
+                 "smer_layernorm_param_reduce_batch: 1 <= nblk <= 4096 and 1 <= N <= 2048 per site");
+    const int cols = (t.dgamma && t.dbeta) ? 2 * t.N : t.N;
+    if (cols > max_cols) max_cols = cols;
+  }
+  smer_ln_param_reduce_batch_launch(nsites, max_cols, sites_dev, (hipStream_t)stream);
+  SMER_CHECK_LAUNCH("smer_layernorm_param_reduce_batch");
   return SMER_OK;
 }
 

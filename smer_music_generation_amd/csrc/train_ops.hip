@@ -194,6 +194,108 @@ void smer_col_reduce_launch(int nblk, int N, const float* part, long stride, lon
   }
 }
 
+// Rows [b0, b1) of one column as row group g of smer_col_reduce sums them:
+// four round-robin accumulators over rows g, g + 4, ..., then the pair sums.
+__device__ __forceinline__ float col_reduce_group(const float* p, long stride, int b0, int b1, int g) {
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  int b = b0 + g;
+  for (; b + 12 < b1; b += 16) {
+    a0 += p[(long)b * stride];
+    a1 += p[(long)(b + 4) * stride];
+    a2 += p[(long)(b + 8) * stride];
+    a3 += p[(long)(b + 12) * stride];
+  }
+  for (; b < b1; b += 4) a0 += p[(long)b * stride];
+  return (a0 + a1) + (a2 + a3);
+}
+
+// All of a step's LayerNorm dgamma / dbeta reductions in one launch:
+// workgroup (x = 64-column tile, y = site) does for its columns what
+// smer_col_reduce_launch does in one or two launches, operation for
+// operation (same accumulators, same pair sums, the 64-row chunk sums kept
+// in LDS where the two launches pass them through scratch), so the sums are
+// bit for bit the per-call ones.  A full chunk's 16 rows per thread are
+// loaded ahead, one chunk in front of the adds: the reduction is a stream
+// of 256-B row segments and would otherwise wait a round trip per row.
+__global__ void __launch_bounds__(256) smer_ln_param_reduce_batch(const smer_ln_reduce_site* __restrict__ sites) {
+  __shared__ float red[2][4][64];
+  __shared__ float csum[SMER_LN_REDUCE_MAX_NBLK / 64][64];
+  const smer_ln_reduce_site st = sites[blockIdx.y];
+  const int cl = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int nblk = st.nblk, N = st.N;
+  const bool both = st.dgamma && st.dbeta;
+  const int ncol = both ? 2 * N : N;  // reduced width: dgamma | dbeta, or one of them
+  if ((int)blockIdx.x * 64 >= ncol || (!st.dgamma && !st.dbeta) || nblk <= 0 ||
+      nblk > SMER_LN_REDUCE_MAX_NBLK)
+    return;  // uniform over the workgroup
+  const long stride = 2L * N;
+  const int col = blockIdx.x * 64 + cl;
+  const bool live = col < ncol;
+  const float* p = st.part + (st.dgamma ? 0 : N) + (live ? col : 0);
+  float* out = st.dgamma ? st.dgamma : st.dbeta;
+  const int nsplit = both ? N : ncol;
+  float total;
+  if (nblk <= 64) {
+    red[0][g][cl] = live ? col_reduce_group(p, stride, 0, nblk, g) : 0.f;
+    __syncthreads();
+    total = (red[0][0][cl] + red[0][1][cl]) + (red[0][2][cl] + red[0][3][cl]);
+  } else {
+    const int nch = (nblk + 63) / 64, nfull = nblk / 64;
+    float v[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = live ? p[(long)(g + 4 * i) * stride] : 0.f;
+    for (int c = 0; c < nfull; ++c) {
+      float w[16];
+      if (c + 1 < nfull) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) w[i] = live ? p[(long)((c + 1) * 64 + g + 4 * i) * stride] : 0.f;
+      }
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        a0 += v[4 * k];
+        a1 += v[4 * k + 1];
+        a2 += v[4 * k + 2];
+        a3 += v[4 * k + 3];
+      }
+      // red is double-buffered: chunk c + 1 writes the other half while row
+      // group 0 may still read this one; chunk c + 2 comes after c + 1's barrier
+      red[c & 1][g][cl] = (a0 + a1) + (a2 + a3);
+      __syncthreads();
+      if (g == 0)
+        csum[c][cl] = (red[c & 1][0][cl] + red[c & 1][1][cl]) + (red[c & 1][2][cl] + red[c & 1][3][cl]);
+      if (c + 1 < nfull) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = w[i];
+      }
+    }
+    if (nch > nfull) {  // ragged last chunk
+      const int c = nfull;
+      red[c & 1][g][cl] = live ? col_reduce_group(p, stride, c * 64, nblk, g) : 0.f;
+      __syncthreads();
+      if (g == 0)
+        csum[c][cl] = (red[c & 1][0][cl] + red[c & 1][1][cl]) + (red[c & 1][2][cl] + red[c & 1][3][cl]);
+    }
+    __syncthreads();
+    // the second launch's pattern over the nch chunk sums
+    const float r = col_reduce_group(&csum[0][cl], 64, 0, nch, g);
+    red[0][g][cl] = r;
+    __syncthreads();
+    total = (red[0][0][cl] + red[0][1][cl]) + (red[0][2][cl] + red[0][3][cl]);
+  }
+  if (g == 0 && live) {
+    float* o = col < nsplit ? out + col : st.dbeta + (col - nsplit);
+    *o = st.accumulate ? *o + total : total;
+  }
+}
+
+void smer_ln_param_reduce_batch_launch(int nsites, int max_cols, const smer_ln_reduce_site* sites_dev,
+                                       hipStream_t s) {
+  if (nsites <= 0 || max_cols <= 0) return;
+  hipLaunchKernelGGL(smer_ln_param_reduce_batch, dim3((max_cols + 63) / 64, nsites), dim3(256), 0, s,
+                     sites_dev);
+}
+
 // ---------------------------------------------------------------------------
 extern "C" int smer_wce_denom(int n, const int64_t* y, const float* ce_all, float* denom,
                               smer_stream_t stream) {

@@ -77,6 +77,18 @@ _WGRAD_FP8_CAP = int(os.environ.get("SMER_WGRAD_FP8_CAP", "192"))
 # attention-dropout keep words generated up front on a second stream
 # (SMER_ATTN_MASK_PREGEN=1)
 _ATTN_MASK_PREGEN = os.environ.get("SMER_ATTN_MASK_PREGEN", "0") == "1"
+# LayerNorm dgamma / dbeta: every LayerNorm backward only writes its partials
+# into a slot of the engine's arena, and one launch per hook range (one per
+# step without a hook) reduces them (SMER_LN_PARAM_BATCH=0: one or two
+# reduction launches per LayerNorm; the same bits)
+_LN_PARAM_BATCH = os.environ.get("SMER_LN_PARAM_BATCH", "1") != "0"
+
+
+class _LnParamPlan:
+    """The partials arena of one device and the site tables over it: slots
+    {site: uint8 view}, groups {hook range: ops.LnReduceTable} in backward
+    order, all = one table of every site."""
+    pass
 
 
 class Engine:
@@ -98,6 +110,7 @@ class Engine:
         self._side = {}         # device -> (wgrad stream, its split-K workspace)
         self._mstream = {}      # device -> attention-mask generator stream
         self._fp8 = None        # fp8.Fp8Forward (precision "fp8")
+        self._ln_plan = {}      # device -> _LnParamPlan (batched dgamma / dbeta reductions)
 
     # ------------------------------------------------------------------
     def act_dtype(self):
@@ -562,6 +575,44 @@ class Engine:
             q8[0].record_stream(stream)
             q8[2].record_stream(stream)
 
+    def _ln_param_plan(self, dev, Mt, Ms, G):
+        """Arena and site tables of the batched LayerNorm parameter
+        reductions, built once per (shape, gradient buffer): the arena is the
+        engine's own, so the tables' pointers hold from step to step."""
+        key = (Mt, Ms, self.m.flat_grad().data_ptr())
+        plan = self._ln_plan.get(dev)
+        if plan is not None and plan.key == key:
+            return plan
+        d = self.d
+        sites = [("head", "dec_norm", Mt, G.dec_norm)]
+        for i in reversed(range(self.n_dec)):
+            sites += [("dec%d" % i, "dec%d.n%d" % (i, k), Mt, getattr(G.dec[i], "n%d" % k)) for k in (3, 2, 1)]
+        # the encoder's final norm: the last encoder layer's range (train.layer_ranges)
+        sites.append(("enc%d" % (self.n_enc - 1) if self.n_enc else "tail", "enc_norm", Ms, G.enc_norm))
+        for i in reversed(range(self.n_enc)):
+            sites += [("enc%d" % i, "enc%d.n%d" % (i, k), Ms, getattr(G.enc[i], "n%d" % k)) for k in (2, 1)]
+        # a site with more partial rows than one workgroup's chunk sums hold keeps its own reduction
+        sites = [s for s in sites if 0 < ops.ln_bwd_partial_bytes(s[2], d) <= ops.LN_REDUCE_MAX_NBLK * 2 * d * 4]
+        sizes = [(ops.ln_bwd_partial_bytes(M, d) + 255) // 256 * 256 for _, _, M, _ in sites]
+        plan = _LnParamPlan()
+        plan.key = key
+        # Dropping an older arena here is safe although the side stream read
+        # it without record_stream: the backward that used it ended with the
+        # main stream joining the side stream.
+        plan.arena = torch.empty(max(1, sum(sizes)), dtype=torch.uint8, device=dev)
+        plan.slots, rows, off = {}, [], 0
+        for (group, name, M, gw), n in zip(sites, sizes):
+            plan.slots[name] = plan.arena[off:off + n]
+            rows.append((group, (plan.slots[name], M, d, gw[0], gw[1], True)))
+            off += n
+        plan.groups = {}
+        for group, _ in rows:
+            if group not in plan.groups:
+                plan.groups[group] = ops.LnReduceTable([r for g_, r in rows if g_ == group], dev)
+        plan.all = ops.LnReduceTable([r for _, r in rows], dev)
+        self._ln_plan[dev] = plan
+        return plan
+
     @staticmethod
     def _join(side):
         if side is not None:
@@ -602,12 +653,49 @@ class Engine:
         from .fp8 import FP8_ATTN_DGRAD, FP8_DGRAD, eligible
         f8 = ctx.f8 if FP8_DGRAD else None
 
+        # Batched dgamma / dbeta reductions.  A slot is written by its
+        # LayerNorm backward on the main stream and read by the reduction on
+        # the weight-gradient stream, which first waits for the main stream
+        # (ln_flush).  The next step's LayerNorm backward cannot overwrite a
+        # slot before that reduction has read it: every backward ends with the
+        # main stream joining the side stream (_join), and the next step's
+        # kernels are queued on the main stream after that.
+        lnp = self._ln_param_plan(dev, Mt, Ms, G) if _LN_PARAM_BATCH else None
+        ln_slot = (lambda name: lnp.slots.get(name)) if lnp is not None else (lambda name: None)  # noqa: E731
+        ln_flushed = set()
+
+        def ln_flush(group=None):
+            """Reduce the partials of one hook range (group None: of every
+            range not reduced yet, in one launch when none was), on the
+            weight-gradient stream when there is one."""
+            if lnp is None:
+                return
+            if group is not None:
+                tabs = [lnp.groups[group]] if group in lnp.groups and group not in ln_flushed else []
+                ln_flushed.add(group)
+            elif not ln_flushed:
+                tabs = [lnp.all]
+            else:
+                tabs = [t for g_, t in lnp.groups.items() if g_ not in ln_flushed]
+            tabs = [t for t in tabs if t.n]
+            if not tabs:
+                return
+            if ps is None:
+                for t in tabs:
+                    ops.ln_param_reduce_batch(t)
+                return
+            ps.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(ps):
+                for t in tabs:
+                    ops.ln_param_reduce_batch(t)
+
         def ln_bwd(g_in, y_, mu, rs, wb, dx_, dxd_, seed_, gw, site):
             """LayerNorm backward; in fp8 mode also the e4m3 copy of the gradient
             feeding the next dgrad: returns (q8, site) once the site's scale has
             a step of history, else None."""
+            # site "b.dec3.ln2" -> slot "dec3.n2"
             kw = dict(dx_drop=dxd_ if p_tr > 0 else None, drop_p=p_tr, seed=seed_, dgamma=gw[0],
-                      dbeta=gw[1], param_stream=ps)
+                      dbeta=gw[1], param_stream=ps, param_slot=ln_slot(site[2:].replace(".ln", ".n")))
             if f8 is None:
                 ops.layernorm_bwd(g_in, y_, mu, rs, wb[0], dx_, **kw)
                 if ops.CK_LOG is not None:
@@ -730,9 +818,10 @@ class Engine:
         y_last, mo, ro = ctx.dec_last
         dy = torch.empty_like(y_last)
         ops.layernorm_bwd(g_out, y_last, mo, ro, W.dec_norm[0], dy, dgamma=G.dec_norm[0],
-                          dbeta=G.dec_norm[1], param_stream=ps)
+                          dbeta=G.dec_norm[1], param_stream=ps, param_slot=ln_slot("dec_norm"))
         ck("M:dy_final", dy)
         if hook:
+            ln_flush("head")
             self._hook(side, hook, "head")
         # every layer's dK|dV of the memory lands in one [Ms, L*2d] buffer:
         # one dgrad GEMM (K = L*2d) after the decoder loop gives dmemory
@@ -820,6 +909,7 @@ class Engine:
             dy, _ = dgrad(dqkvq, dqkv, "dec%d.sa" % i, L.sa_w, residual=dy1)
             ck("M:dec%d.dy" % i, dy)
             if hook:
+                ln_flush("dec%d" % i)
                 self._hook(side, hook, "dec%d" % i)
         d_tgt = dy
         if self.n_dec:
@@ -837,7 +927,7 @@ class Engine:
         x_last, me, re = ctx.enc_last
         dx = torch.empty_like(x_last)
         ops.layernorm_bwd(dmem, x_last, me, re, W.enc_norm[0], dx, dgamma=G.enc_norm[0],
-                          dbeta=G.enc_norm[1], param_stream=ps)
+                          dbeta=G.enc_norm[1], param_stream=ps, param_slot=ln_slot("enc_norm"))
         for i in reversed(range(self.n_enc)):
             L, GL = W.enc[i], G.enc[i]
             (x_in, qkv, o, lse, y1, m1, r1, x1, h, y2, m2, r2) = ctx.enc[i]
@@ -874,7 +964,9 @@ class Engine:
             dx, _ = dgrad(dqkvq, dqkv, "enc%d.in" % i, L.in_w, residual=dy1)
             ck("M:enc%d.dx" % i, dx)
             if hook:
+                ln_flush("enc%d" % i)
                 self._hook(side, hook, "enc%d" % i)
+        ln_flush()  # without a hook: every LayerNorm's dgamma / dbeta, one launch
         # shared embedding (model.py:76): both streams scatter into one table
         ops.embed_bwd(G.emb, math.sqrt(d), [(ctx.src_ids, dx, ctx.p_pos, sd(_SITE["pe_src"])),
                                             (ctx.tgt_ids, d_tgt, ctx.p_pos, sd(_SITE["pe_tgt"]))])

@@ -902,39 +902,50 @@ def layernorm(x, gamma, beta, y, mean, rstd, eps=1e-5):
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, dx, *, dx_drop=None, drop_p=0.0, seed=0,
                   dgamma=None, dbeta=None, accumulate=True, param_stream=None, q8=None, qs=None,
-                  amax=None):
+                  amax=None, param_slot=None):
     """param_stream: run the dgamma / dbeta column reduction on that stream
-    (after this stream's LayerNorm kernel), off the dgrad chain.  q8 (bf16
+    (after this stream's LayerNorm kernel), off the dgrad chain.  param_slot
+    (uint8, at least ln_bwd_partial_bytes(M, N)): only write the [nblk][2N]
+    partials there and launch no reduction; the caller reduces them later
+    (ln_param_reduce_batch), dgamma / dbeta / accumulate are not used.  q8 (bf16
     only): also the e4m3 copy e4m3(g * qs) of the gradient g that feeds the
     next dgrad (the dropped gradient when drop_p > 0, else dx), max|g| folded
     into amax; with q8, drop_p > 0 and no dx_drop that gradient exists only
     as its copy."""
     lib = load()
     M, N = x.shape
-    nbytes = lib.smer_layernorm_bwd_workspace(M, N) if (dgamma is not None or dbeta is not None) else 0
-    ws = torch.empty(max(1, nbytes), dtype=torch.uint8, device=x.device)
+    if param_slot is not None:
+        nbytes = ln_bwd_partial_bytes(M, N)
+        if param_slot.dtype != torch.uint8 or not param_slot.is_contiguous() or param_slot.numel() < nbytes:
+            raise RuntimeError("layernorm_bwd: param_slot must be contiguous uint8 of >= %d bytes" % nbytes)
+        ws, param_stream = param_slot, None
+    else:
+        nbytes = lib.smer_layernorm_bwd_workspace(M, N) if (dgamma is not None or dbeta is not None) else 0
+        ws = torch.empty(max(1, nbytes), dtype=torch.uint8, device=x.device)
     if q8 is not None:
         if x.dtype != torch.bfloat16 or dy.dtype != torch.bfloat16:
             raise RuntimeError("layernorm_bwd: the e4m3 copy needs bf16 dy and x")
-        partial = param_stream is not None and nbytes > 0
+        partial = (param_stream is not None or param_slot is not None) and nbytes > 0
         call("smer_layernorm_bwd_fp8", M, N, _p(dy), _ld(dy), _p(x), _ld(x), _p(mean), _p(rstd),
              _p(gamma), _p(dx), _ld(dx), _p(dx_drop), _ld(dx_drop) if dx_drop is not None else 0,
              float(drop_p), int(seed) & 0xFFFFFFFF, _p(q8), _ld(q8), _p(qs), _p(amax),
              _p(None if partial else dgamma), _p(None if partial else dbeta), int(accumulate),
              _p(ws), nbytes, int(partial), _stream())
-        if partial:
+        if partial and param_slot is None:
             param_stream.wait_stream(torch.cuda.current_stream(x.device))
             with torch.cuda.stream(param_stream):
                 call("smer_layernorm_param_reduce", M, N, _p(ws), nbytes, _p(dgamma), _p(dbeta),
                      int(accumulate), _stream())
             ws.record_stream(param_stream)
         return
-    if param_stream is not None and nbytes:
+    if (param_stream is not None or param_slot is not None) and nbytes:
         call("smer_layernorm_bwd_partials", dtype_code(x.dtype), M, N, _p(dy), _ld(dy),
              int(dy.dtype == torch.float32 and x.dtype != torch.float32), _p(x), _ld(x), _p(mean),
              _p(rstd), _p(gamma), _p(dx), _ld(dx), _p(dx_drop),
              _ld(dx_drop) if dx_drop is not None else 0, float(drop_p), int(seed) & 0xFFFFFFFF,
              _p(ws), nbytes, _stream())
+        if param_slot is not None:
+            return
         param_stream.wait_stream(torch.cuda.current_stream(x.device))
         with torch.cuda.stream(param_stream):
             call("smer_layernorm_param_reduce", M, N, _p(ws), nbytes, _p(dgamma), _p(dbeta),
@@ -946,6 +957,47 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dx, *, dx_drop=None, drop_p=0.0, see
          _p(rstd), _p(gamma), _p(dx), _ld(dx), _p(dx_drop),
          _ld(dx_drop) if dx_drop is not None else 0, float(drop_p), int(seed) & 0xFFFFFFFF,
          _p(dgamma), _p(dbeta), int(accumulate), _p(ws), nbytes, _stream())
+
+
+LN_REDUCE_MAX_NBLK = 4096   # partial rows per site of ln_param_reduce_batch (include/smer_hip.h)
+
+
+def ln_bwd_partial_bytes(M, N):
+    """Bytes of the [nblk][2N] fp32 partials of a LayerNorm backward over [M, N]."""
+    return load().smer_layernorm_bwd_nblk(M, N) * 2 * N * 4
+
+
+class LnReduceTable:
+    """Site table of ln_param_reduce_batch: one (partials slot, M, N, dgamma,
+    dbeta, accumulate) per LayerNorm backward, as the smer_ln_reduce_site
+    array of include/smer_hip.h, on the host and on the slots' device.  The
+    table holds raw pointers: whoever builds it keeps the tensors alive and
+    rebuilds it when one of them moves."""
+
+    def __init__(self, sites, device):
+        import numpy as np
+        dt = np.dtype([("part", "<u8"), ("dgamma", "<u8"), ("dbeta", "<u8"), ("nblk", "<i4"), ("N", "<i4"),
+                       ("accumulate", "<i4"), ("reserved", "<i4")])
+        lib = load()
+        host = np.zeros(len(sites), dtype=dt)
+        for i, (slot, M, N, dgamma, dbeta, accumulate) in enumerate(sites):
+            nblk = lib.smer_layernorm_bwd_nblk(M, N)
+            if slot.dtype != torch.uint8 or not slot.is_contiguous() or slot.numel() < nblk * 2 * N * 4:
+                raise RuntimeError("LnReduceTable: slot %d too small for [%d][%d] partials" % (i, nblk, 2 * N))
+            for t in (dgamma, dbeta):
+                if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != N):
+                    raise RuntimeError("LnReduceTable: dgamma / dbeta must be contiguous float32 [N]")
+            host[i] = (_p(slot), _p(dgamma) or 0, _p(dbeta) or 0, nblk, N, int(bool(accumulate)), 0)
+        self.host = host
+        self.dev = torch.from_numpy(host.view(np.uint8).copy()).to(device) if len(sites) else None
+        self.n = len(sites)
+
+
+def ln_param_reduce_batch(table):
+    """dgamma / dbeta of every site of `table` from its partials, one launch
+    on the current stream; bit for bit the per-call reductions."""
+    if table.n:
+        call("smer_layernorm_param_reduce_batch", table.n, table.host.ctypes.data, _p(table.dev), _stream())
 
 
 def embed(ids, table, pe, out, *, L=0, positions=None, scale, drop_p=0.0, seed=0):
