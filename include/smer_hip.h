@@ -55,6 +55,8 @@
  *                        token, or any pitch) forced ahead of any grammar step
  *   smer_bar_clock       the bar clock: a note span never passes the bar line
  *                        and ends only on it, ahead of any grammar step
+ *   smer_chord_ban       chord-following infill: the pitch set that holds at
+ *                        a note's onset (the bar clock's end), after the clock
  *   smer_layernorm_*   residual LayerNorm, eps 1e-5 (transformer.py:392,395,
  *                        462,466,469; final norms 274-275, 329-330)
  *   smer_embed_*         embedding gather x sqrt(d) + sinusoidal PE + dropout
@@ -592,6 +594,26 @@ int smer_bar_clock(int R, int V, float* logits, long ldl, const int32_t* state, 
                    const int8_t* targets, int max_masks, const int32_t* out_tok, int cap,
                    const uint8_t* cls, const uint8_t* units, int eos, const int32_t* bar_len,
                    int32_t* clock, smer_stream_t stream);
+/* Chord-following infill (not a reference operation): the pitch set of a note
+ * depends on where in its bar the note starts.  Run after smer_bar_clock in
+ * the same step (on the same logits, state, targets, max_masks, cap and
+ * clock), before smer_logits_template.  The clock is only read: with base = S
+ * ? T - P : T and end = base + A, end is the onset of a pitch drawn next.
+ * chord_len int32 [R] is each request's bar length L_r in sixteenths (0: the
+ * request has no chords), chord_at int8 [R, max_masks, 64] the bit row that
+ * governs each position of each mask's bar (-1: none), chord_bits uint32 [R,
+ * 16, 16] the rows (smer_logits_ban's layout: token v is bit v % 32 of word v
+ * / 32, set = banned).  pos = min(max(end, 0), min(L_r, 64) - 1), k =
+ * chord_at[(r * max_masks + mask index) * 64 + pos].  A row that is not done,
+ * has L_r > 0, a mask index in 0..max_masks-1 whose target is 0 (a note
+ * span), c = state word 7 <= cap and 0 <= k < 16 stores -100.f at
+ * logits[(2r+1) * ldl + v] for every v < V whose bit is set in row k.
+ * Nothing else is written.  V <= 512.  Status return, no allocation, no
+ * synchronisation. */
+int smer_chord_ban(int R, int V, float* logits, long ldl, const int32_t* state, int nst,
+                   const int8_t* targets, int max_masks, int cap, const int32_t* clock,
+                   const int32_t* chord_len, const int8_t* chord_at, const uint32_t* chord_bits,
+                   smer_stream_t stream);
 
 int smer_layernorm_fwd(int dtype, int M, int N, const void* x, long ldx,
                        const float* gamma, const float* beta, float eps,

@@ -126,6 +126,7 @@ SIGNATURES = {
     "smer_logprob_rows": (c_int, [c_int, c_int, c_int, P, c_long, P, P, P, P, P, c_int, P, P, P, P]),
     "smer_logits_template": (c_int, [c_int, c_int, P, c_long, P, c_int, P, P, c_int, c_int, P]),
     "smer_bar_clock": (c_int, [c_int, c_int, P, c_long, P, c_int, P, c_int, P, c_int, P, P, c_int, P, P, P]),
+    "smer_chord_ban": (c_int, [c_int, c_int, P, c_long, P, c_int, P, c_int, c_int, P, P, P, P, P]),
     "smer_layernorm_fwd": (c_int, [c_int, c_int, c_int, P, c_long, P, P, c_float, P, c_long, P,
                                    P, P]),
     "smer_layernorm_bwd_workspace": (c_size, [c_int, c_int]),

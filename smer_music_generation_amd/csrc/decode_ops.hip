@@ -1404,3 +1404,78 @@ extern "C" int smer_bar_clock(int R, int V, float* logits, long ldl, const int32
   SMER_CHECK_LAUNCH("smer_bar_clock");
   return SMER_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Chord-following infill (chords=): the pitch set a note may use depends on
+// where in its bar the note starts.  The bar clock's end = base + A (base = S ?
+// T - P : T) is exactly the onset of a pitch drawn next: a pitch is no duration
+// token, so it first closes an open group (T' = base + A) and sounds at the new
+// group's base, which is T'; with no group open A is 0 and the onset is base.
+// So a pitch after 'sep' reads the rewound position, and the second pitch of a
+// chord the first one's.  The node only reads the clock words smer_bar_clock
+// left in this same step (T, P, A, G | S << 1); it never writes them.
+//   chord_len int32 [R]: the bar's length L_r in sixteenths, 0 = no chords;
+//   chord_at int8 [R, max_masks, 64]: the bit row that governs each position
+//   of each mask's bar, -1 for none;
+//   chord_bits uint32 [R, 16, 16]: bit v of row k set = token v is banned
+//   (ban_bits' layout).
+// pos = min(max(end, 0), min(L_r, 64) - 1); k = chord_at[r, midx, pos].  A row
+// is active iff it is not done, L_r > 0, 0 <= midx < max_masks, its target is 0
+// (a note span), c = ST_COUNT <= cap and 0 <= k < 16; it stores -100.f over the
+// set bits of row k at i < V in logits row 2r + 1.  Everything else writes
+// nothing.  One wave per request, 8 tokens per lane (V <= 512),
+// logits_ban_kernel's layout; the lookups are clamped, not guarded, and only
+// the stores are predicated.
+// ---------------------------------------------------------------------------
+namespace {
+constexpr int CHORD_POS = 64, CHORD_ROWS = 16;
+}  // namespace
+
+__global__ __launch_bounds__(64) void chord_ban_kernel(
+    int R, int V, float* __restrict__ logits, long ldl, const int32_t* __restrict__ state, int nst,
+    const int8_t* __restrict__ targets, int max_masks, int cap, const int32_t* __restrict__ clock,
+    const int32_t* __restrict__ chord_len, const int8_t* __restrict__ chord_at,
+    const uint32_t* __restrict__ chord_bits) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int32_t* st = state + (long)r * nst;
+  const int done = st[ST_DONE], midx = st[ST_MIDX], c = st[ST_COUNT];
+  const int cv = clock[(long)r * CK_WORDS + (lane & (CK_WORDS - 1))];  // lane k <- word k, then broadcast
+  const int T = __shfl(cv, 0, 64), P = __shfl(cv, 1, 64), A = __shfl(cv, 2, 64);
+  const int S = (__shfl(cv, 3, 64) >> 1) & 1;
+  const int end = (S ? T - P : T) + A;
+  const int L = chord_len[r];
+  const int pos = max(min(max(end, 0), min(L, CHORD_POS) - 1), 0);
+  const long m = (long)r * max_masks + min(max(midx, 0), max_masks - 1);
+  const int tgt = (int)targets[m];
+  const int k = (int)chord_at[m * CHORD_POS + pos];
+  const int kc = min(max(k, 0), CHORD_ROWS - 1);
+  // lane's 8 tokens are byte (lane & 3) of word lane / 4
+  const uint32_t w = chord_bits[((long)r * CHORD_ROWS + kc) * 16 + (lane >> 2)];
+  const bool on = !done && L > 0 && midx >= 0 && midx < max_masks && tgt == 0 && c <= cap && k >= 0 &&
+                  k < CHORD_ROWS;
+  const uint32_t b = on ? (w >> (8 * (lane & 3))) & 0xffu : 0u;
+  float* lr = logits + (long)(2 * r + 1) * ldl;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int i = lane * 8 + j;
+    if (((b >> j) & 1u) && i < V) lr[i] = -100.f;
+  }
+}
+
+// Graph-capturable, no allocation, no synchronisation.  logits, state, targets
+// and cap are the grammar entry's own arguments (request r's row at (2r+1) *
+// ldl); clock is smer_bar_clock's, which runs ahead of this entry in the step.
+extern "C" int smer_chord_ban(int R, int V, float* logits, long ldl, const int32_t* state, int nst,
+                              const int8_t* targets, int max_masks, int cap, const int32_t* clock,
+                              const int32_t* chord_len, const int8_t* chord_at, const uint32_t* chord_bits,
+                              smer_stream_t stream) {
+  SMER_REQUIRE(R > 0 && V > 0 && V <= 512 && nst >= 9 && max_masks > 0 && cap > 0,
+               "smer_chord_ban: sizes (V <= 512)");
+  SMER_REQUIRE(ldl >= V, "smer_chord_ban: logits row stride");
+  SMER_REQUIRE(logits && state && targets && clock && chord_len && chord_at && chord_bits,
+               "smer_chord_ban: null pointer");
+  hipLaunchKernelGGL(chord_ban_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, R, V, logits, ldl, state,
+                     nst, targets, max_masks, cap, clock, chord_len, chord_at, chord_bits);
+  SMER_CHECK_LAUNCH("smer_chord_ban");
+  return SMER_OK;
+}

@@ -136,12 +136,18 @@ class _GrammarGraph:
     template kernel, on g_barlen int32 [R] (0: the request has no clock),
     g_units uint8 [V] and g_clock int32 [R, CLOCK_WORDS], which follows the
     tokens of g_out and is zeroed per call as g_out is.
+    chord: the graph (which always has the bar node) runs smer_chord_ban between
+    the clock and the template kernel, on g_chordlen int32 [R] (0: the request
+    has no chords), g_chordat int8 [R, nm, CHORD_POS] (-1: no row) and
+    g_chordbits int32 [R, CHORD_ROWS, 16]; it reads g_clock and writes only
+    logits.
     Construction allocates; load() writes a call's inputs, before the capture
     and before every later call alike."""
 
     def __init__(self, sess, key, mode, nm, keep_shape, cls_shape, *, eos, m0, lookahead, max_span,
-                 use_ring, ban, score, tpl=False, bar=False):
+                 use_ring, ban, score, tpl=False, bar=False, chord=False):
         self.key, self.mode, self.ban, self.score, self.tpl, self.bar = key, mode, ban, score, tpl, bar
+        self.chord = chord
         self.graph = None
         R, cap, dev = sess.R, sess.Tmax, sess.dev
 
@@ -171,6 +177,10 @@ class _GrammarGraph:
             b["g_barlen"] = zeros(R)
             b["g_units"] = zeros(cls_shape, dtype=torch.uint8)
             b["g_clock"] = zeros(R, ops.CLOCK_WORDS)
+        if chord:
+            b["g_chordlen"] = zeros(R)
+            b["g_chordat"] = torch.full((R, nm, ops.CHORD_POS), -1, dtype=torch.int8, device=dev)
+            b["g_chordbits"] = zeros(R, ops.CHORD_ROWS, ops.BAN_WORDS)
         # live counts: the step's grammar kernel publishes its count into a
         # pinned host ring itself (no per-step memset / D2H copy between the
         # replays); SMER_GRAMMAR_RING=0: memset + copy per step (A/B)
@@ -180,7 +190,7 @@ class _GrammarGraph:
         self.gargs = dict(eos=eos, m0=m0, trash_pos=sess.Tmax - 1, max_span=max_span,
                           ring=self.ring if use_ring else None)
 
-    def load(self, st, tg, keep, cls, src_len, ban=None, sampler=None, tape=None, bar=None):
+    def load(self, st, tg, keep, cls, src_len, ban=None, sampler=None, tape=None, bar=None, chord=None):
         """Write one call's inputs (host arrays) and clear its outputs."""
         b = self.bufs
 
@@ -200,6 +210,10 @@ class _GrammarGraph:
             up("g_barlen", bar[0])
             up("g_units", bar[1])
             b["g_clock"].zero_()
+        if self.chord:
+            up("g_chordlen", chord[0])
+            up("g_chordat", chord[1])
+            up("g_chordbits", chord[2].view(np.int32))
         if self.mode != "greedy":
             up("g_reject", np.ascontiguousarray(sampler.reject, dtype=np.uint8))
             up("g_mt_rows" if self.mode == "rows" else "g_mt", sampler.mt.view(np.int32))
@@ -223,6 +237,9 @@ class _GrammarGraph:
         if self.bar:  # the bar clock: follows the token the step before drew, then bans by the cursor
             ops.bar_clock(logits, state, targets, b["g_out"], b["g_cls"], b["g_units"], b["g_barlen"],
                           b["g_clock"], eos=self.gargs["eos"])
+        if self.chord:  # the chord at the onset the clock just computed: the pitches outside it -> -100
+            ops.chord_ban(logits, state, targets, b["g_clock"], b["g_chordlen"], b["g_chordat"],
+                          b["g_chordbits"], cap=b["g_out"].shape[1])
         if self.tpl:  # the given opening of a span: forced after the score saw the model's row
             ops.logits_template(logits, state, b["g_cls"], b["g_tape"])
         if self.mode == "greedy":
@@ -300,7 +317,7 @@ class DecodeSession:
         self._pe_ptr = model.pos_enc.pe.data_ptr()
         self.plan = None      # the _StepPlan of the last _run (None: no step has run yet)
         self._side = None     # the second chain's stream, made on first use
-        self._graphs = {}     # name ("greedy", "stream+ban", "rows+ban+bar+tpl+score", ..) -> _GrammarGraph
+        self._graphs = {}     # name ("greedy", "stream+ban", "rows+ban+bar+chord+tpl+score", ..) -> _GrammarGraph
         self._greedy = None   # the _GrammarGraph of the last call
         self.phase_s = {}     # host seconds of the last device loop's phases (bench / probes)
 
@@ -651,7 +668,8 @@ class DecodeSession:
         return t_b - t_a, time.perf_counter() - t_b
 
     def sampled_decode(self, spans, keep, reject, cls, *, eos, m0, lookahead=3, max_span=100,
-                       t=1.0, p=None, seeds=None, bans=None, score=False, templates=None, bars=None):
+                       t=1.0, p=None, seeds=None, bans=None, score=False, templates=None, bars=None,
+                       chords=None):
         """The sampled infill loop (the reference's sampling(): softmax with
         temperature, then weighted_sampling or, with p, nucleus, and its
         redraws) on device: each step is one replay of the captured
@@ -668,7 +686,7 @@ class DecodeSession:
         request form of the kernel (smer_grammar_sample_step_rows), the "rows"
         graph kept beside the unseeded "stream" one, and np.random is neither
         read nor written.  Other seeds replay that graph.
-        bans, score, templates, bars: as greedy_decode's; the scores are taken at
+        bans, score, templates, bars, chords: as greedy_decode's; the scores are taken at
         t = 1 over the whole masked distribution, whatever t and p are.
         Returns a DecodeResult whose `fails` flag the ids whose redraws ran
         out."""
@@ -707,7 +725,7 @@ class DecodeSession:
             mt_h[624] = int(st0[2])
         res = self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead, max_span=max_span,
                                    sampler=_Sampler(reject, mt_h, tp_h, seeds is not None), bans=bans,
-                                   score=score, templates=templates, bars=bars)
+                                   score=score, templates=templates, bars=bars, chords=chords)
         if seeds is None:  # the stream goes on where the device left it
             m = self._greedy.bufs["g_mt"].cpu().numpy().view(np.uint32)
             np.random.set_state(("MT19937", m[:624].copy(), int(m[624]), st0[3], st0[4]))
@@ -715,7 +733,7 @@ class DecodeSession:
                             fails=[[(x >> 16) & 1 for x in q] for q in res.ids])
 
     def greedy_decode(self, spans, keep, cls, *, eos, m0, lookahead=3, max_span=100, bans=None,
-                      score=False, templates=None, bars=None):
+                      score=False, templates=None, bars=None, chords=None):
         """Run the greedy infill loop of `spans` (generation._Span, one per
         request slot 0..len-1, freshly started, sources prefilled) entirely
         on device: each step is one replay of the captured decoder step +
@@ -749,13 +767,23 @@ class DecodeSession:
         call, and the clock words are zeroed per call.  None: the graphs
         without that node, as ever (generation passes None when no request
         sets fill_bar; a list of zeros runs the node on rows it leaves alone,
-        which is how tools/barclock_bench.py prices it)."""
+        which is how tools/barclock_bench.py prices it).
+        chords (chord-following infill): per span None or (L: the bar's length in
+        sixteenths, 1..CHORD_POS; the positions' table int8 [masks, CHORD_POS]: the
+        bit row that governs each position of each mask's bar, -1 for none; bit
+        rows uint32 [k <= CHORD_ROWS, 16]).  Needs `bars` (zeros will do: the
+        node reads the clock's words).  With any span chorded -- or a list of
+        None, which runs the node on all-free tables -- the call replays the
+        '+bar+chord' graph of its mode, whose extra node (smer_chord_ban) sits
+        between the clock and the template kernel; the three tables are the
+        graph's own buffers refreshed per call, so another progression replays
+        that graph.  None: the graphs without that node, as ever."""
         return self._grammar_decode(spans, keep, cls, eos=eos, m0=m0, lookahead=lookahead,
                                     max_span=max_span, bans=bans, score=score, templates=templates,
-                                    bars=bars)
+                                    bars=bars, chords=chords)
 
     def _grammar_decode(self, spans, keep, cls, *, eos, m0, lookahead, max_span, sampler=None, bans=None,
-                        score=False, templates=None, bars=None):
+                        score=False, templates=None, bars=None, chords=None):
         """greedy_decode, or with `sampler` (a _Sampler) sampled_decode."""
         R = len(spans)
         if R > self.R:
@@ -831,6 +859,33 @@ class DecodeSession:
             bar = (bl_h, np.array(unit_table(spans[0].v), dtype=np.uint8))  # (a writable copy: the table is read-only)
             gname += "+bar"
             gkey += ("bar",)
+        # chord-following infill: a graph of its own after the clock, whose three
+        # tables are its own buffers; a call without any replays the graphs that
+        # never held the node
+        chord = None
+        if chords is not None:
+            if len(chords) != R:
+                raise ValueError("one chords entry (or None) per span")
+            if bar is None:
+                raise ValueError("chords: the chord node reads the bar clock (pass bars, zeros will do)")
+            cl_h = np.zeros(self.R, dtype=np.int32)
+            ca_h = np.full((self.R, nm, ops.CHORD_POS), -1, dtype=np.int8)
+            cb_h = np.zeros((self.R, ops.CHORD_ROWS, ops.BAN_WORDS), dtype=np.uint32)
+            for r, ch in enumerate(chords):
+                if ch is None:
+                    continue
+                at = np.asarray(ch[1], dtype=np.int8).reshape(-1, ops.CHORD_POS)[:nm]
+                bits = np.asarray(ch[2], dtype=np.uint32).reshape(-1, ops.BAN_WORDS)
+                if not 1 <= int(ch[0]) <= ops.CHORD_POS or len(bits) > ops.CHORD_ROWS or \
+                        (at.size and not -1 <= at.min() <= at.max() < len(bits)):
+                    raise ValueError("chords: a bar of 1..%d sixteenths, at most %d bit rows, indices -1 .. rows - 1"
+                                     % (ops.CHORD_POS, ops.CHORD_ROWS))
+                cl_h[r] = int(ch[0])
+                ca_h[r, :len(at)] = at
+                cb_h[r, :len(bits)] = bits
+            chord = (cl_h, ca_h, cb_h)
+            gname += "+chord"
+            gkey += ("chord", ops.CHORD_POS, ops.CHORD_ROWS)
         # infill templates: once more a graph of its own, whose tape is device
         # data; a call without any replays the graphs that never held the node
         tape = None
@@ -855,7 +910,7 @@ class DecodeSession:
                 raise ValueError("score: the device path scores vocabularies up to 512 tokens")
             gname += "+score"
             gkey += ("score",)
-        inputs = (st, tg, keep, cls, self.src_len, ban, sampler, tape, bar)
+        inputs = (st, tg, keep, cls, self.src_len, ban, sampler, tape, bar, chord)
         gg = self._graphs.get(gname)
         if gg is not None and gg.key == gkey:
             # the captured step + grammar graph of an earlier call with the
@@ -870,7 +925,8 @@ class DecodeSession:
             self._graphs.pop(gname, None)  # a stale graph's buffers go before the new ones are made
             gg = _GrammarGraph(self, gkey, mode, nm, keep.shape, cls.shape, eos=eos, m0=m0,
                                lookahead=lookahead, max_span=max_span, use_ring=use_ring,
-                               ban=ban is not None, score=score, tpl=tape is not None, bar=bar is not None)
+                               ban=ban is not None, score=score, tpl=tape is not None, bar=bar is not None,
+                               chord=chord is not None)
             gg.load(*inputs)
             warm_s, capture_s = self._capture_grammar(gg)
             self._graphs[gname] = gg

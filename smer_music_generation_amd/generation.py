@@ -41,6 +41,10 @@ Differences, all opt-in keywords with reference defaults:
     fill its bar exactly (a clock in sixteenths follows the tokens drawn and
     masks what would pass the bar line or end the span beside it);
     `bar_units` and `bar_fill` are its public helpers.
+  * `chords=None` on the same three: the harmony of the infilled bars, a
+    pitch set per segment of a bar; the set that holds at a note's onset (the
+    bar clock's position) masks the other pitches (`chord_tones` and
+    `pitch_onsets` are its public helpers).
 The grammar state machine, the -100 logit masking, the float64 softmax and
 the numpy RNG consumption are the reference's, so with the same
 `np.random` state the same token ids come out.
@@ -417,6 +421,25 @@ def pitch_set(lo=None, hi=None, classes=None):
     return out
 
 
+def _is_collection(x):
+    return isinstance(x, (list, tuple, set, frozenset, range, np.ndarray))
+
+
+def _midi_set(x, name):
+    """The sorted tuple of the MIDI numbers of the collection x (`pitches=`, or a
+    segment of `chords=`): every entry an int in [21, 108] (no bool, no float),
+    and at least one.  Raises ValueError."""
+    out = set()
+    for e in (x.tolist() if isinstance(x, np.ndarray) else x):
+        if isinstance(e, (bool, np.bool_)) or not isinstance(e, (int, np.integer)) or \
+                not PITCH_MIN <= e <= PITCH_MAX:
+            raise ValueError("%s: every entry is an int in [%d, %d] (got %r)" % (name, PITCH_MIN, PITCH_MAX, e))
+        out.add(int(e))
+    if not out:
+        raise ValueError("%s: an empty set allows no note" % name)
+    return tuple(sorted(out))
+
+
 def _check_pitches(pitches, tracks, n=None):
     """Validated pitch constraints of a call.  n None (the plugin call):
     `tracks` is its tracks_to_generate and the result None (unconstrained) or
@@ -433,23 +456,13 @@ def _check_pitches(pitches, tracks, n=None):
     and [[60, 62, 64]] * n is that set spelled per request.  Every entry of a
     set is an int in [21, 108] (no bool, no float) and every set is
     non-empty.  Raises ValueError; touches neither the model nor np.random."""
-    def coll(x):
-        return isinstance(x, (list, tuple, set, frozenset, range, np.ndarray))
+    coll = _is_collection
 
     def one_set(x):
         if not coll(x):
             raise ValueError("pitches: a collection of MIDI note numbers, or a dict of them per "
                              "track (got %r)" % (x,))
-        out = set()
-        for e in (x.tolist() if isinstance(x, np.ndarray) else x):
-            if isinstance(e, (bool, np.bool_)) or not isinstance(e, (int, np.integer)) or \
-                    not PITCH_MIN <= e <= PITCH_MAX:
-                raise ValueError("pitches: every entry is an int in [%d, %d] (got %r)"
-                                 % (PITCH_MIN, PITCH_MAX, e))
-            out.add(int(e))
-        if not out:
-            raise ValueError("pitches: an empty set allows no note")
-        return tuple(sorted(out))
+        return _midi_set(x, "pitches")
 
     def one_request(x, trk):
         if x is None:
@@ -746,11 +759,179 @@ def _check_fill_bar(fill_bar, n=None):
     return _per_request(fill_bar, n, one, "fill_bar", "bool")
 
 
+# --------------------------------------------------------------------------
+# chord-following infill (`chords=`): the pitch set that holds at a note's onset
+# --------------------------------------------------------------------------
+CHORD_POS, CHORD_SETS = 64, 16  # the longest bar under chords= in sixteenths; distinct effective sets per request
+_CHORD_KINDS = {'maj': (0, 4, 7), 'min': (0, 3, 7), 'dim': (0, 3, 6), 'aug': (0, 4, 8), '7': (0, 4, 7, 10),
+                'maj7': (0, 4, 7, 11), 'min7': (0, 3, 7, 10)}
+
+
+def chord_tones(root, kind='maj'):
+    """The pitch classes of a chord, for pitch_set(classes=...): root is a pitch
+    class or a MIDI number (taken mod 12), kind one of 'maj' 'min' 'dim' 'aug'
+    '7' 'maj7' 'min7'.  chord_tones(5, 'maj') is F major: (5, 9, 0)."""
+    if isinstance(root, (bool, np.bool_)) or not isinstance(root, (int, np.integer)):
+        raise ValueError("chord_tones: root is an int (got %r)" % (root,))
+    if kind not in _CHORD_KINDS:
+        raise ValueError("chord_tones: kind is one of %s (got %r)" % (" ".join(sorted(_CHORD_KINDS)), kind))
+    return tuple((int(root) + i) % 12 for i in _CHORD_KINDS[kind])
+
+
+def pitch_onsets(vocab, tokens):
+    """[(onset, midi), ...] of one span's tokens (strings or ids): every pitch
+    token with the position in sixteenths from the bar line at which it sounds,
+    by the `_BarClock` rule -- the clock's `end` before the token: a pitch first
+    closes an open duration group and sounds where the next one starts, a pitch
+    after 'sep' at the rewound position, the second pitch of a chord at the
+    first one's."""
+    table = vocab._char2idx
+    cls = np.zeros(vocab.vocab_size, dtype=np.uint8)
+    cls[vocab.duration_only_indices] |= 4
+    cls[vocab.sep_indices] |= 8
+    ck = _BarClock(255, cls, unit_table(vocab))
+    pitch, out = _pitch_mask(vocab), []
+    for x in (tokens.tolist() if isinstance(tokens, np.ndarray) else tokens):
+        i = table[x] if isinstance(x, str) else int(x)
+        if pitch[i]:
+            out.append((ck.end, int(vocab.index2char(i)[2:])))
+        ck.advance_id(i)
+    return out
+
+
+class _Chords(namedtuple("_Chords", "L at rows sets")):
+    """The resolved `chords=` of one request: L the bar's length in sixteenths;
+    at int8 [masks, CHORD_POS], the ban row that governs each position of each
+    mask's bar (-1: none; only note spans carry any); rows boolean [k <=
+    CHORD_SETS, V], True on every pitch token outside the row's effective set;
+    sets, the sorted tuple of MIDI numbers of each row."""
+    __slots__ = ()
+
+    def row_at(self, mask_idx, end):
+        """The ban row that governs a pitch drawn at clock value `end`, or -1."""
+        if not 0 <= mask_idx < len(self.at):
+            return -1
+        return int(self.at[mask_idx, min(max(int(end), 0), min(self.L, CHORD_POS) - 1)])
+
+
+def _mask_layout(events, tracks_to_generate, bars_to_generate):
+    """(bar, track, first mask index) of every masked track-bar in the order
+    `mask_targets` builds the masks (for each bar, for each track: r, d, o, p,
+    and t after the last track), and the number of masks."""
+    names = track_names_of(events)
+    out, at = [], 0
+    for b in bars_to_generate:
+        for t in tracks_to_generate:
+            out.append((int(b), int(t), at))
+            at += 5 if names.index('track_%d' % t) == len(names) - 1 else 4
+    return out, at
+
+
+def _check_chords(chords, requests, allowed, vocab, n=None):
+    """Validated `chords=` of a call: per request None or its `_Chords`.  n None
+    (the plugin call): one value; with n requests one value for all of them (None
+    or a dict) or a list or tuple of n.  requests: (events, tracks_to_generate,
+    bars_to_generate) per request; allowed: `_check_pitches`' value per request.
+    One request's value is a dict: a key is a bar number of bars_to_generate
+    (every track of tracks_to_generate) or a (bar, track) tuple (that track only,
+    replacing the bar's entry for it); a value is a sequence of segments (start,
+    pitches): start an int in sixteenths from the bar line, the first 0, strictly
+    ascending, below L = bar_units(events) <= 64; pitches a collection of MIDI
+    numbers in [21, 108].  The effective set of a segment is its set intersected
+    with the track's `pitches=` set, if it has one; it must not be empty, and a
+    request has at most CHORD_SETS distinct ones.  Raises ValueError; touches
+    neither the model nor np.random."""
+    def is_int(x):
+        return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+    def one_request(x, req, alw):
+        if x is None:
+            return None
+        if not isinstance(x, dict):
+            raise ValueError("chords: a dict {bar or (bar, track): [(start, pitches), ...]} (got %r)" % (x,))
+        events, trk, brs = req
+        trk, brs = [int(t) for t in trk], [int(b) for b in brs]
+        per = {}  # (bar, track) -> segments; the (bar, track) keys replace the bar keys
+        for both in (False, True):
+            for key, segs in x.items():
+                if isinstance(key, tuple) != both:
+                    continue
+                if both:
+                    if len(key) != 2 or not is_int(key[0]) or not is_int(key[1]):
+                        raise ValueError("chords: a key is a bar number or a (bar, track) tuple (got %r)" % (key,))
+                    b, ts = int(key[0]), [int(key[1])]
+                    if ts[0] not in trk:
+                        raise ValueError("chords: track %r is not in tracks_to_generate %r" % (key[1], trk))
+                elif not is_int(key):
+                    raise ValueError("chords: a key is a bar number or a (bar, track) tuple (got %r)" % (key,))
+                else:
+                    b, ts = int(key), trk
+                if b not in brs:
+                    raise ValueError("chords: bar %r is not in bars_to_generate %r" % (b, brs))
+                for t in ts:
+                    per[b, t] = segs
+        if not per:
+            return None
+        L = bar_units(events)
+        if L > CHORD_POS:
+            raise ValueError("chords: a bar of %d sixteenths (at most %d under chords=)" % (L, CHORD_POS))
+        layout, n_masks = _mask_layout(events, trk, brs)
+        midi = _table(vocab, "midi", lambda v: {int(v.index2char(i)[2:]): i for i in v.pitch_indices})
+        at, sets = np.full((n_masks, CHORD_POS), -1, dtype=np.int8), []
+        for b, t, m in layout:
+            segs = per.get((b, t))
+            if segs is None:
+                continue
+            if isinstance(segs, (str, bytes, dict)) or not hasattr(segs, "__len__") or len(segs) == 0:
+                raise ValueError("chords: bar %d, track %d: a non-empty sequence of (start, pitches) segments" % (b, t))
+            starts = []
+            for seg in segs:
+                if isinstance(seg, (str, bytes)) or not hasattr(seg, "__len__") or len(seg) != 2:
+                    raise ValueError("chords: a segment is (start, pitches) (got %r)" % (seg,))
+                start, ps = seg
+                if not is_int(start):
+                    raise ValueError("chords: a start is an int in sixteenths (got %r)" % (start,))
+                if not _is_collection(ps):
+                    raise ValueError("chords: a segment's pitches are a collection of MIDI note numbers (got %r)"
+                                     % (ps,))
+                if int(start) != 0 if not starts else int(start) <= starts[-1]:
+                    raise ValueError("chords: bar %d, track %d: starts begin at 0 and ascend strictly" % (b, t))
+                if int(start) >= L:
+                    raise ValueError("chords: start %d is outside a bar of %d sixteenths" % (start, L))
+                eff = _midi_set(ps, "chords")
+                if alw and t in alw:
+                    eff = tuple(p for p in eff if p in alw[t])
+                    if not eff:
+                        raise ValueError("chords: bar %d, track %d, start %d: no pitch is left under pitches="
+                                         % (b, t, start))
+                if eff not in sets:
+                    if len(sets) == CHORD_SETS:
+                        raise ValueError("chords: more than %d distinct pitch sets in one request" % CHORD_SETS)
+                    sets.append(eff)
+                at[m, int(start):] = sets.index(eff)  # the last segment with start <= position governs
+                starts.append(int(start))
+        rows = np.zeros((len(sets), vocab.vocab_size), dtype=bool)
+        for k, s in enumerate(sets):
+            rows[k, vocab.pitch_indices] = True
+            rows[k, [midi[p] for p in s]] = False
+        return _Chords(L, _frozen(at), _frozen(rows), tuple(sets))
+
+    if n is None:
+        if isinstance(chords, (list, tuple)):
+            raise ValueError("chords is one dict here")
+        return one_request(chords, requests[0], allowed[0])
+    if isinstance(chords, (list, tuple)):
+        if len(chords) != n:
+            raise ValueError("chords: one value, or one per request (%d)" % n)
+        return [one_request(x, rq, a) for x, rq, a in zip(chords, requests, allowed)]
+    return [one_request(chords, rq, a) for rq, a in zip(requests, allowed)]
+
+
 class _Span:
     """Decoding state of one request: mask index, span tokens, grammar flags."""
 
     def __init__(self, vocab, src, mask_target, all_controls, no_whole, greedy, logger, t=1.0,
-                 p=None, rng=np.random, bans=None, score=False, template=None, bar_len=0):
+                 p=None, rng=np.random, bans=None, score=False, template=None, bar_len=0, chords=None):
         self.v = vocab
         self.t = t
         self.p = p
@@ -771,9 +952,16 @@ class _Span:
         # (0: off); the clock follows the tokens of the note span being drawn,
         # and `fill` receives (cursor, bar_len) of every note span that ends
         self.bar_len = int(bar_len)
+        # chord-following infill (chords=): the request's `_Chords`, or None.  The
+        # clock runs whenever the span has chords or a bar length; it bans by the
+        # bar line only when bar_len > 0.  chord_spans receives, per constrained
+        # note span, (onset, midi, allowed set) of every pitch pushed
+        self.chords = chords
         self.clock = _BarClock(bar_len, grammar_tables(vocab, all_controls)[1], unit_table(vocab)) \
-            if self.bar_len else None
+            if self.bar_len or chords is not None else None
         self.fill = []
+        self.chord_spans = []
+        self._chord_cur = None
         self.src = src
         self.mask_target = mask_target
         self.all_controls = set(int(c) for c in all_controls)
@@ -797,20 +985,31 @@ class _Span:
         self.in_pitch = self.in_rest = self.in_sep = self.in_continue = False
         if self.clock is not None:
             self.clock.reset()
+        self._chord_cur = None
+        if self.chords is not None and not self.done and self._note_span() and \
+                self.chords.row_at(self.mask_idx, 0) >= 0:
+            self._chord_cur = []
+            self.chord_spans.append(self._chord_cur)
 
     def _note_span(self):
         return self.mask_idx < len(self.mask_target) and _target_code(self.mask_target[self.mask_idx]) == 0
 
     def clock_ban(self):
-        """Boolean [V]: what the bar clock bans for the next draw (note spans only), or None."""
+        """Boolean [V]: what the bar clock and the chord at the clock's `end` (the
+        onset of a pitch drawn next) ban for the next draw (note spans only), or
+        None."""
         if self.clock is None or self.done or not self._note_span():
             return None
-        return self.clock.banned(self.v)
+        ban = self.clock.banned(self.v) if self.bar_len else None
+        k = -1 if self.chords is None else self.chords.row_at(self.mask_idx, self.clock.end)
+        if k >= 0:
+            ban = self.chords.rows[k] if ban is None else ban | self.chords.rows[k]
+        return ban
 
     def _span_ends(self):
         """A span ended (this_in still holds it, the dropped last token
         included): under the bar clock a note span reports its cursor."""
-        if self.clock is not None and self._note_span():
+        if self.bar_len and self._note_span():
             self.fill.append((bar_fill(self.v, self.this_in[1:-1])[0], self.bar_len))
 
     def prefix(self):
@@ -946,6 +1145,10 @@ class _Span:
         a control token brings its <eos>; at <eos> or the 100-token cap the span
         goes to tgt_inp / total without its last token and the next mask starts."""
         if self.clock is not None:
+            if self._chord_cur is not None and idx in self._pitch:
+                end = self.clock.end
+                k = self.chords.row_at(self.mask_idx, end)
+                self._chord_cur.append((end, int(ev[2:]), self.chords.sets[k] if k >= 0 else None))
             self.clock.advance_id(idx)
         this_in, this_ev = self.this_in, self.this_ev
         if idx in self.all_controls:
@@ -986,18 +1189,20 @@ def _prepare(events, vocab, tracks_to_generate, bars_to_generate):
     return src, mtn, mbn, target, no_whole
 
 
-class _Slot(namedtuple("_Slot", "src mask_track_names mask_bar_names target no_whole t p seed bans tpl bar_len")):
+class _Slot(namedtuple("_Slot", "src mask_track_names mask_bar_names target no_whole t p seed bans tpl bar_len "
+                                "chords")):
     """One decode slot (a request, or one take of it), immutable: `_prepare`'s
     five values and the request's validated keywords -- t, p, the effective
     seed (None: the global stream), `_request_bans`' pair, `_check_template`'s
-    rows and the bar length in sixteenths (0: no clock)."""
+    rows, the bar length in sixteenths (0: no clock) and `_check_chords`'
+    record (None: no chords)."""
     __slots__ = ()
 
     def span(self, vocab, all_controls, greedy, logger, score):
         """A fresh `_Span` of the slot; a seeded one starts its stream anew."""
         rng = np.random if self.seed is None else np.random.RandomState(self.seed)
         return _Span(vocab, self.src, self.target, all_controls, self.no_whole, greedy, logger, self.t,
-                     self.p, rng, self.bans, score, self.tpl, self.bar_len)
+                     self.p, rng, self.bans, score, self.tpl, self.bar_len, self.chords)
 
 
 # A call's requests, resolved: the slots in decode order (request i takes[i] times in a row; takes None:
@@ -1018,12 +1223,12 @@ def _masked_request(vocab, events, tracks_to_generate, bars_to_generate, allowed
 
 
 def _resolve(requests, vocab, all_controls, n, *, t, p, variations, seed, pitches, logprobs, rank,
-             template, fill_bar, checked=None):
+             template, fill_bar, chords=None, checked=None):
     """Validate a call's keywords and build its slots.  n: the number of
     `requests` for generation_batch (a keyword is one value, or one per
     request), None for the plugin call (one request, one value each).  Raises
     ValueError in the order t/p, variations, seed, pitches, logprobs/rank,
-    fill_bar, template; touches neither the model nor np.random.
+    fill_bar, chords, template; touches neither the model nor np.random.
     checked(seeds, allowed): the plugin call's own step between the keyword
     checks and the decode (its stats, its use_kv_cache check); it has always
     come before the request is prepared, and with a template after that."""
@@ -1037,6 +1242,7 @@ def _resolve(requests, vocab, all_controls, n, *, t, p, variations, seed, pitche
     allowed = each(_check_pitches(pitches, requests[0][1] if one else [tr for _, tr, _ in requests], n))
     score = _check_score(logprobs, rank, variations)
     bar_lens = [bar_units(ev) if fb else 0 for (ev, _, _), fb in zip(requests, each(_check_fill_bar(fill_bar, n)))]
+    chord_recs = each(_check_chords(chords, requests, allowed, vocab, n))
     if checked is not None and template is None:
         checked(seeds, allowed)
     try:
@@ -1051,8 +1257,8 @@ def _resolve(requests, vocab, all_controls, n, *, t, p, variations, seed, pitche
         template = [None] * n
     elif not isinstance(template, (list, tuple)) or len(template) != n:
         raise ValueError("template: None, or one value per request (%d)" % n)
-    slots = [_Slot(*q, a, b, None, bn, _check_template(x, vocab, q[0], q[3], all_controls, q[4], bn, bl), bl)
-             for (q, bn), (a, b), x, bl in zip(preps, tps, template, bar_lens)]
+    slots = [_Slot(*q, a, b, None, bn, _check_template(x, vocab, q[0], q[3], all_controls, q[4], bn, bl, ch), bl, ch)
+             for (q, bn), (a, b), x, bl, ch in zip(preps, tps, template, bar_lens, chord_recs)]
     if checked is not None and had_template:
         checked(seeds, allowed)
     if takes is not None:  # the expanded list: take k of request i is a slot of its own
@@ -1086,7 +1292,8 @@ class _Precision:
 def generation_all(model, events, device, vocab, logger, all_controls, tracks_to_generate,
                    bars_to_generate, *, greedy=False, use_kv_cache=True, stats=None,
                    precision="fp32", warm=True, device_grammar=True, t=1.0, p=None, variations=None,
-                   seed=None, pitches=None, logprobs=False, rank=False, template=None, fill_bar=False):
+                   seed=None, pitches=None, logprobs=False, rank=False, template=None, fill_bar=False,
+                   chords=None):
     """`generation.py:468-696`.  Returns (restored '<U9' tokens,
     mask_track_names, mask_bar_names) or None (nothing masked / on error,
     after printing it, as the reference does).  `stats` (a dict, opt-in)
@@ -1218,7 +1425,34 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
     step graphs named '+bar' run the clock (smer_bar_clock); a call without
     the keyword replays the graphs it always did.  Anything but a bool, or a
     bar whose length is no integer in 1..255 sixteenths, raises ValueError
-    before the model or np.random is touched."""
+    before the model or np.random is touched.
+    chords: None (default): today's behaviour, graphs and stats keys.  A dict
+    gives the harmony of the infilled bars: a key is a bar number of
+    bars_to_generate (every track of tracks_to_generate) or a (bar, track) tuple
+    (that track only; it replaces the bar's entry for that track); a value is a
+    sequence of segments (start, pitches) -- start an int in sixteenths from the
+    bar line, the first 0, strictly ascending; pitches a collection of MIDI
+    numbers as `pitches=` takes (pitch_set(classes=chord_tones(5, 'maj'))).
+    The segment that governs a position is the last one that starts at or
+    before it.  It is a masked draw, like the bar clock's: in a note span whose
+    (bar, track) has segments, with `end` the clock's value before the draw --
+    exactly the onset of a pitch drawn next: a pitch closes an open duration
+    group and sounds where the next one starts, after 'sep' at the rewound
+    position, as the second note of a chord at the first one's -- the logit of
+    every pitch token outside the set of the segment that governs min(end, L -
+    1) becomes -100.0, at the place in the row where the bar clock bans (after
+    the score has read the row, before the template).  No other token and no
+    other span is touched, and the clock runs whether or not fill_bar is set.
+    A segment's set is intersected with the track's `pitches=` set, if any.
+    logprobs=True and score_infill report what they report without the keyword.
+    Under `template=` a pitch token item that its onset's chord bans is
+    rejected; with rhythm_template one call reharmonises a bar and keeps its
+    rhythm.  With variations all takes carry the chords.  `stats` receives
+    'chords': per take, per constrained note span, the list of (onset, midi,
+    allowed set) of its pitches.  On the device the step graphs named
+    '+bar+chord' run smer_chord_ban after the clock; a call without the keyword
+    replays the graphs it always did.  `_check_chords` lists what raises
+    ValueError, before the model or np.random is touched."""
     t0 = time.perf_counter()
 
     def checked(seeds, allowed):
@@ -1230,7 +1464,8 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
     try:
         rq = _resolve([(events if variations is None else list(events), tracks_to_generate, bars_to_generate)],
                       vocab, all_controls, None, t=t, p=p, variations=variations, seed=seed, pitches=pitches,
-                      logprobs=logprobs, rank=rank, template=template, fill_bar=fill_bar, checked=checked)
+                      logprobs=logprobs, rank=rank, template=template, fill_bar=fill_bar, chords=chords,
+                      checked=checked)
     except _Unprepared as e:  # reference behaviour (generation.py:695-696)
         print(e.args[0])
         return None
@@ -1243,6 +1478,8 @@ def generation_all(model, events, device, vocab, logger, all_controls, tracks_to
                     stats["steps"] = st["steps"]
                     if rq.slots[0].bar_len:
                         stats["bar_fill"] = st["bar_fill"]
+                    if rq.slots[0].chords is not None:
+                        stats["chords"] = st["chords"]
                     if rq.score:
                         stats["logprobs"], stats["scores"] = st["logprobs"], st["scores"]
                     if rank:
@@ -1281,9 +1518,18 @@ def _device_rows(rows):
 
 def _device_bars(spans):
     """`bars=` of the device decodes: per span its bar length in sixteenths (0:
-    no clock); None when no span has one (the graphs without the clock replay)."""
+    no clock); None when no span has one and none has chords (the graphs
+    without the clock replay; the chord node reads the clock's words)."""
     bars = [sp.bar_len for sp in spans]
-    return bars if any(bars) else None
+    return bars if any(bars) or any(sp.chords is not None for sp in spans) else None
+
+
+def _device_chords(spans):
+    """`chords=` of the device decodes: per span None or (L, the positions' row
+    table int8 [masks, CHORD_POS], the bit rows uint32 [k, 16]); None when no
+    span has chords (the graphs without the chord node replay)."""
+    return _device_rows(None if sp.chords is None else (sp.chords.L, sp.chords.at, ban_bits(sp.chords.rows))
+                        for sp in spans)
 
 
 def _replay(spans, res, logger, sampled=True):
@@ -1326,6 +1572,7 @@ def _decode_on_device(sess, spans, vocab, all_controls, logger, greedy, seeds, s
     touches no global state: fresh spans start fresh RandomStates)."""
     keep, cls = grammar_tables(vocab, all_controls)
     kw = dict(eos=vocab.eos_index, m0=vocab.char2index('m_0'), score=score, bars=_device_bars(spans),
+              chords=_device_chords(spans),
               templates=_device_rows(sp.tpl for sp in spans),
               bans=_device_rows(None if sp.ban_of_mask is None else (sp.ban_of_mask, ban_bits(sp.ban_rows))
                                 for sp in spans))
@@ -1391,6 +1638,8 @@ def _generation_all(model, device, vocab, logger, all_controls, slot, greedy, us
                     stats["scores"] = [float(np.sum(stats["logprobs"][0]))]
                 if slot.bar_len:
                     stats["bar_fill"] = [list(st.fill)]
+                if slot.chords is not None:
+                    stats["chords"] = [list(st.chord_spans)]
         return restore_marked_input(_src_tokens(vocab, src), st.total), slot.mask_track_names, slot.mask_bar_names
     except Exception as e:  # reference behaviour (generation.py:695-696)
         print(e)
@@ -1476,7 +1725,7 @@ def _batch_session(model, R, Smax, Tmax, precision, exact_tmax=False, warm=True,
 def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logger=None,
                      max_tgt=None, precision=None, return_stats=False, device_grammar=True,
                      warm=True, t=1.0, p=None, variations=None, seed=None, pitches=None,
-                     logprobs=False, rank=False, template=None, fill_bar=False):
+                     logprobs=False, rank=False, template=None, fill_bar=False, chords=None):
     """Decode many infill requests in lockstep on one KV-cached session.
 
     requests: list of (events, tracks_to_generate, bars_to_generate).
@@ -1556,6 +1805,16 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
     alone.  The stats dict then receives 'bar_fill': per entry of 'generated'
     None, or one (cursor, L) per note span.  Validated before anything else is
     touched (ValueError).
+    chords: chord-following infill (see generation_all): None, one dict for all
+    requests, or a list or tuple with one value (None or a dict) per request;
+    with variations all takes of a request carry it.  A call in which no
+    request has chords replays the step graphs it always did; otherwise the
+    '+bar+chord' graph of its mode ('greedy+bar+chord', 'rows+ban+bar+chord+tpl',
+    ..), in which the clock node is always present (requests without fill_bar
+    have bar length 0) and the requests without chords read an all-free table.
+    The stats dict then receives 'chords': per entry of 'generated' None, or per
+    constrained note span the list of (onset, midi, allowed set).  Validated
+    before anything else is touched (ValueError).
     Returns a list of (restored, mask_track_names, mask_bar_names) (None
     where nothing was masked), and optionally {'tokens', 'steps', 'sources',
     'prefill_rows', 'seeds' (the effective seed of every entry of 'generated',
@@ -1564,7 +1823,7 @@ def generation_batch(model, requests, vocab, all_controls, *, greedy=True, logge
     t0 = time.perf_counter()
     rq = _resolve([(list(ev), tr, br) for ev, tr, br in requests], vocab, all_controls, len(requests), t=t,
                   p=p, variations=variations, seed=seed, pitches=pitches, logprobs=logprobs, rank=rank,
-                  template=template, fill_bar=fill_bar)
+                  template=template, fill_bar=fill_bar, chords=chords)
     out, stats = _decode_batch(model, rq, vocab, all_controls, greedy=greedy, logger=logger, max_tgt=max_tgt,
                                precision=precision, device_grammar=device_grammar, warm=warm, t0=t0)
     return (out, stats) if return_stats else out
@@ -1683,6 +1942,8 @@ def _decode_batch(model, rq, vocab, all_controls, *, greedy, logger, device_gram
         extra["order"] = order
     if any(s.bar_len for s in slots):
         extra["bar_fill"] = [list(st.fill) if st.bar_len else None for st in spans]
+    if any(s.chords is not None for s in slots):
+        extra["chords"] = [list(st.chord_spans) if st.chords is not None else None for st in spans]
     return out, {**extra, "tokens": tokens, "steps": steps, "prepare_s": t1 - t0,
                  "prefill_s": t2 - t1, "decode_s": t3 - t2, "step_call_s": t_dev,
                  "request_latency_s": latency, "kv_row_reads": kv_reads,
@@ -2022,7 +2283,7 @@ def score_infill(model, events, device, vocab, all_controls, tracks_to_generate,
 # --------------------------------------------------------------------------
 # infill templates: the opening of a span is given, the model writes the rest
 # --------------------------------------------------------------------------
-def _check_template(template, vocab, src, target, all_controls, no_whole, bans=None, bar_len=0):
+def _check_template(template, vocab, src, target, all_controls, no_whole, bans=None, bar_len=0, chords=None):
     """Validated template of one request: None stays None; otherwise one row
     per mask, in mask_targets order, each None (free) or a sequence of items
     -- a token (string or id), ANY_PITCH, or '<eos>' as the last item of a
@@ -2040,13 +2301,15 @@ def _check_template(template, vocab, src, target, all_controls, no_whole, bans=N
     bar_len (fill_bar=: the bar's length in sixteenths, 0: none): the rows are
     replayed with the bar clock, and an item the clock bans is rejected too -- a
     row that overruns the bar, ANY_PITCH at a full bar, a closing '<eos>' on a
-    bar that is not full.
+    bar that is not full.  chords (chords=: the request's `_Chords`): the
+    clock runs as well, and a pitch token item that the chord at its onset bans
+    is rejected; ANY_PITCH stays satisfiable, every effective set being non-empty.
     Touches neither the model nor np.random."""
     if template is None:
         return None
     if isinstance(template, (str, bytes)) or not hasattr(template, "__len__"):
         raise ValueError("template: one row per mask (got %r)" % (template,))
-    sp = _Span(vocab, src, target, all_controls, no_whole, True, None, bans=bans, bar_len=bar_len)
+    sp = _Span(vocab, src, target, all_controls, no_whole, True, None, bans=bans, bar_len=bar_len, chords=chords)
     if len(template) != sp.n_masks or len(target) < sp.n_masks:
         raise ValueError("template: %d rows for %d masks" % (len(template), sp.n_masks))
     V, table, pitch = vocab.vocab_size, vocab._char2idx, _pitch_mask(vocab)
@@ -2085,12 +2348,14 @@ def _check_template(template, vocab, src, target, all_controls, no_whole, bans=N
             check, ban = sp.spec()[1], sp.ban()
             keep, cb, _ = sp.governs()
             if cb is not None:
-                if cb[sp.v.pitch_indices[0]] if x is ANY_PITCH else cb[x]:
-                    raise ValueError("template: row %d, item %d: fill_bar does not allow %s there (the bar holds "
-                                     "%d of %d sixteenths)" % (k, i, "a pitch" if x is ANY_PITCH else
-                                                               repr(vocab.index2char(x)), sp.clock.end, bar_len))
+                if cb[pitch].all() if x is ANY_PITCH else cb[x]:
+                    raise ValueError("template: row %d, item %d: %s not allow %s there (the bar holds %d of %d "
+                                     "sixteenths)" % (k, i, "fill_bar does" if chords is None else "fill_bar and "
+                                                      "chords do", "a pitch" if x is ANY_PITCH else
+                                                      repr(vocab.index2char(x)), sp.clock.end,
+                                                      bar_len or chords.L))
             if x is ANY_PITCH:
-                ok = np.flatnonzero(keep & pitch)
+                ok = np.flatnonzero(keep & pitch if cb is None else keep & pitch & ~cb)
                 if check is not None:
                     ok = [j for j in ok if not check(int(j))]
                 if len(ok) == 0:

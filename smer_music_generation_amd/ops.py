@@ -893,6 +893,41 @@ def bar_clock(logits, state, targets, out_tok, cls, units, bar_len, clock, *, eo
          _p(out_tok), out_tok.shape[1], _p(cls), _p(units), int(eos), _p(bar_len), _p(clock), _stream())
 
 
+CHORD_POS = 64    # positions (sixteenths) of one mask's row of chord_at: a bar under chords= is at most this long
+CHORD_ROWS = 16   # bit rows per request of chord_bits: the distinct effective pitch sets of one request
+
+
+def chord_ban(logits, state, targets, clock, chord_len, chord_at, chord_bits, *, cap):
+    """Chord-following infill ahead of a grammar step (smer_chord_ban; after
+    bar_clock in the same step, before logits_template): for every request r
+    that is not done, has chord_len[r] > 0 and is drawing a note span, the
+    clock words bar_clock left give end = (S ? T - P : T) + A, the onset of a
+    pitch drawn next; k = chord_at[r, mask index, min(max(end, 0),
+    min(chord_len[r], 64) - 1)], and with 0 <= k < 16 the entries of logits row
+    2r + 1 whose bit is set in chord_bits[r, k] become -100.  The clock is only
+    read.  logits float32 [>= 2R, V <= 512] (rows contiguous), state int32 [R,
+    nst], targets int8 [R, max_masks], clock int32 [R, CLOCK_WORDS], chord_len
+    int32 [R] (0: no chords), chord_at int8 [R, max_masks, CHORD_POS] (-1:
+    none), chord_bits int32 [R, CHORD_ROWS, 16] (the bits of uint32 words, as
+    logits_ban's), cap: the capacity of the grammar step's out_tok rows."""
+    R, nst = state.shape
+    V = logits.shape[1]
+    for t, dt in ((logits, torch.float32), (state, torch.int32), (targets, torch.int8), (clock, torch.int32),
+                  (chord_len, torch.int32), (chord_at, torch.int8), (chord_bits, torch.int32)):
+        if t.dtype != dt or t.device != logits.device:
+            raise RuntimeError("chord_ban: expected %s on the logits' device" % dt)
+    if not all(t.is_contiguous() for t in (state, targets, clock, chord_len, chord_at, chord_bits)) or \
+            logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError("chord_ban: expected contiguous tables and logits rows")
+    if logits.shape[0] < 2 * R or targets.dim() != 2 or targets.shape[0] != R or targets.shape[1] < 1 or \
+            tuple(clock.shape) != (R, CLOCK_WORDS) or tuple(chord_len.shape) != (R,) or \
+            tuple(chord_at.shape) != (R, targets.shape[1], CHORD_POS) or \
+            tuple(chord_bits.shape) != (R, CHORD_ROWS, BAN_WORDS) or not 1 <= V <= 512 or nst < 9 or int(cap) < 1:
+        raise RuntimeError("chord_ban: shape mismatch")
+    call("smer_chord_ban", R, V, _p(logits), _ld(logits), _p(state), nst, _p(targets), targets.shape[1], int(cap),
+         _p(clock), _p(chord_len), _p(chord_at), _p(chord_bits), _stream())
+
+
 # ---------------------------------------------------------------------------
 def layernorm(x, gamma, beta, y, mean, rstd, eps=1e-5):
     M, N = x.shape
