@@ -64,6 +64,9 @@
  *   smer_wce_*           the 7-12 weighted cross-entropy criteria fused into
  *                        one pass (train.py:555-642,726-780)
  *   smer_adam            torch.optim.Adam step (train.py:264,786)
+ *   smer_grad_sqnorm_*, smer_clip_scale, smer_adam_guarded: global-norm
+ *                        gradient clipping and the non-finite step guard
+ *                        around that step (torch.nn.utils.clip_grad_norm_)
  *   smer_gemm_wgrad_bias nn.Linear weight AND bias gradients in one pass
  *                        (autograd of transformer.py:389-469 / model.py:106
  *                        linears, train.py:783)
@@ -694,6 +697,38 @@ int smer_wce_fwd_bwd(int dtype, int R, int V, const float* logits, long ldl, con
 int smer_adam(long n, float* p, const float* g, float* m, float* v, void* p_bf16,
               float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
               smer_stream_t stream);
+
+/* Global-norm gradient clipping with a non-finite step guard
+ * (torch.nn.utils.clip_grad_norm_ ahead of train.py:786 optim.step(), which
+ * the reference does not call), all on the device:
+ *
+ * _nparts: partials a range of n floats produces, ceil(n / CH) with CH a
+ *   constant of the library (0 for n <= 0).
+ * _part: part[c] = sum of squares of chunk c of g[0, n), one workgroup per
+ *   chunk, no atomics; a partial depends on its chunk's contents only (not on
+ *   n, the grid or the stream).  Nothing at or behind g + n is read.  g must
+ *   be 16-B aligned (SMER_ERR_UNSUPPORTED otherwise); n == 0 launches
+ *   nothing; n < 0 or a null pointer is SMER_ERR_INVALID.
+ * smer_clip_scale (one workgroup): sums part[0, nparts) in double in a fixed
+ *   order and writes the control block
+ *     ctl[0] = norm (fp32)
+ *     ctl[1] = min(1, max_norm / (norm + 1e-6)) evaluated in fp32 as torch
+ *              does, fl(fl(1 / fl(norm + 1e-6)) * max_norm); 0 on a skip
+ *     ctl[2] = 1 if the norm is inf or NaN (the step is to be skipped), else 0
+ *     ctl[3] += ctl[2]   (the caller zeroes it once)
+ *   max_norm > 0, +inf allowed ("measure and guard, never scale").  A partial
+ *   that overflowed fp32 (|g| of about 1e19 and above) is inf and counts as
+ *   non-finite.
+ * smer_adam_guarded: smer_adam that returns at once when ctl[2] != 0 (p, m,
+ *   v, p_bf16 keep their bits) and otherwise steps on fl32(g[i] * ctl[1]):
+ *   bit for bit smer_adam on that rounded product.  g is not written. */
+long smer_grad_sqnorm_nparts(long n);
+int smer_grad_sqnorm_part(long n, const float* g, float* part, smer_stream_t stream);
+int smer_clip_scale(int nparts, const float* part, float max_norm, float* ctl,
+                    smer_stream_t stream);
+int smer_adam_guarded(long n, float* p, const float* g, float* m, float* v, void* p_bf16,
+                      float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
+                      const float* ctl, smer_stream_t stream);
 
 int smer_cast(int src_dtype, int dst_dtype, long n, const void* src, void* dst,
               smer_stream_t stream);

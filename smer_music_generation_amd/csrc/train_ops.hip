@@ -70,14 +70,37 @@ __global__ __launch_bounds__(256) void sum_div_kernel(int n, const float* __rest
 
 // torch.optim.Adam (_single_tensor_adam): m.lerp_(g, 1-b1); v = b2 v + (1-b2) g^2;
 // p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+//
+// One templated kernel, two instantiations: the unguarded one takes
+// smer_adam's arguments and compiles to the code it always had.  GUARDED (smer_adam_guarded) reads the control block
+// of smer_clip_scale: ctl[2] != 0 (non-finite gradient norm) leaves every
+// buffer untouched, otherwise the update runs on fl32(g * ctl[1]).  The
+// product passes through an empty value barrier: without it hipcc contracts
+// the multiply into the g - m subtraction (v_fma_f32 s, g, -m) and
+// re-associates the v update, and the result is no longer smer_adam's on the
+// rounded product.  With it the two instantiations differ by the skip test
+// and one v_mul_f32 (tests/test_gradclip_gpu.py holds them bit-equal).
+__device__ __forceinline__ const float* adam_ctl(const float* ctl) { return ctl; }
+template <bool GUARDED, typename... CTL>  // CTL: (const float*) when GUARDED, else empty
 __global__ void adam_kernel(long n, float* __restrict__ p, const float* __restrict__ g,
                             float* __restrict__ m, float* __restrict__ v, bf16* __restrict__ pb,
-                            float lr, float b1, float b2, float eps, float bc1, float bc2s) {
+                            float lr, float b1, float b2, float eps, float bc1, float bc2s, CTL... ctl) {
+  static_assert(sizeof...(CTL) == (GUARDED ? 1 : 0), "the control block goes with the guarded kernel");
+  float gs = 1.f;
+  if constexpr (GUARDED) {
+    const float* __restrict__ c = adam_ctl(ctl...);
+    if (c[2] != 0.f) return;
+    gs = c[1];
+  }
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
   const float step = lr / bc1;
   for (; i < n; i += stride) {
     float gi = g[i];
+    if constexpr (GUARDED) {
+      gi = gi * gs;
+      asm volatile("" : "+v"(gi));
+    }
     float mi = m[i];
     mi = mi + (1.f - b1) * (gi - mi);
     float vi = v[i] * b2 + (1.f - b2) * gi * gi;
@@ -87,6 +110,92 @@ __global__ void adam_kernel(long n, float* __restrict__ p, const float* __restri
     v[i] = vi;
     p[i] = pi;
     if (pb) pb[i] = (bf16)pi;
+  }
+}
+
+// Global gradient norm, stage 1: part[c] = sum of squares of chunk c
+// (GN_CH floats) of a range.  256 lanes x 4 iterations x 4 independent 16-B
+// loads; lane accumulator u takes load u of every iteration (16 fmas in
+// element order), then (a0 + a1) + (a2 + a3), the wave butterfly and
+// (w0 + w1) + (w2 + w3): the order is fixed by the element's position in
+// its chunk alone, so a partial is a pure function of the chunk's contents.
+// Elements at or behind n are never read (they add an exact +0).
+constexpr int GN_CH = 16384;
+constexpr int GN_IT = 4, GN_U = 4;
+static_assert(GN_CH == GN_IT * GN_U * 256 * 4, "chunk = iterations x loads x lanes x 4 floats");
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(long n, const float* __restrict__ g,
+                                                          float* __restrict__ part) {
+  __shared__ float red[4];
+  const long base = (long)blockIdx.x * GN_CH;
+  const long rem = n - base;
+  const int cnt = rem < (long)GN_CH ? (int)rem : GN_CH;
+  const float* __restrict__ p = g + base;
+  float a[GN_U] = {0.f, 0.f, 0.f, 0.f};
+  if (cnt == GN_CH) {
+#pragma unroll
+    for (int it = 0; it < GN_IT; ++it) {
+      float4 x[GN_U];
+#pragma unroll
+      for (int u = 0; u < GN_U; ++u)
+        x[u] = *reinterpret_cast<const float4*>(p + ((it * GN_U + u) * 256 + (int)threadIdx.x) * 4);
+#pragma unroll
+      for (int u = 0; u < GN_U; ++u) {
+        a[u] = __builtin_fmaf(x[u].x, x[u].x, a[u]);
+        a[u] = __builtin_fmaf(x[u].y, x[u].y, a[u]);
+        a[u] = __builtin_fmaf(x[u].z, x[u].z, a[u]);
+        a[u] = __builtin_fmaf(x[u].w, x[u].w, a[u]);
+      }
+    }
+  } else {
+    for (int it = 0; it < GN_IT; ++it) {
+#pragma unroll
+      for (int u = 0; u < GN_U; ++u) {
+        const int e = ((it * GN_U + u) * 256 + (int)threadIdx.x) * 4;
+        float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (e + 4 <= cnt) {
+          x = *reinterpret_cast<const float4*>(p + e);
+        } else if (e < cnt) {
+          x.x = p[e];
+          if (e + 1 < cnt) x.y = p[e + 1];
+          if (e + 2 < cnt) x.z = p[e + 2];
+        }
+        a[u] = __builtin_fmaf(x.x, x.x, a[u]);
+        a[u] = __builtin_fmaf(x.y, x.y, a[u]);
+        a[u] = __builtin_fmaf(x.z, x.z, a[u]);
+        a[u] = __builtin_fmaf(x.w, x.w, a[u]);
+      }
+    }
+  }
+  float s = wave_sum((a[0] + a[1]) + (a[2] + a[3]));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// Stage 2, one workgroup: the partials summed in double (lane t takes
+// t, t + 256, .. in index order, then a fixed tree), norm = fl32(sqrt),
+// scale = min(1, max_norm / (norm + 1e-6)) in fp32 the way
+// torch.nn.utils.clip_grad_norm_ evaluates it (scalar / tensor is
+// tensor.reciprocal() * scalar: two roundings), the skip flag and the count.
+__global__ __launch_bounds__(256) void clip_scale_kernel(int nparts, const float* __restrict__ part,
+                                                         float max_norm, float* __restrict__ ctl) {
+  __shared__ double red[256];
+  double a = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) a += (double)part[i];
+  red[threadIdx.x] = a;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(red[0]);
+    const bool finite = fabsf(norm) <= 3.402823466e+38f;  // false for inf and NaN
+    const float skip = finite ? 0.f : 1.f;
+    ctl[0] = norm;
+    ctl[1] = finite ? fminf(1.f, smer_div_rn(1.f, norm + 1e-6f) * max_norm) : 0.f;
+    ctl[2] = skip;
+    ctl[3] += skip;
   }
 }
 
@@ -335,9 +444,50 @@ extern "C" int smer_adam(long n, float* p, const float* g, float* m, float* v, v
   if (n == 0) return SMER_OK;
   long blocks = (n + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v,
+  hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v,
                      (bf16*)p_bf16, lr, b1, b2, eps, bc1, bc2_sqrt);
   SMER_CHECK_LAUNCH("smer_adam");
+  return SMER_OK;
+}
+
+extern "C" int smer_adam_guarded(long n, float* p, const float* g, float* m, float* v, void* p_bf16,
+                                 float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
+                                 const float* ctl, smer_stream_t stream) {
+  SMER_REQUIRE(p && g && m && v && ctl, "smer_adam_guarded: null pointer");
+  SMER_REQUIRE(n >= 0, "smer_adam_guarded: n < 0");
+  if (n == 0) return SMER_OK;
+  long blocks = (n + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL((adam_kernel<true, const float*>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, p, g,
+                     m, v, (bf16*)p_bf16, lr, b1, b2, eps, bc1, bc2_sqrt, ctl);
+  SMER_CHECK_LAUNCH("smer_adam_guarded");
+  return SMER_OK;
+}
+
+extern "C" long smer_grad_sqnorm_nparts(long n) { return n <= 0 ? 0 : (n + GN_CH - 1) / GN_CH; }
+
+extern "C" int smer_grad_sqnorm_part(long n, const float* g, float* part, smer_stream_t stream) {
+  SMER_REQUIRE(n >= 0, "smer_grad_sqnorm_part: n < 0");
+  SMER_REQUIRE(g && part, "smer_grad_sqnorm_part: null pointer");
+  if (((uintptr_t)g & 15) != 0)
+    return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_grad_sqnorm_part: g must be 16-B aligned");
+  if (n == 0) return SMER_OK;
+  const long nparts = smer_grad_sqnorm_nparts(n);
+  SMER_REQUIRE(nparts <= (1L << 23), "smer_grad_sqnorm_part: range too long (2^37 floats at most)");
+  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3((unsigned)nparts), dim3(256), 0, (hipStream_t)stream, n, g,
+                     part);
+  SMER_CHECK_LAUNCH("smer_grad_sqnorm_part");
+  return SMER_OK;
+}
+
+extern "C" int smer_clip_scale(int nparts, const float* part, float max_norm, float* ctl,
+                               smer_stream_t stream) {
+  SMER_REQUIRE(nparts >= 0, "smer_clip_scale: nparts < 0");
+  SMER_REQUIRE(ctl && (part || nparts == 0), "smer_clip_scale: null pointer");
+  SMER_REQUIRE(max_norm > 0.f, "smer_clip_scale: max_norm must be > 0 (inf allowed, NaN not)");
+  hipLaunchKernelGGL(clip_scale_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, nparts, part,
+                     max_norm, ctl);
+  SMER_CHECK_LAUNCH("smer_clip_scale");
   return SMER_OK;
 }
 

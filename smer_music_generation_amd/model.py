@@ -260,7 +260,10 @@ class ScoreTransformer(nn.Module):
         return self._flat
 
     def flat_grad(self):
-        """Flat fp32 gradient buffer; every parameter's .grad is a view."""
+        """Flat fp32 gradient buffer; every parameter's .grad is a view.
+        After `Trainer.step` with `clip_norm` set it still holds the raw,
+        unscaled gradient: the clip scale is applied inside the Adam kernel,
+        not written back."""
         if self._grad_flat is None or self._grad_flat.device != self._flat.device:
             self._grad_flat = torch.zeros_like(self._flat)
         g = self._grad_flat

@@ -1104,6 +1104,47 @@ def adam(p, g, m, v, p_bf16, *, lr, b1, b2, eps, step):
          float(b2), float(eps), float(bc1), float(bc2s), _stream())
 
 
+def grad_sqnorm_nparts(n):
+    """Partials that grad_sqnorm_part writes for a range of n floats."""
+    return int(load().smer_grad_sqnorm_nparts(int(n)))
+
+
+def _flat_f32(t, what):
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise TypeError("%s: contiguous float32 expected" % what)
+    return t
+
+
+def grad_sqnorm_part(g, part):
+    """part[c] = sum of squares of chunk c of the flat fp32 range g, on the
+    current stream (smer_grad_sqnorm_part; g 16-B aligned)."""
+    _flat_f32(g, "grad_sqnorm_part g")
+    _flat_f32(part, "grad_sqnorm_part part")
+    if part.numel() < grad_sqnorm_nparts(g.numel()):
+        raise ValueError("grad_sqnorm_part: part holds %d of %d partials"
+                         % (part.numel(), grad_sqnorm_nparts(g.numel())))
+    call("smer_grad_sqnorm_part", g.numel(), _p(g), _p(part), _stream())
+
+
+def clip_scale(part, max_norm, ctl):
+    """ctl = [norm, scale, skip, skip count += skip] from every partial of
+    `part` (smer_clip_scale), on the current stream."""
+    _flat_f32(part, "clip_scale part")
+    _flat_f32(ctl, "clip_scale ctl")
+    if ctl.numel() < 4:
+        raise ValueError("clip_scale: ctl needs 4 floats")
+    call("smer_clip_scale", part.numel(), _p(part), float(max_norm), _p(ctl), _stream())
+
+
+def adam_guarded(p, g, m, v, p_bf16, ctl, *, lr, b1, b2, eps, step):
+    """adam() on g * ctl[1], skipped on the device when ctl[2] != 0."""
+    import math
+    bc1 = 1.0 - b1 ** step
+    bc2s = math.sqrt(1.0 - b2 ** step)
+    call("smer_adam_guarded", p.numel(), _p(p), _p(g), _p(m), _p(v), _p(p_bf16), float(lr), float(b1),
+         float(b2), float(eps), float(bc1), float(bc2s), _p(ctl), _stream())
+
+
 def cast(src, dst):
     assert src.numel() == dst.numel()
     call("smer_cast", dtype_code(src.dtype), dtype_code(dst.dtype), src.numel(), _p(src),

@@ -13,7 +13,9 @@ Adam semantics (`train.py:264`), as one stream of gfx950 kernels:
     concatenated batch; per-layer gradient slices of the flat buffer are
     all-reduced asynchronously (RCCL over xGMI) as soon as backward has
     produced them, overlapping the remaining backward kernels;
-  * Adam on the flat fp32 master buffer also refreshes the bf16 working copy.
+  * Adam on the flat fp32 master buffer also refreshes the bf16 working copy;
+  * optional (`clip_norm=`): global-norm gradient clipping and a non-finite
+    step guard, measured and applied on the device with no host round trip.
 """
 from __future__ import annotations
 
@@ -146,6 +148,20 @@ def layer_ranges(model):
     return r
 
 
+def check_clip_norm(value):
+    """`Trainer.clip_norm`: None (no clipping, no guard) or a number > 0,
+    `float('inf')` allowed (measure and guard, never scale).  Returns None or
+    the float; anything else raises ValueError."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError("clip_norm must be None or a number > 0, got %r" % (value,))
+    c = float(value)
+    if not c > 0:  # also NaN
+        raise ValueError("clip_norm must be > 0 (float('inf') allowed), got %r" % (value,))
+    return c
+
+
 class FusedAdam(torch.optim.Optimizer):
     """`torch.optim.Adam`'s state and param_groups over the Trainer's flat
     moment buffers (train.py:264 builds `Adam(model.parameters(), lr)`).
@@ -223,19 +239,34 @@ class FusedAdam(torch.optim.Optimizer):
         self.t = steps.pop() if steps else 0
 
 
+class _ClipState:
+    __slots__ = ("slots", "part", "nparts", "ctl")
+
+
 class Trainer:
     """One optimizer step per `step(batch)`; DP across the default process
     group when torch.distributed is initialised (world_size > 1)."""
 
     def __init__(self, model, vocab, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, eos_weight=0.8,
-                 group=None, grad_wire_dtype=None, broadcast=True, dp=None):
-        """grad_wire_dtype: None / torch.float32 (default, parity) or
+                 group=None, grad_wire_dtype=None, broadcast=True, dp=None, clip_norm=None):
+        """clip_norm: None (default) is the plain step.  A number c > 0 is
+        the guarded step: the global L2 norm of the whole flat gradient is
+        taken on the device, Adam runs on the gradient scaled by
+        min(1, c / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_'s rule in
+        fp32; float('inf') never scales), and a step whose norm is inf or NaN
+        is skipped on the device: master weights, moments and the bf16 copy
+        keep their bits and `skipped_steps` goes up by one.  The host is not
+        consulted, so `t` advances on a skipped step too.  Settable per step
+        like `lr`; see `grad_norm`, `clip_scale`, `skipped_steps`.
+        `model.flat_grad()` holds the raw, unscaled gradient after the step.
+        grad_wire_dtype: None / torch.float32 (default, parity) or
         torch.bfloat16 for the DP gradient all-reduce (see GradBucketer).
         broadcast: under DP, copy rank 0's parameters to every rank here.
         dp: run the data-parallel path (normaliser all-reduce, per-layer
         bucketed gradient all-reduces issued from the backward hooks) --
         default: when the process group has more than one rank; True also
         at world size 1 (the real RCCL calls and stream ordering on one GPU)."""
+        self._clip_norm = check_clip_norm(clip_norm)
         self.model = model
         self.vocab = vocab
         dev = model.flat_parameters().device
@@ -256,6 +287,7 @@ class Trainer:
         self._seed = 1
         self.grad_wire_dtype = grad_wire_dtype
         self._bucketer = None
+        self._clip = None  # guarded step's device state, built by its first step
         if self.dp and broadcast:
             broadcast_parameters(model, group)
 
@@ -267,6 +299,49 @@ class Trainer:
     @lr.setter
     def lr(self, value):
         self.optimizer.param_groups[0]["lr"] = float(value)
+
+    @property
+    def clip_norm(self):
+        return self._clip_norm
+
+    @clip_norm.setter
+    def clip_norm(self, value):
+        self._clip_norm = check_clip_norm(value)
+
+    # the last guarded step's control block (device views, no sync until
+    # read); None until a guarded step has run
+    @property
+    def grad_norm(self):
+        """0-dim fp32: the pre-clip global gradient norm of the last guarded step."""
+        return self._clip.ctl[0] if self._clip is not None else None
+
+    @property
+    def clip_scale(self):
+        """0-dim fp32: the scale Adam applied; exactly 1.0 when nothing was
+        clipped, 0.0 on a skipped step."""
+        return self._clip.ctl[1] if self._clip is not None else None
+
+    @property
+    def skipped_steps(self):
+        """0-dim fp32: guarded steps skipped so far (non-finite norm)."""
+        return self._clip.ctl[3] if self._clip is not None else None
+
+    def _clip_state(self, grad):
+        """Partials buffer with one fixed slot range per layer range (the
+        same partition in every mode, so the norm's bits do not depend on
+        the mode) and the control block [norm, scale, skip, skip count]."""
+        st = self._clip
+        if st is None:
+            st = self._clip = _ClipState()
+            st.slots, off = {}, 0
+            for name, (a, b) in self._ranges.items():
+                k = ops.grad_sqnorm_nparts(b - a)
+                st.slots[name] = (off, off + k)
+                off += k
+            st.part = torch.zeros(max(1, off), device=grad.device)
+            st.nparts = off
+            st.ctl = torch.zeros(4, device=grad.device)
+        return st
 
     @property
     def t(self):
@@ -330,6 +405,12 @@ class Trainer:
             ops.adam(flat[sl], grad[sl], self.m[sl], self.v[sl], work[sl] if work is not None else None,
                      lr=g["lr"], b1=g["betas"][0], b2=g["betas"][1], eps=g["eps"], step=self.t)
         stepped = None
+        clip = self._clip_state(grad) if self._clip_norm is not None else None
+
+        def sqnorm(name):
+            a, b = self._ranges[name]
+            o, e = clip.slots[name]
+            ops.grad_sqnorm_part(grad[a:b], clip.part[o:e])
         if self.dp:
             if self._bucketer is None or self._bucketer.flat is not grad:
                 # persistent: the bf16 shadow is allocated once
@@ -337,6 +418,19 @@ class Trainer:
                                               wire_dtype=self.grad_wire_dtype)
             bucketer = self._bucketer
             hook = bucketer.reduce
+        elif clip is not None:
+            # the sum of squares of each layer range as soon as its gradients
+            # are final, on the stream that wrote them (Engine._hook: the
+            # weight-gradient stream is current and every gradient write of
+            # the range is queued on it; the embedding's hook runs on the main
+            # stream after the join).  No Adam before the norm is whole, so
+            # SMER_ADAM_OVERLAP does not apply.
+            stepped = set()
+
+            def hook(name):
+                if name in self._ranges:
+                    sqnorm(name)
+                    stepped.add(name)
         elif os.environ.get("SMER_ADAM_OVERLAP", "1") != "0":
             # Adam of each layer range as soon as its gradients are final: the
             # hook runs with the weight-gradient stream current, which first
@@ -355,7 +449,16 @@ class Trainer:
         eng.backward(ctx, dlog, hook=hook)
         if bucketer is not None:
             bucketer.finish()
-        if stepped is None:
+        if clip is not None:
+            # DP: the reduced gradient is the same on every rank, so is the
+            # norm and the skip decision -- no further collective
+            for name in self._ranges:
+                if stepped is None or name not in stepped:
+                    sqnorm(name)
+            ops.clip_scale(clip.part[:clip.nparts], self._clip_norm, clip.ctl)
+            ops.adam_guarded(flat, grad, self.m, self.v, work, clip.ctl, lr=g["lr"], b1=g["betas"][0],
+                             b2=g["betas"][1], eps=g["eps"], step=self.t)
+        elif stepped is None:
             adam()
         else:  # the ranges no hook stepped (the embedding), on the main stream
             for name, (a, b) in self._ranges.items():
