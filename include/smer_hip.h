@@ -98,6 +98,7 @@ typedef struct ihipStream_t* smer_stream_t; /* == hipStream_t */
 
 #define SMER_F32 0
 #define SMER_BF16 1
+#define SMER_F8 2 /* e4m3 operands: smer_gemm_plan only (smer_gemm: SMER_ERR_UNSUPPORTED) */
 
 int smer_abi_version(void);
 const char* smer_last_error(void);
@@ -166,18 +167,23 @@ int smer_gemm_wgrad_fp8(int M, int N, int K, const void* dy8, long lddy, const v
  * never stamp.  Used by tools/gemm256s_phases.py. */
 int smer_gemm_debug_stamps(void* buf, size_t bytes);
 
-/* Diagnostics: what smer_gemm (rowsum 0) or smer_gemm_wgrad_bias_ex
- * (SMER_PLAN_ROWSUM) would launch for a call, from the same decision the
- * launchers run, without launching.  facts: the SMER_PLAN_* bits that hold
+/* Diagnostics: what smer_gemm (rowsum 0), smer_gemm_wgrad_bias_ex
+ * (SMER_PLAN_ROWSUM) or, with dtype SMER_F8, smer_gemm_fp8 / _q / _ex / _gate8
+ * (a_kcontig = b_kcontig = 1) and smer_gemm_wgrad_fp8 (both 0) would launch
+ * for a call, from the same decision the launchers run, without launching.  facts: the SMER_PLAN_* bits that hold
  * for the call (an operand is passed, relu / dropout on, e.vec: every passed
  * epilogue operand 16-B aligned with a row stride % 8, Cf 16-B aligned, a
- * workspace passed; fp32: lda, ldb % 4 == 0 and A, B 16-B aligned).  cus: the
+ * workspace passed; fp32: lda, ldb % 4 == 0 and A, B 16-B aligned; e4m3:
+ * SMER_PLAN_GATE8, the gate is an e4m3 copy).  cus: the
  * CU count to plan for, 0 = the current device's; with cus > 0 no HIP call is
  * made.  plan receives SMER_GEMM_PLAN_INTS ints: kernel id, template flags
  * (bit 0 a_kcontig, 1 b_kcontig, 2 the skinny kernel's 4-step unroll), grid
  * x, grid y, dynamic LDS bytes, split-K slices, their K depth, and the
  * kernel id of the split-K reduction (-1: none).  smer_gemm_kernel_name:
- * the name of a kernel id, NULL past the last.  Used by the GEMM edge tests. */
+ * the name of a kernel id, NULL past the last; the e4m3 kernels are
+ * f8_generic, f8_stream, f8_q8_generic, f8_q8_stream, f8_q8_gate8 (the
+ * two-stage kernel by epilogue), f8_g256s (staggered) and f8_wgrad256s.
+ * Used by the GEMM edge tests. */
 #define SMER_PLAN_C 0x1
 #define SMER_PLAN_CF 0x2
 #define SMER_PLAN_BIAS 0x4
@@ -192,6 +198,7 @@ int smer_gemm_debug_stamps(void* buf, size_t bytes);
 #define SMER_PLAN_ROWSUM 0x800
 #define SMER_PLAN_WORKSPACE 0x1000
 #define SMER_PLAN_F32_ALIGNED 0x2000
+#define SMER_PLAN_GATE8 0x4000
 #define SMER_GEMM_PLAN_INTS 8
 int smer_gemm_plan(int dtype, int a_kcontig, int b_kcontig, int M, int N, int K, unsigned facts,
                    long ldcf, size_t ws_bytes, int max_workgroups, int cus, int* plan);

@@ -2188,6 +2188,8 @@ static GemmSwitches read_switches(GemmSwitches sw, bool per_call) {
       else if (is("SMER_WGRAD256S")) sw.wgrad256s = on();
       else if (is("SMER_SPLITK_FUSED")) sw.splitk_fused = v[0] == '1';
       else if (is("SMER_GEMM_F32_MFMA")) sw.f32_mfma = on();
+      else if (is("SMER_FP8_Q8_FAST")) sw.fp8_q8_fast = on();
+      else if (is("SMER_GEMM256S_FP8")) sw.gemm256s_fp8 = v[0] == '1';
     } else {
       if (is("SMER_GEMM_GLDS")) sw.gemm_glds = on();
       else if (is("SMER_WGRAD_GLDS")) sw.wgrad_glds = on();
@@ -2235,6 +2237,30 @@ static GemmQuery gemm_query(bool f32, bool ak, bool bk, int M, int N, int K, con
   q.cf_aligned16 = ((uintptr_t)e.Cf & 15) == 0;
   return q;
 }
+// the same of an e4m3 product: forward / dgrad (both operands K-contiguous)
+// or weight gradient (both tokens-major)
+static GemmQuery fp8_query(bool fwd, int M, int N, int K, const GemmEpi& e, bool gate8, const void* ws,
+                           size_t ws_bytes, int max_workgroups) {
+  GemmQuery q = gemm_query(false, fwd, fwd, M, N, K, e);
+  q.f8 = true;
+  q.gate8 = gate8;
+  q.ws = ws != nullptr;
+  q.ws_bytes = ws_bytes;
+  q.cus = smer_num_cus();
+  q.max_workgroups = max_workgroups;
+  return q;
+}
+
+// > 64 KiB of dynamic LDS must be opted into, once per kernel: at the
+// kernel's first launch
+#define LDS_ATTR(kern, bytes)                                                                   \
+  do {                                                                                          \
+    static bool set = false;                                                                    \
+    if (!set) {                                                                                 \
+      hipFuncSetAttribute((const void*)(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); \
+      set = true;                                                                               \
+    }                                                                                           \
+  } while (0)
 
 // Split-K tickets (fused last-arriver reduction): the LAST gp::TICKET_BYTES
 // of a split-K workspace hold one u32 per output tile.  They must be zero
@@ -2258,15 +2284,6 @@ static int launch_bf16(int M, int N, int K, const void* A, long lda, const void*
   float* slabs = (float*)ws;
   float* rs_part = p.rs_offset ? slabs + p.rs_offset : nullptr;
   float* rs_out = p.split > 1 ? rs_part : rowsum;
-  // > 64 KiB of dynamic LDS must be opted into, once per kernel
-#define LDS_ATTR(kern, bytes)                                                                   \
-  do {                                                                                          \
-    static bool set = false;                                                                    \
-    if (!set) {                                                                                 \
-      hipFuncSetAttribute((const void*)(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); \
-      set = true;                                                                               \
-    }                                                                                           \
-  } while (0)
 #define SKB(MI, KF)                                                                                         \
   do {                                                                                                      \
     if (p.unroll4)                                                                                          \
@@ -2325,7 +2342,6 @@ static int launch_bf16(int M, int N, int K, const void* A, long lda, const void*
       return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_gemm(bf16): the plan names no bf16 kernel");
   }
 #undef SKB
-#undef LDS_ATTR
   if (p.reduce == GK_SPLITK_REDUCE) {
     long n4 = ((long)M * N) / 4 + (rowsum ? M : 0);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, M, N, p.split,
@@ -2626,11 +2642,14 @@ extern "C" const char* smer_gemm_kernel_name(int kernel) { return gemm_kernel_na
 
 extern "C" int smer_gemm_plan(int dtype, int a_kcontig, int b_kcontig, int M, int N, int K, unsigned facts,
                               long ldcf, size_t ws_bytes, int max_workgroups, int cus, int* plan) {
-  SMER_REQUIRE(dtype == SMER_BF16 || dtype == SMER_F32, "smer_gemm_plan: dtype");
+  SMER_REQUIRE(dtype == SMER_BF16 || dtype == SMER_F32 || dtype == SMER_F8, "smer_gemm_plan: dtype");
   SMER_REQUIRE(M > 0 && N > 0 && K > 0 && cus >= 0 && plan, "smer_gemm_plan: sizes / null plan");
+  SMER_REQUIRE(dtype != SMER_F8 || !a_kcontig == !b_kcontig,
+               "smer_gemm_plan: e4m3 operands are both K-contiguous or both tokens-major");
   auto has = [&](unsigned f) { return (facts & f) != 0; };
   GemmQuery q;
-  q.f32 = dtype == SMER_F32; q.ak = a_kcontig; q.bk = b_kcontig; q.M = M; q.N = N; q.K = K;
+  q.f32 = dtype == SMER_F32; q.f8 = dtype == SMER_F8; q.gate8 = has(SMER_PLAN_GATE8);
+  q.ak = a_kcontig; q.bk = b_kcontig; q.M = M; q.N = N; q.K = K;
   q.C = has(SMER_PLAN_C); q.Cf = has(SMER_PLAN_CF); q.bias = has(SMER_PLAN_BIAS); q.relu = has(SMER_PLAN_RELU);
   q.drop = has(SMER_PLAN_DROP); q.residual = has(SMER_PLAN_RESIDUAL); q.gate = has(SMER_PLAN_GATE);
   q.vec = has(SMER_PLAN_VEC); q.kv = has(SMER_PLAN_KV); q.q8 = has(SMER_PLAN_Q8);
@@ -3031,22 +3050,12 @@ __global__ __launch_bounds__(64 * SKF_NW) void gemm_skinny_ln_f32_kernel(int M, 
   }
 }
 
-// up to 128 KiB of dynamic LDS (16 rows x 2048) for the LDS-row skinny kernels
-static void skinny_f32_lds_attr() {
-  static bool set = false;
-  if (!set) {
-    hipFuncSetAttribute((const void*)gemm_skinny_ln_f32_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        SKF_BM * 2048 * (int)sizeof(float));
-    hipFuncSetAttribute((const void*)gemm_skinny_ln_f32_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        SKF_BM * 2048 * (int)sizeof(float));
-    set = true;
-  }
-}
 // fp32 Linear of <= 64 rows, K <= 2048 (K % 4 == 0, 16-B aligned rows):
-// rows through LDS, all weight loads of the single round issued first
+// rows through LDS (up to 128 KiB of dynamic LDS, 16 rows x 2048, for the
+// LDS-row skinny kernels), all weight loads of the single round issued first
 static void launch_skinny_rows_f32(dim3 grid, size_t lds, int M, int N, int K, const float* A, long lda,
                                    const float* W, long ldw, const GemmEpi& e, hipStream_t s) {
-  skinny_f32_lds_attr();
+  LDS_ATTR(gemm_skinny_ln_f32_kernel<false>, SKF_BM * 2048 * (int)sizeof(float));
   hipLaunchKernelGGL(gemm_skinny_ln_f32_kernel<false>, grid, dim3(64 * SKF_NW), lds, s, M, N, K, A, lda,
                      (const float*)nullptr, (const float*)nullptr, 0.f, (float*)nullptr, 0L, W, ldw, e);
 }
@@ -3194,7 +3203,7 @@ extern "C" int smer_linear_decode_ln_f32(int M, int N, int K, const void* Y, lon
                                kv_req, kv_pos, kv_col0);
   const dim3 grid((N + SKF_BN - 1) / SKF_BN, (M + SKF_BM - 1) / SKF_BM);
   const size_t lds = (size_t)std::min(M, SKF_BM) * K * sizeof(float);
-  skinny_f32_lds_attr();
+  LDS_ATTR(gemm_skinny_ln_f32_kernel<true>, SKF_BM * 2048 * (int)sizeof(float));
   hipLaunchKernelGGL(gemm_skinny_ln_f32_kernel<true>, grid, dim3(64 * SKF_NW), lds, (hipStream_t)stream, M, N, K,
                      (const float*)Y, ldy, gamma, beta, eps, (float*)X, ldx, (const float*)W, ldw, e);
   SMER_CHECK_LAUNCH("smer_linear_decode_ln_f32");
@@ -3212,12 +3221,7 @@ extern "C" int smer_linear_decode_merge_f32(int M, int N, int K, const float* pa
   const GemmEpi e = decode_epi(bias, relu, residual, ldr, C, ldc, Cf, ldcf, nullptr, 0, 0, nullptr, nullptr, 0);
   const dim3 grid((N + SKF_BN - 1) / SKF_BN, (M + SKF_BM - 1) / SKF_BM);
   const size_t lds = (size_t)std::min(M, SKF_BM) * K * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)gemm_skinny_merge_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        SKF_BM * 2048 * (int)sizeof(float));
-    attr_set = true;
-  }
+  LDS_ATTR(gemm_skinny_merge_f32_kernel, SKF_BM * 2048 * (int)sizeof(float));
   hipLaunchKernelGGL(gemm_skinny_merge_f32_kernel, grid, dim3(64 * SKF_NW), lds, (hipStream_t)stream, M, N, K, part,
                      (const float*)W, ldw, e);
   SMER_CHECK_LAUNCH("smer_linear_decode_merge_f32");
@@ -4217,96 +4221,30 @@ extern "C" int smer_gemm_wgrad_fp8(int M, int N, int K, const void* dy8, long ld
   GemmEpi e{};
   e.alpha = 1.f; e.drop_scale = 1.f;
   e.Cf = dW; e.ldcf = lddw; e.accumulate = accumulate; e.vec = 1; e.rs_accumulate = db_accumulate;
-  const GemmSwitches& sw = gemm_switches_once();
-  const long t2 = (long)(M / G2) * (N / G2);
+  // the weight gradient reads no per-call switch
+  const GemmPlan p = gemm_plan(fp8_query(false, M, N, K, e, false, workspace, ws_bytes, max_workgroups),
+                               gemm_switches_once());
+  // split-K: alpha-scaled slabs, then N / 256 x M bias partials per slice
   const int nbn = N / G2;
-  const long cus = smer_num_cus();
   const size_t slab_bytes = workspace && ws_bytes > gp::TICKET_BYTES ? ws_bytes - gp::TICKET_BYTES : 0;
-  long ns = std::min<long>(gp::cap(max_workgroups, sw.wgrad256_slots ? sw.wgrad256_slots : cus) / t2, K / sw.wgrad256_depth);
-  // per slice: an M x N slab and nbn x M bias partials
-  ns = std::min<long>(ns, (long)(slab_bytes / (((size_t)M * N + (size_t)nbn * M) * sizeof(float))));
-  ns = std::max<long>(1, std::min<long>(ns, 64));
-  const int KS = 2 * GS_KS;
-  const int kchunk = (int)(((K + ns - 1) / ns + KS - 1) / KS * KS);
-  const int split = (K + kchunk - 1) / kchunk;
-  const long nwg = t2 * split;
-  const long gcap = gp::cap(max_workgroups, cus);
-  const int grid = nwg > gcap ? (int)(gcap & ~7L) : (int)nwg;
-  static bool attr = false;
-  if (!attr) {
-    hipFuncSetAttribute((const void*)gemm256s_wgrad_fp8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        4 * GS_SLOT);
-    attr = true;
-  }
-  // split-K: alpha-scaled slabs, then the bias partials
-  const size_t slab_floats = split > 1 ? (size_t)split * M * N : 0;
-  float* rs_part = db ? (float*)workspace + slab_floats : nullptr;
-  if (db && (slab_floats + (size_t)split * nbn * M) * sizeof(float) > slab_bytes)  // db: workspace non-null
+  float* rs_part = db ? (float*)workspace + p.rs_offset : nullptr;
+  if (db && (p.rs_offset + (size_t)p.split * nbn * M) * sizeof(float) > slab_bytes)  // db: workspace non-null
     return smer_set_error(SMER_ERR_INVALID, "smer_gemm_wgrad_fp8: workspace too small for the bias partials");
-  hipLaunchKernelGGL(gemm256s_wgrad_fp8_kernel, dim3(grid), dim3(512), 4 * GS_SLOT, s, M, N, K,
-                     (const uint8_t*)dy8, lddy, (const uint8_t*)x8, ldx, dy_inv, x_inv, e, split, kchunk,
+  LDS_ATTR(gemm256s_wgrad_fp8_kernel, 4 * GS_SLOT);
+  hipLaunchKernelGGL(gemm256s_wgrad_fp8_kernel, dim3(p.grid_x), dim3(p.block), p.lds, s, M, N, K,
+                     (const uint8_t*)dy8, lddy, (const uint8_t*)x8, ldx, dy_inv, x_inv, e, p.split, p.kchunk,
                      (float*)workspace, rs_part);
-  if (split > 1) {
+  if (p.reduce == GK_SPLITK_REDUCE) {
     const long n4 = ((long)M * N) / 4;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, M, N, split,
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, M, N, p.split,
                        (const float*)workspace, 1.f, dW, lddw, accumulate, (const float*)nullptr, (float*)nullptr,
                        0);
   }
   if (db)
-    hipLaunchKernelGGL(wgrad_rowsum_reduce_kernel, dim3((M + 63) / 64), dim3(64), 0, s, M, split * nbn,
+    hipLaunchKernelGGL(wgrad_rowsum_reduce_kernel, dim3((M + 63) / 64), dim3(64), 0, s, M, p.split * nbn,
                        (const float*)rs_part, db, db_accumulate);
   SMER_CHECK_LAUNCH("smer_gemm_wgrad_fp8");
   return SMER_OK;
-}
-
-
-extern "C" int smer_gemm_fp8_q(int M, int N, int K, const void* A, long lda, const void* B, long ldb,
-                               const float* a_inv, const float* b_inv, const float* bias, int relu,
-                               const void* residual, long ldr, float drop_p, uint32_t drop_seed,
-                               void* C, long ldc, void* q8, long ldq8, const float* q8_scale,
-                               unsigned* q8_amax, smer_stream_t stream);
-
-// The staggered fp8 kernel for whole-tile bf16-output products: opt-in
-// (SMER_GEMM256S_FP8=1 / 0 forces it on / off, read per call).  Isolated
-// and warm (tools/gemm256s_fp8_ab.py, C4 rows 65536, operands re-used across
-// iterations) it wins at K >= 1024 (FFN2 forward 122.3 vs 133.1 us, FFN1 /
-// QKV dgrads 113.8 / 125.1 vs 123.0 / 131.7) and loses at K = 768 (QKV
-// forward 160.7 vs 151.7); inside the C4 fp8 train step, whose operands
-// arrive cold from HBM, the same K >= 1024 calls ran slower (paired
-// kernel trace: 133.5 vs 129.3 us at the 130-us shapes, 794 vs 698 at the
-// vocabulary-long K) and the step did not move (86.3 vs 85.9 ms), so the
-// two-stage kernel stays the default.
-// The e4m3-copy products (the gated FFN2 dgrad, FFN1 with SMER_FP8_FFN2)
-// on the streamed epilogue, whose residual / gate rows arrive by LDS-DMA a
-// pass ahead, one item at a time (round 6: C4 gated dgrad 65536 x 2048 x
-// 768 301 -> 245 us, step 78.96-78.99 -> 78.48-78.57 ms); SMER_FP8_Q8_FAST=0
-// (read per call) keeps the generic epilogue, whose gate loads are a
-// dependent HBM round trip per pass
-static bool smer_fp8_q8_fast() {
-  const char* e = getenv("SMER_FP8_Q8_FAST");
-  return !(e && e[0] == '0');
-}
-static bool smer_gemm256s_fp8_enabled(int K) {
-  (void)K;
-  const char* e = getenv("SMER_GEMM256S_FP8");
-  return e && e[0] == '1';
-}
-
-extern "C" int smer_gemm_fp8(int M, int N, int K, const void* A, long lda, const void* B, long ldb,
-                             const float* a_inv, const float* b_inv, const float* bias, int relu,
-                             const void* residual, long ldr, float drop_p, uint32_t drop_seed,
-                             void* C, long ldc, smer_stream_t stream) {
-  return smer_gemm_fp8_q(M, N, K, A, lda, B, ldb, a_inv, b_inv, bias, relu, residual, ldr, drop_p,
-                         drop_seed, C, ldc, nullptr, 0, nullptr, nullptr, stream);
-}
-
-extern "C" int smer_gemm_fp8_q(int M, int N, int K, const void* A, long lda, const void* B, long ldb,
-                               const float* a_inv, const float* b_inv, const float* bias, int relu,
-                               const void* residual, long ldr, float drop_p, uint32_t drop_seed,
-                               void* C, long ldc, void* q8, long ldq8, const float* q8_scale,
-                               unsigned* q8_amax, smer_stream_t stream) {
-  return smer_gemm_fp8_ex(M, N, K, A, lda, B, ldb, a_inv, b_inv, bias, relu, residual, ldr, nullptr, 0, 1.f,
-                          drop_p, drop_seed, C, ldc, q8, ldq8, q8_scale, q8_amax, stream);
 }
 
 static int gemm_fp8_impl(int M, int N, int K, const void* A, long lda, const void* B, long ldb,
@@ -4317,11 +4255,12 @@ static int gemm_fp8_impl(int M, int N, int K, const void* A, long lda, const voi
                          smer_stream_t stream) {
   if (M <= 0 || N <= 0 || K <= 0 || M % G2 || N % G2 || K % F8K)
     return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_gemm_fp8: needs M, N % 256 == 0 and K % 128 == 0");
+  const GemmSwitches sw = gemm_switches();
   // (C may be null only beside an e4m3 copy on the streamed epilogue: the
   // copy alone is written)
-  const bool c_less = !C && q8 && smer_fp8_q8_fast();
+  const bool c_less = !C && q8 && sw.fp8_q8_fast;
   SMER_REQUIRE(A && B && (C || c_less) && a_inv && b_inv, "smer_gemm_fp8: null pointer");
-  SMER_REQUIRE(!gate_u8 || (gate && q8 && smer_fp8_q8_fast() && ((uintptr_t)gate & 15) == 0 && ldg % 16 == 0),
+  SMER_REQUIRE(!gate_u8 || (gate && q8 && sw.fp8_q8_fast && ((uintptr_t)gate & 15) == 0 && ldg % 16 == 0),
                "smer_gemm_fp8_gate8: e4m3 gate needs the streamed e4m3-copy epilogue and 16-B aligned rows");
   SMER_REQUIRE(lda % 16 == 0 && ldb % 16 == 0 && aligned16(A) && aligned16(B),
                "smer_gemm_fp8: operand strides / alignment");
@@ -4341,57 +4280,25 @@ static int gemm_fp8_impl(int M, int N, int K, const void* A, long lda, const voi
                  "smer_gemm_fp8_q: fp8 output needs aligned vectors, scale and amax");
     e.q8 = (uint8_t*)q8; e.ldq8 = ldq8; e.q8_scale = q8_scale; e.q8_amax = q8_amax;
   }
+  const GemmPlan p = gemm_plan(fp8_query(true, M, N, K, e, gate_u8 != 0, nullptr, 0, 0), sw);
+  const uint8_t *a = (const uint8_t*)A, *b = (const uint8_t*)B;
   hipStream_t s = (hipStream_t)stream;
-  const long tiles = (long)(M / G2) * (N / G2);
-  const int grid = tiles > smer_num_cus() ? (smer_num_cus() & ~7) : (int)tiles;
-  if (e.vec && !q8 && K % (2 * GS_KS) == 0 && K / (2 * GS_KS) >= 4 && smer_gemm256s_fp8_enabled(K)) {
-    static bool attr_s = false;
-    if (!attr_s) {
-      hipFuncSetAttribute((const void*)gemm256s_fp8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS);
-      attr_s = true;
-    }
-    hipLaunchKernelGGL(gemm256s_fp8_kernel, dim3(grid), dim3(512), G2_LDS, s, M, N, K, (const uint8_t*)A, lda,
-                       (const uint8_t*)B, ldb, a_inv, b_inv, e);
-    SMER_CHECK_LAUNCH("smer_gemm_fp8");
-    return SMER_OK;
+#define F8(kern)                                                                                          \
+  do {                                                                                                    \
+    LDS_ATTR((kern), (int)p.lds);                                                                         \
+    hipLaunchKernelGGL((kern), dim3(p.grid_x), dim3(p.block), p.lds, s, M, N, K, a, lda, b, ldb, a_inv, b_inv, e); \
+  } while (0)
+  switch (p.kernel) {
+    case GK_F8_G256S: F8(gemm256s_fp8_kernel); break;
+    case GK_F8_GENERIC: F8((gemm256_fp8_kernel<false, false>)); break;
+    case GK_F8_STREAM: F8((gemm256_fp8_kernel<true, false>)); break;
+    case GK_F8_Q8_GENERIC: F8((gemm256_fp8_kernel<false, true>)); break;
+    case GK_F8_Q8_STREAM: F8((gemm256_fp8_kernel<true, true>)); break;
+    case GK_F8_Q8_GATE8: F8((gemm256_fp8_kernel<true, true, true>)); break;
+    default:
+      return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_gemm_fp8: the plan names no fp8 kernel");
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)gemm256_fp8_kernel<false, false>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 2 * G2_STAGE);
-    hipFuncSetAttribute((const void*)gemm256_fp8_kernel<true, false>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS);
-    hipFuncSetAttribute((const void*)gemm256_fp8_kernel<false, true>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 2 * G2_STAGE);
-    attr_set = true;
-  }
-  if (!e.vec)  // (q8 requires e.vec)
-    hipLaunchKernelGGL((gemm256_fp8_kernel<false, false>), dim3(grid), dim3(512), 2 * G2_STAGE, s, M, N,
-                       K, (const uint8_t*)A, lda, (const uint8_t*)B, ldb, a_inv, b_inv, e);
-  else if (gate_u8) {
-    static bool attr_g8 = false;
-    if (!attr_g8) {
-      hipFuncSetAttribute((const void*)gemm256_fp8_kernel<true, true, true>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS);
-      attr_g8 = true;
-    }
-    hipLaunchKernelGGL((gemm256_fp8_kernel<true, true, true>), dim3(grid), dim3(512), G2_LDS, s, M, N, K,
-                       (const uint8_t*)A, lda, (const uint8_t*)B, ldb, a_inv, b_inv, e);
-  } else if (q8 && smer_fp8_q8_fast()) {
-    static bool attr_q = false;
-    if (!attr_q) {
-      hipFuncSetAttribute((const void*)gemm256_fp8_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          G2_LDS);
-      attr_q = true;
-    }
-    hipLaunchKernelGGL((gemm256_fp8_kernel<true, true>), dim3(grid), dim3(512), G2_LDS, s, M, N, K,
-                       (const uint8_t*)A, lda, (const uint8_t*)B, ldb, a_inv, b_inv, e);
-  } else if (q8)
-    hipLaunchKernelGGL((gemm256_fp8_kernel<false, true>), dim3(grid), dim3(512), 2 * G2_STAGE, s, M, N, K,
-                       (const uint8_t*)A, lda, (const uint8_t*)B, ldb, a_inv, b_inv, e);
-  else
-    hipLaunchKernelGGL((gemm256_fp8_kernel<true, false>), dim3(grid), dim3(512), G2_LDS, s, M, N, K,
-                       (const uint8_t*)A, lda, (const uint8_t*)B, ldb, a_inv, b_inv, e);
+#undef F8
   SMER_CHECK_LAUNCH("smer_gemm_fp8");
   return SMER_OK;
 }
@@ -4404,6 +4311,23 @@ extern "C" int smer_gemm_fp8_ex(int M, int N, int K, const void* A, long lda, co
                                 smer_stream_t stream) {
   return gemm_fp8_impl(M, N, K, A, lda, B, ldb, a_inv, b_inv, bias, relu, residual, ldr, gate, ldg, 0,
                        gate_scale, drop_p, drop_seed, C, ldc, q8, ldq8, q8_scale, q8_amax, stream);
+}
+
+extern "C" int smer_gemm_fp8_q(int M, int N, int K, const void* A, long lda, const void* B, long ldb,
+                               const float* a_inv, const float* b_inv, const float* bias, int relu,
+                               const void* residual, long ldr, float drop_p, uint32_t drop_seed,
+                               void* C, long ldc, void* q8, long ldq8, const float* q8_scale,
+                               unsigned* q8_amax, smer_stream_t stream) {
+  return smer_gemm_fp8_ex(M, N, K, A, lda, B, ldb, a_inv, b_inv, bias, relu, residual, ldr, nullptr, 0, 1.f,
+                          drop_p, drop_seed, C, ldc, q8, ldq8, q8_scale, q8_amax, stream);
+}
+
+extern "C" int smer_gemm_fp8(int M, int N, int K, const void* A, long lda, const void* B, long ldb,
+                             const float* a_inv, const float* b_inv, const float* bias, int relu,
+                             const void* residual, long ldr, float drop_p, uint32_t drop_seed,
+                             void* C, long ldc, smer_stream_t stream) {
+  return smer_gemm_fp8_q(M, N, K, A, lda, B, ldb, a_inv, b_inv, bias, relu, residual, ldr, drop_p,
+                         drop_seed, C, ldc, nullptr, 0, nullptr, nullptr, stream);
 }
 
 // The gated FFN2 dgrad of the fp8 step with FFN1's e4m3 copy as the ReLU /

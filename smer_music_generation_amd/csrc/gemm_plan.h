@@ -1,6 +1,6 @@
 // The GEMM dispatch of gemm.hip as a pure function: which kernel a smer_gemm /
-// smer_gemm_wgrad_bias_ex call runs on, with which grid, LDS size and split-K
-// slices.  Plain C++17, no HIP and no environment: the launchers fill a
+// smer_gemm_wgrad_bias_ex / smer_gemm_fp8* / smer_gemm_wgrad_fp8 call runs on,
+// with which grid, LDS size and split-K slices.  Plain C++17, no HIP and no environment: the launchers fill a
 // GemmQuery, read the switches once per call (gemm_switches, gemm.hip) and
 // launch what gemm_plan returns; smer_gemm_plan answers the same question
 // without launching (tests/gemmref.py's mirror is held against it).
@@ -45,6 +45,8 @@ struct GemmSwitches {
   bool wgrad256s = true;     // SMER_WGRAD256S=0: the two-stage 256x256 weight gradient
   bool splitk_fused = false; // SMER_SPLITK_FUSED=1: last-arriver reduction
   bool f32_mfma = true;      // SMER_GEMM_F32_MFMA=0: fp32 NT shapes on the VALU tile kernel
+  bool fp8_q8_fast = true;   // SMER_FP8_Q8_FAST=0: e4m3-copy fp8 products on the generic epilogue
+  bool gemm256s_fp8 = false; // SMER_GEMM256S_FP8=1: the staggered fp8 kernel
   // once per process
   bool gemm_glds = true;     // SMER_GEMM_GLDS=0: register staging everywhere
   // SMER_WGRAD_GLDS=0: register staging for the 128x128 weight gradients
@@ -76,11 +78,13 @@ struct GemmSwitches {
 
 struct GemmQuery {
   bool f32 = false;  // else bf16
+  bool f8 = false;   // e4m3 operands (smer_gemm_fp8*, smer_gemm_wgrad_fp8); excludes f32
   bool ak = true, bk = true;
   int M = 0, N = 0, K = 0;
   // what the dispatch reads of the epilogue (GemmEpi)
   bool C = false, Cf = false, bias = false, relu = false, drop = false, residual = false, gate = false;
   bool vec = false, kv = false, q8 = false;
+  bool gate8 = false;        // fp8: the gate is an e4m3 copy (smer_gemm_fp8_gate8)
   long ldcf = 0;
   bool cf_aligned16 = false;
   bool rowsum = false;       // the fused bias gradient (smer_gemm_wgrad_bias_ex)
@@ -96,6 +100,8 @@ enum GemmKernel {
   GK_SKINNY_M16_KF, GK_SKINNY_M16_GUARD, GK_SKINNY_S64_KF, GK_SKINNY_S64_GUARD, GK_GEMM64,
   GK_G128_GLDS, GK_G128_REG, GK_G256_STREAM, GK_G256_GENERIC, GK_G256S, GK_SPLITK_REDUCE,
   GK_SPLITK_FUSED, GK_WGRAD256, GK_WGRAD256S, GK_F32_ROWS, GK_F32_SKINNY, GK_F32_MFMA, GK_F32_TILE,
+  // gemm256_fp8_kernel<STREAM, Q8, GATE8>, gemm256s_fp8_kernel, gemm256s_wgrad_fp8_kernel
+  GK_F8_GENERIC, GK_F8_STREAM, GK_F8_Q8_GENERIC, GK_F8_Q8_STREAM, GK_F8_Q8_GATE8, GK_F8_G256S, GK_F8_WGRAD256S,
   GK_COUNT
 };
 constexpr int GK_NONE = -1;
@@ -104,7 +110,8 @@ inline const char* gemm_kernel_name(int k) {
   static const char* const names[GK_COUNT] = {
       "skinny_m16_kf", "skinny_m16_guard", "skinny_s64_kf", "skinny_s64_guard", "gemm64",
       "g128_glds", "g128_reg", "g256_stream", "g256_generic", "g256s", "splitk_reduce",
-      "splitk_fused", "wgrad256", "wgrad256s", "f32_rows", "f32_skinny", "f32_mfma", "f32_tile"};
+      "splitk_fused", "wgrad256", "wgrad256s", "f32_rows", "f32_skinny", "f32_mfma", "f32_tile",
+      "f8_generic", "f8_stream", "f8_q8_generic", "f8_q8_stream", "f8_q8_gate8", "f8_g256s", "f8_wgrad256s"};
   return k >= 0 && k < GK_COUNT ? names[k] : nullptr;
 }
 
@@ -116,7 +123,7 @@ struct GemmPlan {
   size_t lds = 0;             // dynamic LDS bytes
   int split = 1, kchunk = 0;  // split-K slices and their K depth (kchunk = K unsplit)
   int reduce = GK_NONE;       // GK_SPLITK_REDUCE (separate kernel), GK_SPLITK_FUSED (tickets) or none
-  size_t rs_offset = 0;       // row-sum partials in the workspace, in floats (split > 1 with rowsum)
+  size_t rs_offset = 0;       // row-sum partials in the workspace, in floats (split > 1 with rowsum; fp8: split > 1)
 };
 
 namespace gp {
@@ -129,14 +136,15 @@ inline long cap(int max_workgroups, long v) {
 
 // Deterministic split-K of a weight gradient: `slots` work items over
 // `tiles` output tiles, slices at least `depth` deep and whole multiples of
-// `granule`, slabs of M * N floats plus M floats of row-sum partials per
-// slice within the workspace (its tickets excluded), at most 64 slices.
+// `granule`, slabs of M * N floats plus `rs_rows` x M floats of row-sum
+// partials per slice within the workspace (its tickets excluded), at most 64
+// slices.
 struct SplitK { long slices; int split, kchunk; };
-inline SplitK splitk(const GemmQuery& q, long slots, long tiles, int depth, int granule) {
+inline SplitK splitk(const GemmQuery& q, long slots, long tiles, int depth, int granule, int rs_rows) {
   const size_t ws_bytes = q.ws ? q.ws_bytes : 0;
   const size_t slab_bytes = ws_bytes > TICKET_BYTES ? ws_bytes - TICKET_BYTES : 0;
   long s = std::min<long>(slots / std::max<long>(1, tiles), q.K / depth);
-  s = std::min<long>(s, (long)(slab_bytes / (((size_t)q.M * q.N + q.M) * sizeof(float))));
+  s = std::min<long>(s, (long)(slab_bytes / (((size_t)q.M * q.N + (size_t)rs_rows * q.M) * sizeof(float))));
   s = std::max<long>(1, std::min<long>(s, 64));
   SplitK r{s, 1, q.K};
   if (s > 1) {
@@ -176,11 +184,65 @@ inline GemmPlan plan_f32(const GemmQuery& q, const GemmSwitches& sw) {
   p.kernel = al && sw.f32_mfma ? GK_F32_MFMA : GK_F32_TILE;
   return p;
 }
+
+// e4m3 operands (the launchers refuse anything but M, N % 256 == 0 and
+// K % 128 == 0 forward / K % 64 == 0 weight gradient before they ask): whole
+// 256x256 tiles, a persistent grid past one tile per CU.
+inline GemmPlan plan_f8(const GemmQuery& q, const GemmSwitches& sw) {
+  GemmPlan p;
+  p.ak = q.ak; p.bk = q.bk; p.kchunk = q.K;
+  p.block = 512;
+  const long cus = q.cus, tiles = (long)(q.M / G2) * (q.N / G2);
+  if (!q.ak && !q.bk) {
+    // weight gradient: the split-K of the bf16 GK_WGRAD256S branch, a slice
+    // carrying N / 256 x M bias partials (one row per column tile) whether
+    // or not the bias gradient is asked for
+    const long slots = cap(q.max_workgroups, sw.wgrad256_slots ? sw.wgrad256_slots : cus);
+    const SplitK sk = splitk(q, slots, tiles, sw.wgrad256_depth, G2K, q.N / G2);
+    p.kernel = GK_F8_WGRAD256S;
+    p.lds = 4 * GS_SLOT;
+    p.split = sk.split;
+    p.kchunk = sk.kchunk;
+    if (sk.split > 1) {
+      p.reduce = GK_SPLITK_REDUCE;
+      p.rs_offset = (size_t)sk.split * q.M * q.N;
+    }
+    const long nwg = tiles * sk.split, gcap = cap(q.max_workgroups, cus);
+    p.grid_x = nwg > gcap ? (int)(gcap & ~7L) : (int)nwg;
+    return p;
+  }
+  p.grid_x = tiles > cus ? (int)(cus & ~7L) : (int)tiles;
+  // The staggered fp8 kernel for whole-tile bf16-output products: opt-in
+  // (SMER_GEMM256S_FP8=1 / 0 forces it on / off, read per call).  Isolated
+  // and warm (tools/gemm256s_fp8_ab.py, C4 rows 65536, operands re-used across
+  // iterations) it wins at K >= 1024 (FFN2 forward 122.3 vs 133.1 us, FFN1 /
+  // QKV dgrads 113.8 / 125.1 vs 123.0 / 131.7) and loses at K = 768 (QKV
+  // forward 160.7 vs 151.7); inside the C4 fp8 train step, whose operands
+  // arrive cold from HBM, the same K >= 1024 calls ran slower (paired
+  // kernel trace: 133.5 vs 129.3 us at the 130-us shapes, 794 vs 698 at the
+  // vocabulary-long K) and the step did not move (86.3 vs 85.9 ms), so the
+  // two-stage kernel stays the default.
+  // The e4m3-copy products (the gated FFN2 dgrad, FFN1 with SMER_FP8_FFN2)
+  // on the streamed epilogue, whose residual / gate rows arrive by LDS-DMA a
+  // pass ahead, one item at a time (round 6: C4 gated dgrad 65536 x 2048 x
+  // 768 301 -> 245 us, step 78.96-78.99 -> 78.48-78.57 ms); SMER_FP8_Q8_FAST=0
+  // (read per call) keeps the generic epilogue, whose gate loads are a
+  // dependent HBM round trip per pass
+  if (q.vec && !q.q8 && q.K % G2K == 0 && q.K / G2K >= 4 && sw.gemm256s_fp8) p.kernel = GK_F8_G256S;
+  else if (!q.vec) p.kernel = GK_F8_GENERIC;  // (q8 and gate8 require vec)
+  else if (q.gate8) p.kernel = GK_F8_Q8_GATE8;
+  else if (q.q8) p.kernel = sw.fp8_q8_fast ? GK_F8_Q8_STREAM : GK_F8_Q8_GENERIC;
+  else p.kernel = GK_F8_STREAM;
+  // the generic epilogues need no epilogue rows in LDS
+  p.lds = p.kernel == GK_F8_GENERIC || p.kernel == GK_F8_Q8_GENERIC ? 2 * G2_STAGE : G2_LDS;
+  return p;
+}
 }  // namespace gp
 
 inline GemmPlan gemm_plan(const GemmQuery& q, const GemmSwitches& sw) {
   using namespace gp;
   if (q.f32) return plan_f32(q, sw);
+  if (q.f8) return plan_f8(q, sw);
   const int M = q.M, N = q.N, K = q.K;
   const long cus = q.cus;
   GemmPlan p;
@@ -234,7 +296,7 @@ inline GemmPlan gemm_plan(const GemmQuery& q, const GemmSwitches& sw) {
                    (sw.wgrad256 == 2 && ((long)M * N >= 1536L * 768 || (M >= 768 && N >= 768)));
   if (!q.ak && !q.bk && K % G2K == 0 && q.ws && big) {
     const long slots = cap(q.max_workgroups, sw.wgrad256_slots ? sw.wgrad256_slots : cus);
-    const SplitK sk = splitk(q, slots, t2, sw.wgrad256_depth, G2K);
+    const SplitK sk = splitk(q, slots, t2, sw.wgrad256_depth, G2K, 1);
     if (cf_only && t2 * sk.slices * 4 >= 3 * cus) {
       const bool stag = sw.wgrad256s && whole2 && q.vec;
       p.kernel = stag ? GK_WGRAD256S : GK_WGRAD256;
@@ -253,7 +315,7 @@ inline GemmPlan gemm_plan(const GemmQuery& q, const GemmSwitches& sw) {
   const int tiles = (int)(cdiv(M, BM) * cdiv(N, BN));
   const long resident = cap(q.max_workgroups, std::max(8L, sw.wgrad_wgp2 * cus / 2));
   SplitK sk{1, 1, K};
-  if (cf_only && tiles < 512 && K >= 1024) sk = splitk(q, resident, tiles, sw.splitk_depth, BK);
+  if (cf_only && tiles < 512 && K >= 1024) sk = splitk(q, resident, tiles, sw.splitk_depth, BK, 1);
   // mid-size forward / dgrad: fewer 128x128 tiles than two per CU -> 64x128
   if (q.ak && !q.rowsum && sk.split == 1 && K % BK == 0 && tiles <= 4 * cus && M > 4 * SK_BM &&
       sw.gemm_glds && sw.gemm64) {

@@ -7,6 +7,8 @@ tensor is rejected, a missing library raises at first use.
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from ._lib import call, load
@@ -78,26 +80,48 @@ class KernelTimer:
 GEMM_TIMER = None  # set to a KernelTimer to instrument smer_gemm launches
 
 
+class _Timed:
+    """HIP events around the launches of a `with` body, appended to a
+    KernelTimer as (start, end, flops, tag); `tag` may be a callable, so
+    that nothing is formatted when no timer is set."""
+
+    def __init__(self, timer, flops, tag):
+        self.timer, self.flops, self.tag = timer, flops, tag
+        self.ev0 = torch.cuda.Event(enable_timing=True)
+        self.ev1 = torch.cuda.Event(enable_timing=True)
+
+    def __enter__(self):
+        self.ev0.record()
+
+    def __exit__(self, *exc):
+        self.ev1.record()
+        tag = self.tag
+        self.timer.records.append((self.ev0, self.ev1, self.flops, tag() if callable(tag) else tag))
+
+
+_UNTIMED = contextlib.nullcontext()
+
+
+def _timed(flops, tag):
+    timer = GEMM_TIMER
+    return _UNTIMED if timer is None else _Timed(timer, flops, tag)
+
+
 def gemm(A, B, *, M, N, K, a_kcontig=True, b_kcontig=True, out=None, out_f32=None,
          accumulate=False, bias=None, alpha=1.0, relu=False, residual=None, gate=None,
          gate_scale=1.0, drop_p=0.0, seed=0, dtype=None):
     """out (+)= epilogue(alpha * op(A) op(B)^T); see include/smer_hip.h."""
     dt = dtype_code(dtype if dtype is not None else A.dtype)
-    timer = GEMM_TIMER
-    if timer is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    _gemm_call(dt, A, B, M, N, K, a_kcontig, b_kcontig, out, out_f32, accumulate, bias, alpha,
-               relu, residual, gate, gate_scale, drop_p, seed)
-    if timer is not None:
-        ev1.record()
+
+    def tag():
         epi = "".join(c for c, on in (("b", bias is not None), ("r", relu), ("d", drop_p > 0),
                                       ("R", residual is not None), ("g", gate is not None),
                                       ("f", out_f32 is not None), ("+", accumulate)) if on)
-        tag = "%s%s M%d N%d K%d %s" % ("n" if a_kcontig else "t", "t" if b_kcontig else "n",
-                                        M, N, K, epi)
-        timer.records.append((ev0, ev1, 2.0 * M * N * K, tag))
+        return "%s%s M%d N%d K%d %s" % ("n" if a_kcontig else "t", "t" if b_kcontig else "n", M, N, K, epi)
+
+    with _timed(2.0 * M * N * K, tag):
+        _gemm_call(dt, A, B, M, N, K, a_kcontig, b_kcontig, out, out_f32, accumulate, bias, alpha,
+                   relu, residual, gate, gate_scale, drop_p, seed)
 
 
 class CkLog:
@@ -214,18 +238,10 @@ def linear_wgrad(dy, x, dw, *, M=None, accumulate=True, db=None, ws=None, max_wg
     if db is not None and dy.dtype == torch.bfloat16:
         if ws is None:
             ws = splitk_workspace(dy.device)
-        timer = GEMM_TIMER
-        if timer is not None:
-            ev0 = torch.cuda.Event(enable_timing=True)
-            ev1 = torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        call("smer_gemm_wgrad_bias_ex", BF16, Mo, x.shape[1], T, _p(dy), _ld(dy), _p(x), _ld(x),
-             _p(dw), _ld(dw), int(accumulate), _p(db), int(accumulate), _p(ws), ws.numel(),
-             int(max_wg), _stream())
-        if timer is not None:
-            ev1.record()
-            timer.records.append((ev0, ev1, 2.0 * Mo * x.shape[1] * T,
-                                  "wgrad+bias M%d N%d K%d" % (Mo, x.shape[1], T)))
+        with _timed(2.0 * Mo * x.shape[1] * T, lambda: "wgrad+bias M%d N%d K%d" % (Mo, x.shape[1], T)):
+            call("smer_gemm_wgrad_bias_ex", BF16, Mo, x.shape[1], T, _p(dy), _ld(dy), _p(x), _ld(x),
+                 _p(dw), _ld(dw), int(accumulate), _p(db), int(accumulate), _p(ws), ws.numel(),
+                 int(max_wg), _stream())
         return
     gemm(dy, x, M=Mo, N=x.shape[1], K=T, a_kcontig=False, b_kcontig=False, out_f32=dw,
          accumulate=accumulate, dtype=dy.dtype)
@@ -485,6 +501,24 @@ def fp8_quantize_segments_t(seg, amax_ws, inv, blocks_per_seg=64):
          _stream())
 
 
+def _gemm_fp8(a8, a_inv, b8, b_inv, out, tag, *, bias=None, relu=False, residual=None, gate=None,
+              gate_scale=1.0, drop_p=0.0, seed=0, q8=None, qs=None, amax=None):
+    """The fp8 forward / dgrad wrappers below on smer_gemm_fp8_ex (the entry
+    smer_gemm_fp8 and smer_gemm_fp8_q forward to); `tag`: the timer's label
+    of the product, given "M%d N%d K%d" of its shape."""
+    M, K = a8.shape
+    N = b8.shape[0]
+    if M % 256 or N % 256 or K % 128:
+        return False
+    with _timed(2.0 * M * N * K, lambda: tag("M%d N%d K%d" % (M, N, K))):
+        call("smer_gemm_fp8_ex", M, N, K, _p(a8), _ld(a8), _p(b8), _ld(b8), _p(a_inv), _p(b_inv),
+             _p(bias), int(bool(relu)), _p(residual), _ld(residual) if residual is not None else 0, _p(gate),
+             _ld(gate) if gate is not None else 0, float(gate_scale), float(drop_p), int(seed) & 0xFFFFFFFF,
+             _p(out), _ld(out) if out is not None else 0, _p(q8), _ld(q8) if q8 is not None else 0, _p(qs),
+             _p(amax), _stream())
+    return True
+
+
 def gemm_fp8_ex(a8, a_inv, b8, b_inv, out, *, bias=None, residual=None, gate=None, gate_scale=1.0,
                 q8=None, qs=None, amax=None):
     """out[M,N] bf16 = a_inv*b_inv * a8 @ b8^T (+ bias) (+ residual | ReLU gate:
@@ -492,24 +526,9 @@ def gemm_fp8_ex(a8, a_inv, b8, b_inv, out, *, bias=None, residual=None, gate=Non
     (q8 = e4m3(out * qs), max|out| folded into amax).  The fp8 backward's
     dgrad products; out may be None beside q8 (the e4m3 copy alone, streamed
     epilogue).  Returns False (nothing launched) outside the tiling."""
-    M, K = a8.shape
-    N = b8.shape[0]
-    if M % 256 or N % 256 or K % 128:
-        return False
-    timer = GEMM_TIMER
-    if timer is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    call("smer_gemm_fp8_ex", M, N, K, _p(a8), _ld(a8), _p(b8), _ld(b8), _p(a_inv), _p(b_inv),
-         _p(bias), 0, _p(residual), _ld(residual) if residual is not None else 0, _p(gate),
-         _ld(gate) if gate is not None else 0, float(gate_scale), 0.0, 0, _p(out), _ld(out) if out is not None else 0, _p(q8),
-         _ld(q8) if q8 is not None else 0, _p(qs), _p(amax), _stream())
-    if timer is not None:
-        ev1.record()
-        timer.records.append((ev0, ev1, 2.0 * M * N * K, "fp8 dgrad M%d N%d K%d%s" % (
-            M, N, K, " g" if gate is not None else " R" if residual is not None else "")))
-    return True
+    epi = " g" if gate is not None else " R" if residual is not None else ""
+    return _gemm_fp8(a8, a_inv, b8, b_inv, out, lambda mnk: "fp8 dgrad %s%s" % (mnk, epi), bias=bias,
+                     residual=residual, gate=gate, gate_scale=gate_scale, q8=q8, qs=qs, amax=amax)
 
 
 def linear_wgrad_fp8(dy8, dy_inv, x8, x_inv, dw, *, accumulate=True, db=None, ws=None, max_wg=0):
@@ -523,16 +542,9 @@ def linear_wgrad_fp8(dy8, dy_inv, x8, x_inv, dw, *, accumulate=True, db=None, ws
         return False
     if ws is None:
         ws = splitk_workspace(dy8.device)
-    timer = GEMM_TIMER
-    if timer is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    call("smer_gemm_wgrad_fp8", M, N, T, _p(dy8), _ld(dy8), _p(x8), _ld(x8), _p(dy_inv), _p(x_inv), _p(dw),
-         _ld(dw), int(accumulate), _p(db), int(accumulate), _p(ws), ws.numel(), int(max_wg), _stream())
-    if timer is not None:
-        ev1.record()
-        timer.records.append((ev0, ev1, 2.0 * M * N * T, "fp8 wgrad M%d N%d K%d" % (M, N, T)))
+    with _timed(2.0 * M * N * T, lambda: "fp8 wgrad M%d N%d K%d" % (M, N, T)):
+        call("smer_gemm_wgrad_fp8", M, N, T, _p(dy8), _ld(dy8), _p(x8), _ld(x8), _p(dy_inv), _p(x_inv), _p(dw),
+             _ld(dw), int(accumulate), _p(db), int(accumulate), _p(ws), ws.numel(), int(max_wg), _stream())
     return True
 
 
@@ -540,23 +552,9 @@ def gemm_fp8(a8, a_inv, b8, b_inv, out, *, bias=None, relu=False, residual=None,
              seed=0):
     """out[M,N] bf16 = a_inv*b_inv * a8 @ b8^T (+ epilogue).  Returns False
     (nothing launched) when the shape is outside the fp8 kernel's tiling."""
-    M, K = a8.shape
-    N = b8.shape[0]
-    if M % 256 or N % 256 or K % 128:
-        return False
-    timer = GEMM_TIMER
-    if timer is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    call("smer_gemm_fp8", M, N, K, _p(a8), _ld(a8), _p(b8), _ld(b8), _p(a_inv), _p(b_inv),
-         _p(bias), int(bool(relu)), _p(residual), _ld(residual) if residual is not None else 0,
-         float(drop_p), int(seed) & 0xFFFFFFFF, _p(out), _ld(out), _stream())
-    if timer is not None:
-        ev1.record()
-        timer.records.append((ev0, ev1, 2.0 * M * N * K, "fp8 M%d N%d K%d%s" % (
-            M, N, K, " R" if residual is not None else "")))
-    return True
+    epi = " R" if residual is not None else ""
+    return _gemm_fp8(a8, a_inv, b8, b_inv, out, lambda mnk: "fp8 %s%s" % (mnk, epi), bias=bias, relu=relu,
+                     residual=residual, drop_p=drop_p, seed=seed)
 
 
 def gemm_fp8_gate8(a8, a_inv, b8, b_inv, gate8, gate_scale, out, q8, qs, amax):
@@ -568,18 +566,10 @@ def gemm_fp8_gate8(a8, a_inv, b8, b_inv, gate8, gate_scale, out, q8, qs, amax):
     N = b8.shape[0]
     if M % 256 or N % 256 or K % 128:
         return False
-    timer = GEMM_TIMER
-    if timer is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    call("smer_gemm_fp8_gate8", M, N, K, _p(a8), _ld(a8), _p(b8), _ld(b8), _p(a_inv), _p(b_inv),
-         _p(gate8), _ld(gate8), float(gate_scale), _p(out), _ld(out) if out is not None else 0, _p(q8), _ld(q8),
-         _p(qs), _p(amax),
-         _stream())
-    if timer is not None:
-        ev1.record()
-        timer.records.append((ev0, ev1, 2.0 * M * N * K, "fp8 dgrad M%d N%d K%d g8" % (M, N, K)))
+    with _timed(2.0 * M * N * K, lambda: "fp8 dgrad M%d N%d K%d g8" % (M, N, K)):
+        call("smer_gemm_fp8_gate8", M, N, K, _p(a8), _ld(a8), _p(b8), _ld(b8), _p(a_inv), _p(b_inv),
+             _p(gate8), _ld(gate8), float(gate_scale), _p(out), _ld(out) if out is not None else 0, _p(q8),
+             _ld(q8), _p(qs), _p(amax), _stream())
     return True
 
 
@@ -588,23 +578,8 @@ def gemm_fp8_q(a8, a_inv, b8, b_inv, out, *, bias=None, relu=False, residual=Non
     """gemm_fp8 plus an e4m3 copy of `out` (q8 = e4m3(out * qs), max|out| folded
     into amax): the fp8 training forward's FFN1 (its output feeds FFN2).
     out=None: the e4m3 copy alone (streamed epilogue, SMER_FP8_Q8_FAST)."""
-    M, K = a8.shape
-    N = b8.shape[0]
-    if M % 256 or N % 256 or K % 128:
-        return False
-    timer = GEMM_TIMER
-    if timer is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    call("smer_gemm_fp8_q", M, N, K, _p(a8), _ld(a8), _p(b8), _ld(b8), _p(a_inv), _p(b_inv),
-         _p(bias), int(bool(relu)), _p(residual), _ld(residual) if residual is not None else 0,
-         float(drop_p), int(seed) & 0xFFFFFFFF, _p(out), _ld(out) if out is not None else 0, _p(q8),
-         _ld(q8) if q8 is not None else 0, _p(qs), _p(amax), _stream())
-    if timer is not None:
-        ev1.record()
-        timer.records.append((ev0, ev1, 2.0 * M * N * K, "fp8q M%d N%d K%d" % (M, N, K)))
-    return True
+    return _gemm_fp8(a8, a_inv, b8, b_inv, out, lambda mnk: "fp8q %s" % mnk, bias=bias, relu=relu,
+                     residual=residual, drop_p=drop_p, seed=seed, q8=q8, qs=qs, amax=amax)
 
 
 def layernorm_fp8(x, gamma, beta, y, mean, rstd, q8, qs, amax, eps=1e-5):

@@ -1,6 +1,7 @@
 """float64 reference, exact input classes, frames, bounds, dispatch mirror and
 shape table of the GEMM kernels (csrc/gemm.hip: smer_gemm in bf16 and fp32,
-smer_gemm_wgrad_bias / _ex).  Plain torch on the CPU;
+smer_gemm_wgrad_bias / _ex), and the dispatch mirror of the e4m3 products
+(smer_gemm_fp8 / _q / _ex / _gate8, smer_gemm_wgrad_fp8).  Plain torch on the CPU;
 tests/test_gemm_ref_cpu.py checks this file, tests/test_gemm_edges_gpu.py
 holds the kernels to it.
 
@@ -57,7 +58,8 @@ F_CLASS_FLOP = 0.5e9        # class F runs on the cases up to this size
 
 # environment switches csrc/gemm.hip reads on every call
 ENV_SWITCHES = ("SMER_GEMM64", "SMER_GEMM256", "SMER_GEMM256S", "SMER_G256_NONPERSIST",
-                "SMER_GEMM_F32_MFMA", "SMER_SPLITK_FUSED", "SMER_WGRAD256S")
+                "SMER_GEMM_F32_MFMA", "SMER_SPLITK_FUSED", "SMER_WGRAD256S", "SMER_FP8_Q8_FAST",
+                "SMER_GEMM256S_FP8")
 
 
 def f32r(x):
@@ -295,10 +297,14 @@ R_RUNS = (
     ("f32-200x309x66", Run("full", "odd")),
 )
 
-# every kernel the table must reach (tests/test_gemm_ref_cpu.py)
+# every kernel the tables must reach (tests/test_gemm_ref_cpu.py), in the
+# library's order: CASES the bf16 / fp32 ones, F8_CASES the e4m3 ones
+F8_KERNEL_NAMES = ("f8_generic", "f8_stream", "f8_q8_generic", "f8_q8_stream", "f8_q8_gate8", "f8_g256s",
+                   "f8_wgrad256s")
 KERNEL_NAMES = ("skinny_m16_kf", "skinny_m16_guard", "skinny_s64_kf", "skinny_s64_guard", "gemm64",
                 "g128_glds", "g128_reg", "g256_stream", "g256_generic", "g256s", "splitk_reduce",
-                "splitk_fused", "wgrad256", "wgrad256s", "f32_rows", "f32_skinny", "f32_mfma", "f32_tile")
+                "splitk_fused", "wgrad256", "wgrad256s", "f32_rows", "f32_skinny", "f32_mfma",
+                "f32_tile") + F8_KERNEL_NAMES
 
 
 def classes(case):
@@ -445,12 +451,132 @@ def library_plan(lib, case, run, cus):
     return SimpleNamespace(name=name, split=split, kchunk=kchunk)
 
 
+# ------------------------------------------------- e4m3 dispatch mirror
+F8 = 2                      # include/smer_hip.h SMER_F8
+PLAN_Q8, PLAN_GATE8 = 0x200, 0x4000
+F8_LDS_GENERIC = 128 << 10  # two 64-KiB operand stages
+F8_LDS_STREAM = 160 << 10   # + 64 epilogue rows of 256 bf16
+F8_LDS_WGRAD = 128 << 10    # four 32-KiB slots
+
+
+def expected_plan_f8(fwd, M, N, K, *, vec=True, q8=False, gate8=False, ws_bytes=WS_BYTES, max_wg=0,
+                     env=None, cus=256):
+    """Pure-Python mirror of the e4m3 dispatch (csrc/gemm_plan.h plan_f8),
+    written from its rules: the forward / dgrad products (fwd; M, N % 256 ==
+    0, K % 128 == 0) by epilogue on min(tiles, CUs rounded down to 8)
+    workgroups; the weight gradient (K % 64 == 0) on its one kernel, split
+    over K like the bf16 256x256 weight gradient but for N / 256 rows of M
+    bias partials per slice.  name, split, kchunk as expected_plan; grid and
+    dynamic LDS bytes."""
+    env = env or {}
+    tiles = (M // 256) * (N // 256)
+
+    def persistent(nwg, room):
+        return nwg if nwg <= room else room // 8 * 8
+
+    def P(name, lds, grid, split=1, kchunk=K):
+        return SimpleNamespace(name=name, split=split, kchunk=kchunk, grid=grid, lds=lds)
+
+    if fwd:
+        grid = persistent(tiles, cus)
+        if env.get("SMER_GEMM256S_FP8", "")[:1] == "1" and vec and not q8 and K % 64 == 0 and K // 64 >= 4:
+            return P("f8_g256s", F8_LDS_STREAM, grid)
+        if not vec:
+            return P("f8_generic", F8_LDS_GENERIC, grid)
+        if gate8:
+            return P("f8_q8_gate8", F8_LDS_STREAM, grid)
+        if q8 and env.get("SMER_FP8_Q8_FAST", "")[:1] == "0":
+            return P("f8_q8_generic", F8_LDS_GENERIC, grid)
+        return P("f8_q8_stream" if q8 else "f8_stream", F8_LDS_STREAM, grid)
+    room = max(8, min(cus, max_wg)) if max_wg > 0 else cus
+    slice_bytes = 4 * (M * N + (N // 256) * M)
+    ns = min(room // tiles, K // 512, max(0, ws_bytes - TICKET_BYTES) // slice_bytes, 64)
+    split, kchunk = 1, K
+    if ns > 1:
+        kchunk = _cdiv(_cdiv(K, ns), 64) * 64
+        split = _cdiv(K, kchunk)
+    return P("f8_wgrad256s" + ("+splitk_reduce" if split > 1 else ""), F8_LDS_WGRAD,
+             persistent(tiles * split, room), split, kchunk)
+
+
+def library_plan_f8(lib, fwd, M, N, K, *, vec=True, q8=False, gate8=False, ws_bytes=WS_BYTES, max_wg=0, cus=0):
+    """smer_gemm_plan's answer for the e4m3 call expected_plan_f8 describes,
+    under the current environment (cus = 0: the current device's count)."""
+    import ctypes
+    facts = PLAN_BITS["C"] if fwd else PLAN_BITS["Cf"] | PLAN_CF_ALIGNED16
+    facts |= (PLAN_BITS["vec"] if vec else 0) | (PLAN_Q8 if q8 else 0)
+    facts |= (PLAN_GATE8 | PLAN_BITS["gate"] if gate8 else 0) | (PLAN_BITS["ws"] if not fwd and ws_bytes else 0)
+    out = (ctypes.c_int * 8)()
+    rc = lib.smer_gemm_plan(F8, int(fwd), int(fwd), M, N, K, facts, N, 0 if fwd else ws_bytes, max_wg, cus, out)
+    assert rc == 0, lib.smer_last_error()
+    kernel, _, grid, _, lds, split, kchunk, reduce = out
+    name = "+".join(lib.smer_gemm_kernel_name(i).decode() for i in (kernel, reduce) if i >= 0)
+    return SimpleNamespace(name=name, split=split, kchunk=kchunk, grid=grid, lds=lds)
+
+
+def _f8_table():
+    """Plan-only cases (no operands) at the edges where plan_f8 decides."""
+    t = []
+
+    def add(cid, fwd, M, N, K, env=None, **facts):
+        t.append(SimpleNamespace(id=cid, fwd=fwd, M=M, N=N, K=K, env=dict(env or {}), facts=facts))
+
+    stag = {"SMER_GEMM256S_FP8": "1"}
+    add("f8-stream", True, 512, 768, 768)
+    add("f8-generic-bias-off4", True, 512, 768, 768, vec=False)     # e.g. a bias view at a 4-byte offset
+    add("f8-q8", True, 512, 768, 768, q8=True)
+    add("f8-q8-fast1", True, 512, 768, 768, q8=True, env={"SMER_FP8_Q8_FAST": "1"})
+    add("f8-q8-fast0", True, 512, 768, 768, q8=True, env={"SMER_FP8_Q8_FAST": "0"})
+    add("f8-fast0-no-copy", True, 512, 768, 768, env={"SMER_FP8_Q8_FAST": "0"})
+    add("f8-gate8", True, 512, 768, 256, q8=True, gate8=True)
+    add("f8-g256s-K256", True, 512, 768, 256, env=stag)              # the four-step minimum
+    add("f8-g256s-K128", True, 512, 768, 128, env=stag)              # below it
+    add("f8-g256s-q8", True, 512, 768, 768, env=stag, q8=True)       # the e4m3 copy is not staggered
+    add("f8-g256s-novec", True, 512, 768, 768, env=stag, vec=False)
+    add("f8-g256s-off", True, 512, 768, 768, env={"SMER_GEMM256S_FP8": "0"})
+    add("f8-bf16-switch", True, 512, 768, 768, env={"SMER_GEMM256S": "1"})   # the bf16 switch of the same prefix
+    # tile counts one below, at and one above 64 / 256 / 304 CUs
+    for tm, tn in ((7, 9), (8, 8), (5, 13), (15, 17), (16, 16), (1, 257), (3, 101), (16, 19), (5, 61)):
+        add("f8-tiles%d" % (tm * tn), True, 256 * tm, 256 * tn, 128)
+        add("f8w-tiles%d" % (tm * tn), False, 256 * tm, 256 * tn, 64)
+    # weight gradients
+    add("f8w-T64", False, 256, 256, 64)                              # one slice
+    add("f8w-depth", False, 768, 768, 2048)                          # K / 512 = 4 binds
+    add("f8w-ws", False, 2304, 768, 65536, ws_bytes=16 << 20)        # two slices fit
+    # N / 256 = 2: three slices of M * N + 2 M floats fit, four of bf16's M * N + M would
+    add("f8w-partials", False, 256, 512, 8192, ws_bytes=TICKET_BYTES + 16 * (256 * 512 + 2 * 256) - 4)
+    add("f8w-64slices", False, 256, 256, 65536)
+    for w in (4, 8, 100, 1000):                                      # 4: the cap's floor of 8 workgroups
+        add("f8w-wg%d" % w, False, 768, 768, 8192, max_wg=w)
+    add("f8w-wg100-over", False, 2304, 3072, 8192, max_wg=100)       # 108 tiles on 96 = 100 rounded down to 8
+    add("f8w-no-ws", False, 768, 768, 8192, ws_bytes=0)
+    add("f8w-tickets-only", False, 768, 768, 8192, ws_bytes=TICKET_BYTES)
+    add("f8w-c4", False, 768, 3072, 65536)
+    return t
+
+
+F8_CASES = _f8_table()
+assert len({c.id for c in F8_CASES}) == len(F8_CASES)
+
+
+def f8_mirror(case, cus):
+    return expected_plan_f8(case.fwd, case.M, case.N, case.K, env=case.env, cus=cus, **case.facts)
+
+
 def plan_mismatches(lib, cus, setenv, lib_cus=None):
     """Every (case, run) of the table whose mirror and library plans differ at
     `cus` CUs (the library asked with lib_cus when given: 0 is the device's
     own count), the case's env applied through `setenv(env)`:
-    [(case id, run id, mirror, library)]."""
+    [(case id, run id, mirror, library)]; of F8_CASES, the cases that differ
+    in name, split, kchunk, grid or LDS bytes."""
     bad = []
+    for case in F8_CASES:
+        setenv(case.env)
+        m = f8_mirror(case, cus)
+        l = library_plan_f8(lib, case.fwd, case.M, case.N, case.K, cus=cus if lib_cus is None else lib_cus,
+                            **case.facts)
+        if vars(m) != vars(l):
+            bad.append((case.id, "", vars(m), vars(l)))
     for case in CASES:
         setenv(case.env)
         for run in case.runs:

@@ -38,6 +38,6 @@ def test_every_switch_is_documented():
             "SMER_WGRAD256S", "SMER_SPLITK_FUSED", "SMER_GEMM_F32_MFMA", "SMER_GEMM_GLDS", "SMER_WGRAD_GLDS",
             "SMER_SPLITK_DEPTH", "SMER_WGRAD256", "SMER_WGRAD256_SLOTS", "SMER_WGRAD256_DEPTH", "SMER_SKINNY16",
             "SMER_SKINNY16_CAP", "SMER_WGRAD_WGP2", "SMER_G256_MIN", "SMER_SKINNY_KF",
-            "SMER_SKINNY_ROWS_F32"} <= switches
+            "SMER_SKINNY_ROWS_F32", "SMER_FP8_Q8_FAST", "SMER_GEMM256S_FP8"} <= switches
     missing = sorted(s for s in switches if "`%s`" % s not in table)
     assert not missing, "undocumented runtime switches: %s" % missing

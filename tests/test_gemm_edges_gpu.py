@@ -76,9 +76,9 @@ def planned(case, run):
 def test_plan_matches_mirror(monkeypatch, ncus):
     """The library's dispatch (smer_gemm_plan: the very gemm_plan the
     launchers run, nothing launched) and gemmref's mirror agree on every
-    (case, run) of the table, split-K slices and depth included, at this
-    device's CU count and at 64 / 256 / 304; the library's kernel names are
-    gemmref.KERNEL_NAMES."""
+    (case, run) of the table, split-K slices and depth included, and on every
+    plan-only e4m3 case (gemmref.F8_CASES), at this device's CU count and at
+    64 / 256 / 304; the library's kernel names are gemmref.KERNEL_NAMES."""
     from smer_music_generation_amd import _lib as L
     lib = L.load()
     names = [lib.smer_gemm_kernel_name(i) for i in range(len(G.KERNEL_NAMES) + 1)]

@@ -87,11 +87,38 @@ def test_every_kernel_is_reached():
     for case in G.CASES:
         for run in case.runs:
             seen.update(_names(G.label(case, run, CUS)))
-    assert seen == set(G.KERNEL_NAMES), (set(G.KERNEL_NAMES) - seen, seen - set(G.KERNEL_NAMES))
+    table = set(G.KERNEL_NAMES) - set(G.F8_KERNEL_NAMES)
+    assert seen == table, (table - seen, seen - table)
     rseen = set()
     for cid, run in G.R_RUNS:
         rseen.update(_names(G.label(G.BY_ID[cid], run, CUS)))
-    assert rseen == set(G.KERNEL_NAMES), set(G.KERNEL_NAMES) - rseen
+    assert rseen == table, table - rseen
+    # the e4m3 kernels: each named by some plan-only case, so no branch of plan_f8 goes unmirrored
+    f8seen = set()
+    for case in G.F8_CASES:
+        f8seen.update(_names(G.f8_mirror(case, CUS).name))
+    assert len(G.F8_KERNEL_NAMES) == 7 and f8seen == set(G.F8_KERNEL_NAMES) | {"splitk_reduce"}, f8seen
+
+
+def test_f8_table_edges():
+    """The splits and grids the comments of gemmref.F8_CASES claim."""
+    by = {c.id: c for c in G.F8_CASES}
+    plan = lambda cid, cus=CUS: G.f8_mirror(by[cid], cus)  # noqa: E731
+    assert [plan(c).name for c in ("f8-stream", "f8-g256s-K256", "f8-g256s-K128", "f8-bf16-switch")] == \
+        ["f8_stream", "f8_g256s", "f8_stream", "f8_stream"]
+    assert plan("f8-q8-fast0").name == "f8_q8_generic" and plan("f8-fast0-no-copy").name == "f8_stream"
+    for cus in (64, 256, 304):
+        below, at, above = {64: (63, 64, 65), 256: (255, 256, 257), 304: (303, 304, 305)}[cus]
+        assert [plan("f8-tiles%d" % t, cus).grid for t in (below, at, above)] == [below, at, cus]
+        assert [plan("f8w-tiles%d" % t, cus).grid for t in (below, at, above)] == [below, at, cus]
+    assert (plan("f8w-T64").split, plan("f8w-depth").split, plan("f8w-ws").split) == (1, 4, 2)
+    p = plan("f8w-partials")
+    assert (p.split, p.kchunk) == (3, 2752)   # M * N + M floats per slice would give (4, 2048)
+    assert plan("f8w-64slices").split == 64 and plan("f8w-64slices", 64).split == 64
+    assert [(plan("f8w-wg%d" % w).split, plan("f8w-wg%d" % w).grid) for w in (4, 8, 100, 1000)] == \
+        [(1, 8), (1, 8), (11, 99), (16, 144)]
+    assert plan("f8w-wg100-over").grid == 96
+    assert plan("f8w-no-ws").split == plan("f8w-tickets-only").split == 1
 
 
 @pytest.mark.parametrize("edge", G.NOT_EDGES, ids=lambda e: e[0])
@@ -120,32 +147,54 @@ def test_table_edges_at_256_cus():
     assert [G.epi_flags(c, r).vec for r in c.runs] == [True] * 7 + [False, True, False]
 
 
-@pytest.mark.parametrize("ncus", [64, 256, 304])
-def test_plan_matches_mirror(monkeypatch, ncus):
-    """The library's dispatch (smer_gemm_plan with an explicit CU count: no
-    HIP call, nothing launched) and the mirror agree on every (case, run) of
-    the table, split-K slices and depth included.  Skips only where
-    libsmer_hip.so is not built or cannot be loaded without a GPU;
-    tests/test_gemm_edges_gpu.py runs the same comparison on the device."""
+def _library():
+    """libsmer_hip.so; skips only where it is not built or cannot be loaded
+    without a GPU."""
     import os
     from smer_music_generation_amd import _lib as L
     if not os.path.exists(L.LIB_PATH):
         pytest.skip("libsmer_hip.so is not built")
     try:
-        lib = L.load()
+        return L.load()
     except OSError as e:
         if torch.cuda.is_available():
             raise
         pytest.skip("libsmer_hip.so does not load without a GPU: %s" % e)
 
-    def setenv(env):
-        for k in G.ENV_SWITCHES:
-            monkeypatch.setenv(k, env[k]) if k in env else monkeypatch.delenv(k, raising=False)
 
+def _setenv(monkeypatch, env):
+    for k in G.ENV_SWITCHES:
+        monkeypatch.setenv(k, env[k]) if k in env else monkeypatch.delenv(k, raising=False)
+
+
+@pytest.mark.parametrize("ncus", [64, 256, 304])
+def test_plan_matches_mirror(monkeypatch, ncus):
+    """The library's dispatch (smer_gemm_plan with an explicit CU count: no
+    HIP call, nothing launched) and the mirror agree on every (case, run) of
+    the table, split-K slices and depth included, and on every plan-only
+    e4m3 case (gemmref.F8_CASES), grid and LDS bytes included.
+    tests/test_gemm_edges_gpu.py runs the same comparison on the device."""
+    lib = _library()
+    setenv = lambda env: _setenv(monkeypatch, env)  # noqa: E731
     names = [lib.smer_gemm_kernel_name(i) for i in range(len(G.KERNEL_NAMES) + 1)]
     assert names == [n.encode() for n in G.KERNEL_NAMES] + [None]
     bad = G.plan_mismatches(lib, ncus, setenv)
     assert not bad, bad
+
+
+def test_f8_persistent_grid_is_a_multiple_of_eight(monkeypatch):
+    """64, 256 and 304 are multiples of 8, so the rounding of the e4m3
+    products' persistent grids shows only at another CU count: 100."""
+    lib = _library()
+    _setenv(monkeypatch, {})
+    grids = {True: set(), False: set()}
+    for case in G.F8_CASES:
+        if case.id.startswith(("f8-tiles", "f8w-tiles")):
+            m = G.f8_mirror(case, 100)
+            l = G.library_plan_f8(lib, case.fwd, case.M, case.N, case.K, cus=100, **case.facts)
+            assert vars(m) == vars(l), (case.id, vars(m), vars(l))
+            grids[case.fwd].add(l.grid)
+    assert grids[True] == grids[False] == {63, 64, 65, 96}
 
 
 # --------------------------------------------------------------- frames

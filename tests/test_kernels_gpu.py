@@ -1085,6 +1085,20 @@ def _e4m3_ref(x, amax):
     return torch.from_numpy(np.clip(y, -448, 448)).to(torch.float8_e4m3fn).view(torch.uint8)
 
 
+def f8_planned(name, fwd, M, N, K, **facts):
+    """Before an e4m3 call: the library's plan for it (smer_gemm_plan on this
+    device, under the current environment) must name `name`, the kernel
+    tests/gemmref.py's mirror expects of the call, with the mirror's split."""
+    from smer_music_generation_amd import _lib as L
+    from tests import gemmref as G
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    want = G.expected_plan_f8(fwd, M, N, K, env=os.environ, cus=cus, **facts)
+    got = G.library_plan_f8(L.load(), fwd, M, N, K, **facts)
+    print("fp8 %s %dx%dx%d %s -> %s" % ("fwd" if fwd else "wgrad", M, N, K, facts, vars(got)))
+    assert vars(got) == vars(want) and got.name.split("+")[0] == name, (name, vars(want), vars(got))
+    return got
+
+
 def test_gemm_fp8_exact_integer_layout():
     """fp8 MFMA fragment / output layout with exact small-integer e4m3 data
     and an asymmetric B: the kernel must reproduce A.B^T exactly."""
@@ -1098,8 +1112,34 @@ def test_gemm_fp8_exact_integer_layout():
     b8 = B.to(torch.float8_e4m3fn).view(torch.uint8).to(dev)
     one = torch.ones(1, device=dev)
     C = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+    f8_planned("f8_stream", True, M, N, K)
     assert O.gemm_fp8(a8, one, b8, one, C)
     ref = A.to(torch.float8_e4m3fn).float() @ B.to(torch.float8_e4m3fn).float().t()
+    torch.cuda.synchronize()
+    assert torch.equal(C.float().cpu(), ref.to(torch.bfloat16).float())
+
+
+def test_gemm_fp8_generic_epilogue_exact():
+    """A bias view at a 4-byte offset breaks the vector epilogue: the call
+    runs on the generic two-stage kernel (f8_generic), which no other test
+    executes.  Exact small-integer e4m3 data and an integer bias: A.B^T +
+    bias bit for bit."""
+    O = ops()
+    M, N, K = 256, 256, 128
+    g = torch.Generator(device="cpu").manual_seed(3)
+    A = torch.randint(-4, 5, (M, K), generator=g).float()
+    B = torch.randint(-3, 4, (N, K), generator=g).float()
+    B[:, 0] += torch.arange(N) % 5  # asymmetric
+    bias = torch.randint(-16, 17, (N,), generator=g).float()
+    a8 = A.to(torch.float8_e4m3fn).view(torch.uint8).to(dev)
+    b8 = B.to(torch.float8_e4m3fn).view(torch.uint8).to(dev)
+    one = torch.ones(1, device=dev)
+    bias_off = torch.cat([torch.zeros(1), bias]).to(dev)[1:]
+    assert bias_off.data_ptr() % 16 == 4
+    C = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+    f8_planned("f8_generic", True, M, N, K, vec=False)
+    assert O.gemm_fp8(a8, one, b8, one, C, bias=bias_off)
+    ref = A @ B.t() + bias  # |.| <= 128 * 4 * 7 + 16: exact in fp32, integers the bf16 store may round
     torch.cuda.synchronize()
     assert torch.equal(C.float().cpu(), ref.to(torch.bfloat16).float())
 
@@ -1129,14 +1169,18 @@ def test_gemm256s_fp8_matches_two_stage_kernel(monkeypatch, M, N, K):
 
     def run(flag):
         monkeypatch.setenv("SMER_GEMM256S_FP8", flag)
+        kernel = "f8_g256s" if flag == "1" else "f8_stream"
         outs = []
         C = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+        f8_planned(kernel, True, M, N, K)
         assert O.gemm_fp8(a8, one, b8, one, C)
         outs.append(C)
         C = torch.empty_like(C)
+        f8_planned(kernel, True, M, N, K)
         assert O.gemm_fp8(a8, ai, b8, bi, C, bias=bias, relu=True, residual=res, drop_p=0.1, seed=7)
         outs.append(C)
         C = torch.empty_like(C)
+        f8_planned(kernel, True, M, N, K)
         assert O.gemm_fp8_ex(a8, ai, b8, bi, C, gate=gate, gate_scale=1.25)
         outs.append(C)
         torch.cuda.synchronize()
@@ -1395,6 +1439,9 @@ def test_wgrad_fp8_exact_integer_layout(M, N, T, acc, strided):
     dw = old.to(dev) if acc else torch.full((M, N), float("nan"), device=dev)
     oldb = torch.randint(-8, 9, (M,), generator=g).float()
     db = oldb.to(dev) if acc else torch.full((M,), float("nan"), device=dev)
+    plan = f8_planned("f8_wgrad256s", False, M, N, T)
+    if T == 64 or (M, N, T) == (768, 512, 4096):  # one slice; split with N / 256 = 2 rows of bias partials
+        assert (plan.split > 1) == (T > 64), vars(plan)
     assert O.linear_wgrad_fp8(dy8, si, x8, xi, dw, accumulate=acc, db=db)
     ref = (dY.t() @ X) * 0.125 + (old if acc else 0.0)
     refb = dY.sum(0) * 0.5 + (oldb if acc else 0.0)
@@ -1402,6 +1449,7 @@ def test_wgrad_fp8_exact_integer_layout(M, N, T, acc, strided):
     assert torch.equal(dw.cpu(), ref)
     assert torch.equal(db.cpu(), refb)
     dw2 = torch.zeros(M, N, device=dev)  # without the bias gradient: the same dW
+    f8_planned("f8_wgrad256s", False, M, N, T)
     assert O.linear_wgrad_fp8(dy8, si, x8, xi, dw2, accumulate=False)
     torch.cuda.synchronize()
     assert torch.equal(dw2.cpu(), (dY.t() @ X) * 0.125)
@@ -1440,6 +1488,7 @@ def test_fp8_q8_streamed_epilogue_equals_generic(monkeypatch, mode):
 
     def run(flag):
         monkeypatch.setenv("SMER_FP8_Q8_FAST", flag)
+        f8_planned("f8_q8_stream" if flag == "1" else "f8_q8_generic", True, M, N, K, q8=True)
         C = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
         q = torch.empty(M, N, device=dev, dtype=torch.uint8)
         am = torch.zeros(1, device=dev, dtype=torch.int32)
@@ -1513,6 +1562,7 @@ def test_fp8_e4m3_gate_and_copy_only_output():
         out = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
         q = torch.empty(M, N, device=dev, dtype=torch.uint8)
         am = torch.zeros(1, device=dev, dtype=torch.int32)
+        f8_planned("f8_q8_gate8" if use8 else "f8_q8_stream", True, M, N, K, q8=True, gate8=use8)
         if use8:
             assert O.gemm_fp8_gate8(a8, inv, b8, inv, g8, 1.25, out, q, qs, am)
         else:
@@ -1526,6 +1576,7 @@ def test_fp8_e4m3_gate_and_copy_only_output():
     for use8 in (False, True):
         q = torch.empty(M, N, device=dev, dtype=torch.uint8)
         am = torch.zeros(1, device=dev, dtype=torch.int32)
+        f8_planned("f8_q8_gate8" if use8 else "f8_q8_stream", True, M, N, K, q8=True, gate8=use8)
         if use8:
             assert O.gemm_fp8_gate8(a8, inv, b8, inv, g8, 1.25, None, q, qs, am)
         else:
@@ -1539,6 +1590,7 @@ def test_fp8_e4m3_gate_and_copy_only_output():
         out = torch.empty(M, N, device=dev, dtype=torch.bfloat16) if with_c else None
         q = torch.empty(M, N, device=dev, dtype=torch.uint8)
         am = torch.zeros(1, device=dev, dtype=torch.int32)
+        f8_planned("f8_q8_stream", True, M, N, K, q8=True)
         assert O.gemm_fp8_q(a8, inv, b8, inv, out, bias=bias, relu=True, drop_p=0.1, seed=4, q8=q, qs=qs,
                             amax=am)
         res.append((q, am))
