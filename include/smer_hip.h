@@ -67,6 +67,9 @@
  *   smer_grad_sqnorm_*, smer_clip_scale, smer_adam_guarded: global-norm
  *                        gradient clipping and the non-finite step guard
  *                        around that step (torch.nn.utils.clip_grad_norm_)
+ *   smer_adam_ex         that step with weight decay (torch.optim.AdamW's
+ *                        decoupled form or Adam(weight_decay=)'s coupled L2)
+ *                        and an EMA of the weights, in the same pass
  *   smer_gemm_wgrad_bias nn.Linear weight AND bias gradients in one pass
  *                        (autograd of transformer.py:389-469 / model.py:106
  *                        linears, train.py:783)
@@ -736,6 +739,33 @@ int smer_clip_scale(int nparts, const float* part, float max_norm, float* ctl,
 int smer_adam_guarded(long n, float* p, const float* g, float* m, float* v, void* p_bf16,
                       float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
                       const float* ctl, smer_stream_t stream);
+
+/* The Adam step with weight decay and an exponential moving average of the
+ * weights in one pass over p, g, m, v (p_bf16, ema).  smer_adam's arguments
+ * plus: ctl, the control block of smer_clip_scale (null: unguarded); wd,
+ * decay_mul, decoupled; ema (nullable), ema_decay.  Per element, in fp32:
+ *   1. ctl && ctl[2] != 0: the kernel returns at once; p, m, v, p_bf16 and
+ *      ema keep their bits
+ *   2. gi = ctl ? fl(g[i] * ctl[1]) : g[i]
+ *   3. decoupled == 0 && wd != 0 (torch.optim.Adam(weight_decay=wd)):
+ *      gi = gi + wd * p[i], after the clip scale, as clip_grad_norm_ followed
+ *      by Adam.step does
+ *   4. decoupled != 0 (torch.optim.AdamW): pi = p[i] * decay_mul, where the
+ *      caller passes decay_mul = (float)(1 - (double)lr * wd), one rounding
+ *      of the double product as AdamW's param.mul_(1 - lr * weight_decay)
+ *   5. smer_adam's moments and step on gi and pi; m, v, p (p_bf16) stored
+ *   6. ema: e = e + (1 - ema_decay) * (p_new - e)
+ * wd == 0, decay_mul == 1 and ema == null write smer_adam's (ctl == null) or
+ * smer_adam_guarded's bits.  The body moves 16-B vectors (8-B for p_bf16); a
+ * scalar head and tail take any n >= 0 and any 4-B aligned bases (all scalar
+ * when p, g, m, v, ema do not share one offset within 16 B).  Elementwise:
+ * no atomics, no workspace, and a range split into several launches gets
+ * the same bits.  A null p/g/m/v, n < 0, a misaligned pointer or a wd,
+ * decay_mul or ema_decay that is not finite is SMER_ERR_INVALID. */
+int smer_adam_ex(long n, float* p, const float* g, float* m, float* v, void* p_bf16,
+                 float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
+                 const float* ctl, float wd, float decay_mul, int decoupled, float* ema,
+                 float ema_decay, smer_stream_t stream);
 
 int smer_cast(int src_dtype, int dst_dtype, long n, const void* src, void* dst,
               smer_stream_t stream);

@@ -113,6 +113,113 @@ __global__ void adam_kernel(long n, float* __restrict__ p, const float* __restri
   }
 }
 
+// smer_adam_ex: the step above with weight decay and an exponential moving
+// average of the weights in the same pass.  Per element, in adam_kernel's own
+// arithmetic: gi = fl(g * ctl[1]) when GUARDED; WD == 1 (coupled L2, torch
+// Adam(weight_decay=)): gi += wd * p, after the clip scale; WD == 2
+// (decoupled, torch AdamW): p *= decay_mul before the update; EMA: e += (1 -
+// ema_decay) * (p_new - e).  The value barriers keep gi, the decayed weight
+// and the stored weight the rounded values they are documented to be (see
+// adam_kernel), so WD == 0 without EMA is adam_kernel bit for bit
+// (tests/test_adam_ex_gpu.py).
+struct AdamExArgs {
+  float lr, b1, b2, eps, bc1, bc2s, wd, decay_mul, ema_decay;
+};
+
+template <bool GUARDED, int WD, bool EMA>
+__device__ __forceinline__ void adam_ex_elem(const AdamExArgs& a, float step, float gs, float& p, float g,
+                                             float& m, float& v, float& e) {
+  float gi = g;
+  if constexpr (GUARDED) {
+    gi = gi * gs;
+    asm volatile("" : "+v"(gi));
+  }
+  float pi = p;
+  if constexpr (WD == 1) {
+    gi = __builtin_fmaf(a.wd, pi, gi);
+    asm volatile("" : "+v"(gi));
+  }
+  if constexpr (WD == 2) {
+    pi = pi * a.decay_mul;
+    asm volatile("" : "+v"(pi));
+  }
+  // adam_kernel's expressions with the contractions written out as hipcc
+  // forms them there (which product of v * b2 + (1 - b2) * g * g it fuses
+  // depends on the loop around it: left alone, this kernel's scalar loop
+  // fused the other one and lost the last bit of v)
+  float mi = m;
+  mi = __builtin_fmaf(1.f - a.b1, gi - mi, mi);
+  float vi = __builtin_fmaf((1.f - a.b2) * gi, gi, v * a.b2);
+  float den = sqrtf(vi) / a.bc2s + a.eps;
+  pi = __builtin_fmaf(-step, mi / den, pi);
+  m = mi;
+  v = vi;
+  p = pi;
+  if constexpr (EMA) {
+    asm volatile("" : "+v"(pi));
+    e = __builtin_fmaf(1.f - a.ema_decay, pi - e, e);
+  }
+}
+
+// Elements [head, head + 4 nvec) go as 16-B vectors of p/g/m/v/ema and 8-B
+// vectors of the bf16 copy (the host picks head so that all of them are
+// aligned there, or head = n when the bases disagree); the n - 4 nvec
+// elements in front of and behind them go one by one.  Every element is
+// updated by exactly one lane from its own inputs: no atomics, no workspace,
+// and a range split into several launches gets the same bits.
+template <bool GUARDED, int WD, bool EMA>
+__global__ __launch_bounds__(256) void adam_ex_kernel(long n, long head, long nvec, float* __restrict__ p,
+                                                      const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, bf16* __restrict__ pb,
+                                                      float* __restrict__ ema, const float* __restrict__ ctl,
+                                                      AdamExArgs a) {
+  float gs = 1.f;
+  if constexpr (GUARDED) {
+    if (ctl[2] != 0.f) return;
+    gs = ctl[1];
+  }
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  const long stride = (long)gridDim.x * 256;
+  const float step = a.lr / a.bc1;
+  for (long k = t; k < nvec; k += stride) {
+    const long i = head + 4 * k;
+    f32x4 P = *reinterpret_cast<const f32x4*>(p + i);
+    const f32x4 G = *reinterpret_cast<const f32x4*>(g + i);
+    f32x4 M = *reinterpret_cast<const f32x4*>(m + i);
+    f32x4 V = *reinterpret_cast<const f32x4*>(v + i);
+    f32x4 E = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (EMA) E = *reinterpret_cast<const f32x4*>(ema + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pj = P[j], mj = M[j], vj = V[j], ej = E[j];
+      adam_ex_elem<GUARDED, WD, EMA>(a, step, gs, pj, G[j], mj, vj, ej);
+      P[j] = pj, M[j] = mj, V[j] = vj, E[j] = ej;
+    }
+    *reinterpret_cast<f32x4*>(m + i) = M;
+    *reinterpret_cast<f32x4*>(v + i) = V;
+    *reinterpret_cast<f32x4*>(p + i) = P;
+    if (pb) {
+      bf16x4 B;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) B[j] = (bf16)P[j];
+      *reinterpret_cast<bf16x4*>(pb + i) = B;
+    }
+    if constexpr (EMA) *reinterpret_cast<f32x4*>(ema + i) = E;
+  }
+  const long nscalar = n - 4 * nvec;
+  for (long s = t; s < nscalar; s += stride) {
+    const long i = s < head ? s : s + 4 * nvec;
+    float pi = p[i], mi = m[i], vi = v[i], ei = 0.f;
+    if constexpr (EMA) ei = ema[i];
+    adam_ex_elem<GUARDED, WD, EMA>(a, step, gs, pi, g[i], mi, vi, ei);
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = pi;
+    if (pb) pb[i] = (bf16)pi;
+    if constexpr (EMA) ema[i] = ei;
+  }
+}
+
 // Global gradient norm, stage 1: part[c] = sum of squares of chunk c
 // (GN_CH floats) of a range.  256 lanes x 4 iterations x 4 independent 16-B
 // loads; lane accumulator u takes load u of every iteration (16 fmas in
@@ -461,6 +568,70 @@ extern "C" int smer_adam_guarded(long n, float* p, const float* g, float* m, flo
   hipLaunchKernelGGL((adam_kernel<true, const float*>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, p, g,
                      m, v, (bf16*)p_bf16, lr, b1, b2, eps, bc1, bc2_sqrt, ctl);
   SMER_CHECK_LAUNCH("smer_adam_guarded");
+  return SMER_OK;
+}
+
+namespace {
+struct AdamExLaunch {
+  long n, head, nvec;
+  float *p, *m, *v, *ema;
+  const float *g, *ctl;
+  bf16* pb;
+  AdamExArgs a;
+  hipStream_t stream;
+};
+
+template <bool GUARDED, int WD, bool EMA>
+void adam_ex_launch(const AdamExLaunch& l) {
+  const long nscalar = l.n - 4 * l.nvec;
+  long blocks = ((l.nvec > nscalar ? l.nvec : nscalar) + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL((adam_ex_kernel<GUARDED, WD, EMA>), dim3(blocks), dim3(256), 0, l.stream, l.n, l.head,
+                     l.nvec, l.p, l.g, l.m, l.v, l.pb, l.ema, l.ctl, l.a);
+}
+
+template <bool GUARDED, int WD>
+void adam_ex_pick_ema(const AdamExLaunch& l) {
+  l.ema ? adam_ex_launch<GUARDED, WD, true>(l) : adam_ex_launch<GUARDED, WD, false>(l);
+}
+
+template <bool GUARDED>
+void adam_ex_pick_wd(const AdamExLaunch& l, int wd_mode) {
+  if (wd_mode == 0) adam_ex_pick_ema<GUARDED, 0>(l);
+  else if (wd_mode == 1) adam_ex_pick_ema<GUARDED, 1>(l);
+  else adam_ex_pick_ema<GUARDED, 2>(l);
+}
+}  // namespace
+
+extern "C" int smer_adam_ex(long n, float* p, const float* g, float* m, float* v, void* p_bf16, float lr,
+                            float b1, float b2, float eps, float bc1, float bc2_sqrt, const float* ctl,
+                            float wd, float decay_mul, int decoupled, float* ema, float ema_decay,
+                            smer_stream_t stream) {
+  SMER_REQUIRE(p && g && m && v, "smer_adam_ex: null pointer");
+  SMER_REQUIRE(n >= 0, "smer_adam_ex: n < 0");
+  SMER_REQUIRE(__builtin_isfinite(wd) && __builtin_isfinite(decay_mul) && __builtin_isfinite(ema_decay),
+               "smer_adam_ex: wd, decay_mul and ema_decay must be finite");
+  const uintptr_t a4[5] = {(uintptr_t)p, (uintptr_t)g, (uintptr_t)m, (uintptr_t)v, (uintptr_t)ema};
+  SMER_REQUIRE(((a4[0] | a4[1] | a4[2] | a4[3] | a4[4]) & 3) == 0 && ((uintptr_t)p_bf16 & 1) == 0,
+               "smer_adam_ex: p, g, m, v, ema must be 4-B aligned, p_bf16 2-B aligned");
+  if (n == 0) return SMER_OK;
+  // the scalar head ends where p reaches a 16-B boundary; the vector body
+  // needs g, m, v, ema on one there too, and the bf16 copy on an 8-B one
+  long head = (long)(((16 - (a4[0] & 15)) & 15) / 4);
+  if (head > n) head = n;
+  bool vec = true;
+  for (int k = 1; k < 5; ++k) vec = vec && (a4[k] == 0 || (a4[k] & 15) == (a4[0] & 15));
+  if (p_bf16) vec = vec && (((uintptr_t)p_bf16 + 2 * (uintptr_t)head) & 7) == 0;
+  if (!vec) head = n;
+  AdamExLaunch l;
+  l.n = n, l.head = head, l.nvec = (n - head) / 4;
+  l.p = p, l.g = g, l.m = m, l.v = v, l.ema = ema, l.ctl = ctl, l.pb = (bf16*)p_bf16;
+  l.a = AdamExArgs{lr, b1, b2, eps, bc1, bc2_sqrt, wd, decay_mul, ema_decay};
+  l.stream = (hipStream_t)stream;
+  const int wd_mode = decoupled ? 2 : (wd != 0.f ? 1 : 0);
+  if (ctl) adam_ex_pick_wd<true>(l, wd_mode);
+  else adam_ex_pick_wd<false>(l, wd_mode);
+  SMER_CHECK_LAUNCH("smer_adam_ex");
   return SMER_OK;
 }
 

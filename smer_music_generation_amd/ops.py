@@ -1120,6 +1120,25 @@ def adam_guarded(p, g, m, v, p_bf16, ctl, *, lr, b1, b2, eps, step):
          float(b2), float(eps), float(bc1), float(bc2s), _p(ctl), _stream())
 
 
+def adam_ex(p, g, m, v, p_bf16, ctl=None, *, lr, b1, b2, eps, step, weight_decay=0.0, decoupled=True,
+            ema=None, ema_decay=0.0):
+    """adam() / adam_guarded() (ctl given) with weight decay and an EMA of
+    the weights in the same pass (smer_adam_ex).  decoupled: AdamW's
+    p *= 1 - lr * weight_decay before the update, the factor formed in double
+    and rounded to fp32 once as torch does; otherwise torch Adam's coupled
+    g += weight_decay * p (after the clip scale).  ema (flat fp32, the size of
+    p, or None): e += (1 - ema_decay) * (p_new - e)."""
+    import math
+    bc1 = 1.0 - b1 ** step
+    bc2s = math.sqrt(1.0 - b2 ** step)
+    if ema is not None and ema.numel() != p.numel():
+        raise ValueError("adam_ex: ema holds %d elements, p %d" % (ema.numel(), p.numel()))
+    decay_mul = 1.0 - float(lr) * float(weight_decay) if decoupled else 1.0
+    call("smer_adam_ex", p.numel(), _p(p), _p(g), _p(m), _p(v), _p(p_bf16), float(lr), float(b1),
+         float(b2), float(eps), float(bc1), float(bc2s), _p(ctl), float(weight_decay), decay_mul,
+         1 if decoupled else 0, _p(ema), float(ema_decay), _stream())
+
+
 def cast(src, dst):
     assert src.numel() == dst.numel()
     call("smer_cast", dtype_code(src.dtype), dtype_code(dst.dtype), src.numel(), _p(src),

@@ -15,10 +15,14 @@ Adam semantics (`train.py:264`), as one stream of gfx950 kernels:
     produced them, overlapping the remaining backward kernels;
   * Adam on the flat fp32 master buffer also refreshes the bf16 working copy;
   * optional (`clip_norm=`): global-norm gradient clipping and a non-finite
-    step guard, measured and applied on the device with no host round trip.
+    step guard, measured and applied on the device with no host round trip;
+  * optional (`weight_decay=`, `ema_decay=`): AdamW's decoupled or Adam's
+    coupled weight decay and an exponential moving average of the weights,
+    inside the same Adam pass (smer_adam_ex).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 
@@ -162,6 +166,30 @@ def check_clip_norm(value):
     return c
 
 
+def check_ema_decay(value):
+    """`Trainer.ema_decay`: None (no average kept) or a number 0 <= d < 1.
+    Returns None or the float; anything else raises ValueError."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError("ema_decay must be None or a number in [0, 1), got %r" % (value,))
+    d = float(value)
+    if not 0.0 <= d < 1.0:  # also NaN
+        raise ValueError("ema_decay must be in [0, 1), got %r" % (value,))
+    return d
+
+
+def check_weight_decay(value):
+    """`param_groups[0]['weight_decay']` as the step reads it: a finite
+    number >= 0 (torch's own rule).  Returns the float."""
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError("weight_decay must be a number >= 0, got %r" % (value,))
+    w = float(value)
+    if not 0.0 <= w < float("inf"):  # also NaN
+        raise ValueError("weight_decay must be finite and >= 0, got %r" % (value,))
+    return w
+
+
 class FusedAdam(torch.optim.Optimizer):
     """`torch.optim.Adam`'s state and param_groups over the Trainer's flat
     moment buffers (train.py:264 builds `Adam(model.parameters(), lr)`).
@@ -173,13 +201,18 @@ class FusedAdam(torch.optim.Optimizer):
         970-971) resumes here and ours resumes in torch Adam;
       * `param_groups[0]['lr']` is read every step, so
         `ReduceLROnPlateau(trainer.optimizer, ...)` (train.py:663-664, 939)
-        drives the fused step.
-    Per-parameter `exp_avg` / `exp_avg_sq` are views of the flat buffers."""
+        drives the fused step; `weight_decay` and `decoupled_weight_decay`
+        (True: `torch.optim.AdamW`, False: `Adam(weight_decay=)`'s coupled
+        L2) are read every step in the same way, so an AdamW checkpoint
+        resumes here too.
+    Per-parameter `exp_avg` / `exp_avg_sq` are views of the flat buffers.
+    There is one parameter group: every parameter decays alike (no
+    per-parameter exclusion); amsgrad and maximize are not implemented."""
 
-    def __init__(self, model, m, v, lr, betas, eps):
-        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0, amsgrad=False,
+    def __init__(self, model, m, v, lr, betas, eps, weight_decay=0, decoupled_weight_decay=False):
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False,
                         maximize=False, foreach=None, capturable=False, differentiable=False,
-                        fused=None, decoupled_weight_decay=False)
+                        fused=None, decoupled_weight_decay=bool(decoupled_weight_decay))
         super().__init__(list(model.parameters()), defaults)
         self._m, self._v = m, v
         self._views = []
@@ -215,11 +248,15 @@ class FusedAdam(torch.optim.Optimizer):
         if len(groups) != 1 or len(groups[0]["params"]) != len(self._views):
             raise ValueError("optimizer state has %d groups / %s params, expected 1 / %d"
                              % (len(groups), [len(g["params"]) for g in groups], len(self._views)))
+        if groups[0].get("amsgrad") or groups[0].get("maximize"):
+            raise ValueError("FusedAdam implements Adam / AdamW without amsgrad / maximize")
+        if "weight_decay" in groups[0]:
+            check_weight_decay(groups[0]["weight_decay"])
         for k in ("lr", "betas", "eps", "weight_decay", "amsgrad"):
             if k in groups[0]:
                 self.param_groups[0][k] = groups[0][k]
-        if self.param_groups[0].get("weight_decay", 0) or self.param_groups[0].get("amsgrad"):
-            raise ValueError("FusedAdam implements Adam without weight decay / amsgrad (train.py:264)")
+        # a group without the flag was written by torch.optim.Adam: coupled
+        self.param_groups[0]["decoupled_weight_decay"] = bool(groups[0].get("decoupled_weight_decay", False))
         st = state_dict["state"]
         steps = set()
         order = groups[0]["params"]
@@ -248,7 +285,8 @@ class Trainer:
     group when torch.distributed is initialised (world_size > 1)."""
 
     def __init__(self, model, vocab, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, eos_weight=0.8,
-                 group=None, grad_wire_dtype=None, broadcast=True, dp=None, clip_norm=None):
+                 group=None, grad_wire_dtype=None, broadcast=True, dp=None, clip_norm=None,
+                 weight_decay=0.0, decoupled_weight_decay=True, ema_decay=None):
         """clip_norm: None (default) is the plain step.  A number c > 0 is
         the guarded step: the global L2 norm of the whole flat gradient is
         taken on the device, Adam runs on the gradient scaled by
@@ -259,6 +297,17 @@ class Trainer:
         consulted, so `t` advances on a skipped step too.  Settable per step
         like `lr`; see `grad_norm`, `clip_scale`, `skipped_steps`.
         `model.flat_grad()` holds the raw, unscaled gradient after the step.
+        weight_decay, decoupled_weight_decay: torch's two forms, under
+        torch's names in `optimizer.param_groups[0]` (read every step like
+        `lr`).  Decoupled (default, `torch.optim.AdamW`): p *= 1 - lr * wd
+        before the update.  Coupled (`torch.optim.Adam(weight_decay=)`):
+        g += wd * p, after the clip scale.  Every parameter decays alike.
+        ema_decay: None (default) or 0 <= d < 1: `ema`, a flat fp32 copy of
+        the weights, follows them by e += (1 - d) * (p - e) inside the Adam
+        pass of every step that is not skipped; it starts as a copy of the
+        weights when ema_decay first becomes a number.  Settable per step.
+        See `ema_weights`, `ema_state_dict`, `load_ema_state_dict`.  With
+        weight_decay == 0 and ema_decay None the step is the plain one.
         grad_wire_dtype: None / torch.float32 (default, parity) or
         torch.bfloat16 for the DP gradient all-reduce (see GradBucketer).
         broadcast: under DP, copy rank 0's parameters to every rank here.
@@ -267,6 +316,8 @@ class Trainer:
         default: when the process group has more than one rank; True also
         at world size 1 (the real RCCL calls and stream ordering on one GPU)."""
         self._clip_norm = check_clip_norm(clip_norm)
+        ema_decay = check_ema_decay(ema_decay)
+        weight_decay = check_weight_decay(weight_decay)
         self.model = model
         self.vocab = vocab
         dev = model.flat_parameters().device
@@ -277,7 +328,9 @@ class Trainer:
         n = model.flat_parameters().numel()
         self.m = torch.zeros(n, device=dev)
         self.v = torch.zeros(n, device=dev)
-        self.optimizer = FusedAdam(model, self.m, self.v, lr, betas, eps)
+        self.optimizer = FusedAdam(model, self.m, self.v, lr, betas, eps, weight_decay, decoupled_weight_decay)
+        self._ema = None
+        self._ema_swapped = False
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         if dp and not (dist.is_available() and dist.is_initialized()):
@@ -290,6 +343,7 @@ class Trainer:
         self._clip = None  # guarded step's device state, built by its first step
         if self.dp and broadcast:
             broadcast_parameters(model, group)
+        self.ema_decay = ema_decay  # after the broadcast: the average starts from the shared weights
 
     # hyper-parameters live in the optimizer's param group (schedulers edit it)
     @property
@@ -307,6 +361,80 @@ class Trainer:
     @clip_norm.setter
     def clip_norm(self, value):
         self._clip_norm = check_clip_norm(value)
+
+    @property
+    def ema_decay(self):
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, value):
+        self._ema_decay = check_ema_decay(value)
+        if self._ema_decay is not None:
+            self._ema_buffer()
+
+    @property
+    def ema(self):
+        """Flat fp32 average of `model.flat_parameters()` (same layout), None
+        until `ema_decay` has been a number once."""
+        return self._ema
+
+    def _ema_buffer(self):
+        if self._ema is None:
+            self._ema = self.model.flat_parameters().detach().clone()
+        return self._ema
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """The model on the averaged weights: exchanges the contents of the
+        flat parameters and `ema` (so `eval_step`, `validate`, `generation_*`
+        run on the average unchanged) and exchanges them back on exit, also on
+        an exception.  `step` raises inside."""
+        if self._ema is None:
+            raise RuntimeError("ema_weights: no average is kept (ema_decay has never been set)")
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights: already inside the context")
+        self._swap_ema()
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+
+    def _swap_ema(self):
+        flat = self.model.flat_parameters().data
+        with torch.no_grad():
+            tmp = flat.clone()
+            flat.copy_(self._ema)
+            self._ema.copy_(tmp)
+        self._ema_swapped = not self._ema_swapped
+        self.model.engine.mark_params_updated()
+
+    def ema_state_dict(self):
+        """The average in `model.state_dict()`'s format (buffers as the model
+        holds them)."""
+        if self._ema is None:
+            raise RuntimeError("ema_state_dict: no average is kept (ema_decay has never been set)")
+        model = self.model
+        src = model.flat_parameters().detach() if self._ema_swapped else self._ema
+        sd = type(model.state_dict())((k, t.detach().clone()) for k, t in model.state_dict().items())
+        for name, p in model.named_parameters():
+            o = model._offsets[name]
+            sd[name] = src[o: o + p.numel()].view(p.shape).clone()
+        return sd
+
+    def load_ema_state_dict(self, state_dict):
+        """Restore the average from `ema_state_dict()`'s format (a
+        `model.state_dict()`; entries that are not parameters are ignored)."""
+        model = self.model
+        missing = [n for n, _ in model.named_parameters() if n not in state_dict]
+        if missing:
+            raise ValueError("load_ema_state_dict: missing %s" % missing[:5])
+        dst = model.flat_parameters().data if self._ema_swapped else self._ema_buffer()
+        with torch.no_grad():
+            for name, p in model.named_parameters():
+                o = model._offsets[name]
+                dst[o: o + p.numel()].copy_(state_dict[name].reshape(-1).to(dst.device, dst.dtype))
+        if self._ema_swapped:
+            model.engine.mark_params_updated()
 
     # the last guarded step's control block (device views, no sync until
     # read); None until a guarded step has run
@@ -369,6 +497,8 @@ class Trainer:
         """batch: dict of device tensors input/target_in/target_out/
         input_pad_mask/target_pad_mask (dataset.py:856-862).  Returns the
         (local-share) loss as a device scalar; no host sync."""
+        if self._ema_swapped:
+            raise RuntimeError("Trainer.step inside ema_weights(): the model holds the averaged weights")
         model = self.model
         eng = model.engine
         model.train()
@@ -400,10 +530,26 @@ class Trainer:
         g = self.optimizer.param_groups[0]
         flat = model.flat_parameters()
 
-        def adam(a=None, b=None):
+        hp = dict(lr=g["lr"], b1=g["betas"][0], b2=g["betas"][1], eps=g["eps"], step=self.t)
+        wd = check_weight_decay(g.get("weight_decay", 0))
+        ema = self._ema_buffer() if self._ema_decay is not None else None
+        # weight decay or an average: every Adam launch of the step is the
+        # extended kernel, same slices on the same streams; otherwise the
+        # plain step's own calls
+        ex = None
+        if wd != 0 or ema is not None:
+            ex = dict(weight_decay=wd, decoupled=bool(g.get("decoupled_weight_decay", False)),
+                      ema_decay=self._ema_decay if ema is not None else 0.0)
+
+        def adam(a=None, b=None, ctl=None):
             sl = slice(a, b)
-            ops.adam(flat[sl], grad[sl], self.m[sl], self.v[sl], work[sl] if work is not None else None,
-                     lr=g["lr"], b1=g["betas"][0], b2=g["betas"][1], eps=g["eps"], step=self.t)
+            bufs = (flat[sl], grad[sl], self.m[sl], self.v[sl], work[sl] if work is not None else None)
+            if ex is not None:
+                ops.adam_ex(*bufs, ctl, ema=ema[sl] if ema is not None else None, **ex, **hp)
+            elif ctl is not None:
+                ops.adam_guarded(*bufs, ctl, **hp)
+            else:
+                ops.adam(*bufs, **hp)
         stepped = None
         clip = self._clip_state(grad) if self._clip_norm is not None else None
 
@@ -456,8 +602,7 @@ class Trainer:
                 if stepped is None or name not in stepped:
                     sqnorm(name)
             ops.clip_scale(clip.part[:clip.nparts], self._clip_norm, clip.ctl)
-            ops.adam_guarded(flat, grad, self.m, self.v, work, clip.ctl, lr=g["lr"], b1=g["betas"][0],
-                             b2=g["betas"][1], eps=g["eps"], step=self.t)
+            adam(ctl=clip.ctl)
         elif stepped is None:
             adam()
         else:  # the ranges no hook stepped (the embedding), on the main stream

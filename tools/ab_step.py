@@ -1,7 +1,9 @@
 """A/B of one environment switch on the train step: each value in its own
 process (the switches are read once per process), rounds interleaved.
     python tools/ab_step.py c2|c4|c4bf16 ENV_NAME VALUE_A VALUE_B ... [--rounds 2]
-    python tools/ab_step.py c2 ENV "A=1,B=2" "A=0" ...   (several switches per value)"""
+    python tools/ab_step.py c2 ENV "A=1,B=2" "A=0" ...   (several switches per value)
+    python tools/ab_step.py c2adam ARGS "" "weight_decay=0.01" "weight_decay=0.01,ema_decay=0.999" ...
+        (the C2 step of tools/adam_ex_step.py, each value its comma-separated arguments)"""
 import json
 import os
 import subprocess
@@ -23,9 +25,12 @@ for r in range(rounds):
                 if kv:
                     k, x = kv.split("=", 1)
                     env[k] = x
-        else:
+        elif name != "ARGS":
             env[name] = v
-        if cfg == "c2":
+        if cfg == "c2adam":
+            cmd = [sys.executable, os.path.join(ROOT, "tools", "adam_ex_step.py")]
+            cmd += [a for a in v.split(",") if a] if name == "ARGS" else []
+        elif cfg == "c2":
             cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3",
                    "--no-infill", "--no-cpu", "--no-c4", "--no-c5", "--no-roofline"]
         else:

@@ -25,8 +25,11 @@ def tools_available():
 def scan(lib):
     with tempfile.TemporaryDirectory() as d:
         fat = os.path.join(d, "fatbin")
-        subprocess.run(["objcopy", "--dump-section", ".hip_fatbin=" + fat, lib], check=True,
-                       capture_output=True)
+        # with an output file of its own: without one objcopy rewrites `lib` in
+        # place, and a process that has the library loaded (mapped) dies of a
+        # bus error the next time it touches one of its pages
+        subprocess.run(["objcopy", "--dump-section", ".hip_fatbin=" + fat, lib, os.path.join(d, "copy.so")],
+                       check=True, capture_output=True)
         data = open(fat, "rb").read()
         starts = [m.start() for m in re.finditer(re.escape(MAGIC), data)]
         found = {}
