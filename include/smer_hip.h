@@ -70,7 +70,9 @@
  *   smer_adam_ex         that step with weight decay (torch.optim.AdamW's
  *                        decoupled form or Adam(weight_decay=)'s coupled L2)
  *                        and an EMA of the weights, in the same pass
- *   smer_gemm_wgrad_bias nn.Linear weight AND bias gradients in one pass
+ *   smer_adam_groups     smer_adam_ex with torch's parameter groups: lr,
+ *                        betas, eps and weight decay per group, one pass
+ *   smer_gemm_wgrad_biasnn.Linear weight AND bias gradients in one pass
  *                        (autograd of transformer.py:389-469 / model.py:106
  *                        linears, train.py:783)
  *   smer_colsum          bias gradients (autograd of nn.Linear bias)
@@ -766,6 +768,40 @@ int smer_adam_ex(long n, float* p, const float* g, float* m, float* v, void* p_b
                  float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
                  const float* ctl, float wd, float decay_mul, int decoupled, float* ema,
                  float ema_decay, smer_stream_t stream);
+
+/* smer_adam_ex with parameter groups: one pass over p, g, m, v (p_bf16, ema)
+ * in which every element is stepped with the hyper-parameters of its own
+ * group.  Group membership is constant on blocks of 64 elements (every
+ * parameter's slot in the flat buffer is 64-aligned): gmap, in device memory,
+ * holds one byte per block of the whole flat buffer, and block0 is the block
+ * of p[0], so element i of the call belongs to group gmap[block0 + i / 64]
+ * (padding elements of a slot carry their parameter's group; their p, g, m, v
+ * are 0 and stay 0).  `groups` is read by the host and travels to the kernel
+ * by value: ngroups rows, 1..SMER_ADAM_MAX_GROUPS, each smer_adam_ex's scalars
+ * as the caller forms them for that group -- bc1 = 1 - b1^t, bc2_sqrt =
+ * sqrt(1 - b2^t), decay_mul = (float)(1 - (double)lr * wd) when decoupled,
+ * else 1 -- and wd_mode: 0 no decay, 1 coupled (gi += wd * p), 2 decoupled
+ * (p *= decay_mul).  ema_decay and ctl (nullable, smer_clip_scale's block)
+ * are shared by all groups.  An element of group k gets, bit for bit, what
+ * smer_adam_ex writes with group k's arguments (wd_mode 1 there: decoupled ==
+ * 0 && wd != 0; 2: decoupled != 0); ctl[2] != 0 returns before anything is
+ * read.  Slices are whole slots: n % 64 == 0, p, g, m, v, ema 16-B aligned
+ * and p_bf16 8-B aligned.  Elementwise: no atomics, no workspace, and a range
+ * split into several launches gets the same bits.  SMER_ERR_INVALID, before
+ * any launch: a null p/g/m/v/gmap/groups, n < 0, n % 64 != 0, a misaligned
+ * pointer, ngroups outside 1..SMER_ADAM_MAX_GROUPS, a wd, decay_mul or
+ * ema_decay that is not finite, a wd_mode outside 0..2.  n == 0 launches
+ * nothing.  A map byte >= ngroups is the caller's to exclude (the host cannot
+ * read the map). */
+#define SMER_ADAM_MAX_GROUPS 16
+typedef struct smer_adam_group {
+  float lr, b1, b2, eps, bc1, bc2_sqrt, wd, decay_mul;
+  int wd_mode;
+} smer_adam_group;
+int smer_adam_groups(long n, float* p, const float* g, float* m, float* v, void* p_bf16,
+                     const float* ctl, const uint8_t* gmap, long block0,
+                     const smer_adam_group* groups, int ngroups, float* ema, float ema_decay,
+                     smer_stream_t stream);
 
 int smer_cast(int src_dtype, int dst_dtype, long n, const void* src, void* dst,
               smer_stream_t stream);

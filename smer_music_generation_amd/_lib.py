@@ -154,6 +154,7 @@ SIGNATURES = {
                                   c_float, P, P]),
     "smer_adam_ex": (c_int, [c_long, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float,
                              c_float, P, c_float, c_float, c_int, P, c_float, P]),
+    "smer_adam_groups": (c_int, [c_long, P, P, P, P, P, P, P, c_long, P, c_int, P, c_float, P]),
     "smer_cast":(c_int, [c_int, c_int, c_long, P, P, P]),
     "smer_cast2d": (c_int, [c_int, c_int, c_int, c_int, P, c_long, P, c_long, P]),
     "smer_colsum_workspace": (c_size, [c_int, c_int]),

@@ -220,6 +220,94 @@ __global__ __launch_bounds__(256) void adam_ex_kernel(long n, long head, long nv
   }
 }
 
+// smer_adam_groups: smer_adam_ex with the hyper-parameters of a parameter
+// group per element.  Group membership is constant on 64-element blocks (a
+// parameter's slot is 64-aligned), gmap holds one byte per block of the flat
+// buffer and block0 is the block of this slice's first element.  The table
+// travels by value in the kernel arguments.
+//
+// A lane owns one 16-B vector, so 16 lanes share a block and a wave iteration
+// covers four.  The wave runs a waterfall over the group ids its lanes hold:
+// readfirstlane picks one, the lanes that hold it update their vector through
+// adam_ex_elem with that group's row -- read from the kernel arguments with a
+// wave-uniform index, so it stays in scalar registers, never scratch -- and
+// the loop ends when no lane is left: one pass wherever a wave sees one group,
+// four at most.  The arithmetic is adam_ex_elem's and nothing else, so an
+// element of group k gets the bits smer_adam_ex writes with k's arguments
+// (tests/test_param_groups_gpu.py).  n % 64 == 0 and 16-B aligned bases (8-B
+// for the bf16 copy): there is no scalar head or tail.  One lane per element,
+// no atomics, no workspace; a range split at a block boundary gets the same
+// bits.
+struct AdamGroupTable {
+  smer_adam_group row[SMER_ADAM_MAX_GROUPS];
+};
+
+template <bool GUARDED, int WD, bool EMA>
+__device__ __forceinline__ void adam_groups_vec(const AdamExArgs& a, float gs, f32x4& P, const f32x4& G,
+                                                f32x4& M, f32x4& V, f32x4& E) {
+  const float step = a.lr / a.bc1;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float pj = P[j], mj = M[j], vj = V[j], ej = E[j];
+    adam_ex_elem<GUARDED, WD, EMA>(a, step, gs, pj, G[j], mj, vj, ej);
+    P[j] = pj, M[j] = mj, V[j] = vj, E[j] = ej;
+  }
+}
+
+template <bool GUARDED, bool EMA>
+__global__ __launch_bounds__(256) void adam_groups_kernel(long nvec, float* __restrict__ p,
+                                                          const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, bf16* __restrict__ pb,
+                                                          float* __restrict__ ema, const float* __restrict__ ctl,
+                                                          const uint8_t* __restrict__ gmap, long block0,
+                                                          float ema_decay, AdamGroupTable tab) {
+  float gs = 1.f;
+  if constexpr (GUARDED) {
+    if (ctl[2] != 0.f) return;
+    gs = ctl[1];
+  }
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  const long stride = (long)gridDim.x * 256;
+  for (long k = t; k < nvec; k += stride) {
+    const long i = 4 * k;
+    const int gid = gmap[block0 + (k >> 4)];
+    f32x4 P = *reinterpret_cast<const f32x4*>(p + i);
+    const f32x4 G = *reinterpret_cast<const f32x4*>(g + i);
+    f32x4 M = *reinterpret_cast<const f32x4*>(m + i);
+    f32x4 V = *reinterpret_cast<const f32x4*>(v + i);
+    f32x4 E = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (EMA) E = *reinterpret_cast<const f32x4*>(ema + i);
+    bool todo = true;
+    while (todo) {
+      const int cur = __builtin_amdgcn_readfirstlane(gid);
+      // the table index as a scalar the compiler cannot equate with gid: under
+      // gid == cur it would index with the per-lane gid instead (vector loads
+      // of the row).  The mask keeps the read inside the table whatever the
+      // map holds.
+      int row = cur & (SMER_ADAM_MAX_GROUPS - 1);
+      asm volatile("" : "+s"(row));
+      if (gid == cur) {
+        const smer_adam_group& r = tab.row[row];
+        const AdamExArgs a{r.lr, r.b1, r.b2, r.eps, r.bc1, r.bc2_sqrt, r.wd, r.decay_mul, ema_decay};
+        if (r.wd_mode == 0) adam_groups_vec<GUARDED, 0, EMA>(a, gs, P, G, M, V, E);
+        else if (r.wd_mode == 1) adam_groups_vec<GUARDED, 1, EMA>(a, gs, P, G, M, V, E);
+        else adam_groups_vec<GUARDED, 2, EMA>(a, gs, P, G, M, V, E);
+        todo = false;
+      }
+    }
+    *reinterpret_cast<f32x4*>(m + i) = M;
+    *reinterpret_cast<f32x4*>(v + i) = V;
+    *reinterpret_cast<f32x4*>(p + i) = P;
+    if (pb) {
+      bf16x4 B;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) B[j] = (bf16)P[j];
+      *reinterpret_cast<bf16x4*>(pb + i) = B;
+    }
+    if constexpr (EMA) *reinterpret_cast<f32x4*>(ema + i) = E;
+  }
+}
+
 // Global gradient norm, stage 1: part[c] = sum of squares of chunk c
 // (GN_CH floats) of a range.  256 lanes x 4 iterations x 4 independent 16-B
 // loads; lane accumulator u takes load u of every iteration (16 fmas in
@@ -632,6 +720,48 @@ extern "C" int smer_adam_ex(long n, float* p, const float* g, float* m, float* v
   if (ctl) adam_ex_pick_wd<true>(l, wd_mode);
   else adam_ex_pick_wd<false>(l, wd_mode);
   SMER_CHECK_LAUNCH("smer_adam_ex");
+  return SMER_OK;
+}
+
+extern "C" int smer_adam_groups(long n, float* p, const float* g, float* m, float* v, void* p_bf16,
+                                const float* ctl, const uint8_t* gmap, long block0,
+                                const smer_adam_group* groups, int ngroups, float* ema, float ema_decay,
+                                smer_stream_t stream) {
+  SMER_REQUIRE(p && g && m && v && gmap && groups, "smer_adam_groups: null pointer");
+  SMER_REQUIRE(n >= 0 && block0 >= 0, "smer_adam_groups: n < 0 or block0 < 0");
+  SMER_REQUIRE(n % 64 == 0, "smer_adam_groups: n must be a multiple of 64 (whole parameter slots)");
+  SMER_REQUIRE(ngroups >= 1 && ngroups <= SMER_ADAM_MAX_GROUPS,
+               "smer_adam_groups: ngroups must be 1..SMER_ADAM_MAX_GROUPS");
+  const uintptr_t a16 = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema;
+  SMER_REQUIRE((a16 & 15) == 0 && ((uintptr_t)p_bf16 & 7) == 0,
+               "smer_adam_groups: p, g, m, v, ema must be 16-B aligned, p_bf16 8-B aligned");
+  SMER_REQUIRE(__builtin_isfinite(ema_decay), "smer_adam_groups: wd, decay_mul and ema_decay must be finite");
+  AdamGroupTable tab = {};
+  for (int k = 0; k < ngroups; ++k) {
+    SMER_REQUIRE(__builtin_isfinite(groups[k].wd) && __builtin_isfinite(groups[k].decay_mul),
+                 "smer_adam_groups: wd, decay_mul and ema_decay must be finite");
+    SMER_REQUIRE(groups[k].wd_mode >= 0 && groups[k].wd_mode <= 2, "smer_adam_groups: wd_mode must be 0, 1 or 2");
+    tab.row[k] = groups[k];
+  }
+  if (n == 0) return SMER_OK;
+  const long nvec = n / 4;
+  long blocks = (nvec + 255) / 256;  // adam_ex_launch's rule
+  if (blocks > 8192) blocks = 8192;
+  bf16* pb = (bf16*)p_bf16;
+  const dim3 grid((unsigned)blocks), wg(256);
+  hipStream_t s = (hipStream_t)stream;
+#define SMER_ADAM_GROUPS_LAUNCH(GUARDED, EMA)                                                                 \
+  hipLaunchKernelGGL((adam_groups_kernel<GUARDED, EMA>), grid, wg, 0, s, nvec, p, g, m, v, pb, ema, ctl, gmap, \
+                     block0, ema_decay, tab)
+  if (ctl) {
+    if (ema) SMER_ADAM_GROUPS_LAUNCH(true, true);
+    else SMER_ADAM_GROUPS_LAUNCH(true, false);
+  } else {
+    if (ema) SMER_ADAM_GROUPS_LAUNCH(false, true);
+    else SMER_ADAM_GROUPS_LAUNCH(false, false);
+  }
+#undef SMER_ADAM_GROUPS_LAUNCH
+  SMER_CHECK_LAUNCH("smer_adam_groups");
   return SMER_OK;
 }
 

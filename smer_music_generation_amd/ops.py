@@ -1139,6 +1139,56 @@ def adam_ex(p, g, m, v, p_bf16, ctl=None, *, lr, b1, b2, eps, step, weight_decay
          1 if decoupled else 0, _p(ema), float(ema_decay), _stream())
 
 
+ADAM_MAX_GROUPS = 16  # include/smer_hip.h SMER_ADAM_MAX_GROUPS
+
+
+def adam_group_rows(groups, step):
+    """The smer_adam_group rows of `groups` at `step` (a numpy record array):
+    per group the scalars adam_ex forms, in double as it forms them -- bc1,
+    bc2s, decay_mul = 1 - lr * weight_decay when decoupled, else 1 -- and
+    wd_mode as smer_adam_ex picks it (2 decoupled, 1 coupled with a non-zero
+    fp32 weight decay, 0 none)."""
+    import math
+
+    import numpy as np
+    dt = np.dtype([(k, "<f4") for k in ("lr", "b1", "b2", "eps", "bc1", "bc2_sqrt", "wd", "decay_mul")]
+                  + [("wd_mode", "<i4")])
+    if not 1 <= len(groups) <= ADAM_MAX_GROUPS:
+        raise ValueError("adam_groups: %d groups, 1..%d supported" % (len(groups), ADAM_MAX_GROUPS))
+    rows = np.zeros(len(groups), dtype=dt)
+    for i, g in enumerate(groups):
+        lr, (b1, b2), wd = float(g["lr"]), g["betas"], float(g.get("weight_decay", 0.0))
+        decoupled = bool(g.get("decoupled_weight_decay", False))
+        decay_mul = 1.0 - lr * wd if decoupled else 1.0
+        mode = 2 if decoupled else (1 if np.float32(wd) != 0 else 0)
+        rows[i] = (lr, b1, b2, g["eps"], 1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step), wd, decay_mul, mode)
+    return rows
+
+
+def adam_groups(p, g, m, v, p_bf16, ctl, gmap, block0, groups, *, step, ema=None, ema_decay=0.0):
+    """adam_ex() with parameter groups, one launch (smer_adam_groups): element
+    i of the slice is stepped with the values of group gmap[block0 + i // 64].
+    gmap: device uint8, one byte per 64-element block of the whole flat
+    buffer, every byte < len(groups) (whoever builds the map checks that: it
+    is not read back here); block0: the block of p[0].  groups: dicts with lr,
+    betas, eps, weight_decay, decoupled_weight_decay, or the rows
+    adam_group_rows made of them for this step.  ctl (or None), ema and
+    ema_decay as in adam_ex, shared by all groups.  The slice is whole slots:
+    a multiple of 64 elements on 16-B aligned bases."""
+    import numpy as np
+    rows = groups if isinstance(groups, np.ndarray) else adam_group_rows(groups, step)
+    n = p.numel()
+    if ema is not None and ema.numel() != n:
+        raise ValueError("adam_groups: ema holds %d elements, p %d" % (ema.numel(), n))
+    if gmap.dtype != torch.uint8 or not gmap.is_contiguous():
+        raise TypeError("adam_groups: gmap must be a contiguous uint8 tensor")
+    if block0 < 0 or n % 64 or gmap.numel() < block0 + n // 64:
+        raise ValueError("adam_groups: %d elements from block %d do not fit a map of %d blocks of 64"
+                         % (n, block0, gmap.numel()))
+    call("smer_adam_groups", n, _p(p), _p(g), _p(m), _p(v), _p(p_bf16), _p(ctl), _p(gmap), int(block0),
+         rows.ctypes.data, len(rows), _p(ema), float(ema_decay), _stream())
+
+
 def cast(src, dst):
     assert src.numel() == dst.numel()
     call("smer_cast", dtype_code(src.dtype), dtype_code(dst.dtype), src.numel(), _p(src),

@@ -18,7 +18,10 @@ Adam semantics (`train.py:264`), as one stream of gfx950 kernels:
     step guard, measured and applied on the device with no host round trip;
   * optional (`weight_decay=`, `ema_decay=`): AdamW's decoupled or Adam's
     coupled weight decay and an exponential moving average of the weights,
-    inside the same Adam pass (smer_adam_ex).
+    inside the same Adam pass (smer_adam_ex);
+  * optional (`param_groups=`): torch's parameter groups -- lr, betas, eps
+    and weight decay per group -- still one Adam pass per slice
+    (smer_adam_groups reads each 64-element block's group from a byte map).
 """
 from __future__ import annotations
 
@@ -190,6 +193,114 @@ def check_weight_decay(value):
     return w
 
 
+MAX_PARAM_GROUPS = ops.ADAM_MAX_GROUPS
+_GROUP_KEYS = ("lr", "betas", "eps", "weight_decay", "decoupled_weight_decay")
+# torch's own group keys that change nothing here (amsgrad and maximize must be off)
+_GROUP_IGNORED = ("amsgrad", "maximize", "foreach", "capturable", "differentiable", "fused")
+
+
+def _check_nonneg(name, value):
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError("%s must be a number >= 0, got %r" % (name, value))
+    x = float(value)
+    if not 0.0 <= x < float("inf"):  # also NaN
+        raise ValueError("%s must be finite and >= 0, got %r" % (name, value))
+    return x
+
+
+def check_group_values(g):
+    """lr, betas, eps, weight_decay, amsgrad and maximize of one parameter
+    group as the step reads them; ValueError on anything it cannot run."""
+    if g.get("amsgrad") or g.get("maximize"):
+        raise ValueError("FusedAdam implements Adam / AdamW without amsgrad / maximize")
+    if "lr" in g:
+        _check_nonneg("lr", g["lr"])
+    if "eps" in g:
+        _check_nonneg("eps", g["eps"])
+    if "weight_decay" in g:
+        check_weight_decay(g["weight_decay"])
+    if "betas" in g:
+        try:
+            b1, b2 = (float(b) for b in g["betas"])
+        except (TypeError, ValueError):
+            raise ValueError("betas must be two numbers in [0, 1), got %r" % (g["betas"],)) from None
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):  # also NaN
+            raise ValueError("betas must be in [0, 1), got %r" % (g["betas"],))
+
+
+def resolve_param_groups(model, param_groups, defaults):
+    """`Trainer(param_groups=)` -> [(parameter names, values)]: torch-shaped
+    dicts whose "params" hold parameter names as `model.named_parameters()`
+    gives them, fnmatch patterns over those names, or the parameters
+    themselves; keys a group leaves out come from `defaults`.  The names of a
+    group are in named_parameters() order.  ValueError: no group or more than
+    MAX_PARAM_GROUPS, a parameter in two groups or in none, a name or pattern
+    that matches nothing, a tensor that is no parameter of the model, an
+    unknown key, amsgrad / maximize, or a value check_group_values refuses."""
+    import fnmatch
+    if isinstance(param_groups, dict) or not isinstance(param_groups, (list, tuple)):
+        raise ValueError("param_groups must be a list of dicts, got %r" % type(param_groups).__name__)
+    if not 1 <= len(param_groups) <= MAX_PARAM_GROUPS:
+        raise ValueError("param_groups: %d groups, 1..%d supported" % (len(param_groups), MAX_PARAM_GROUPS))
+    named = list(model.named_parameters())
+    names = [n for n, _ in named]
+    by_id = {id(p): n for n, p in named}
+    known = set(names)
+    owner, out = {}, []
+    for gi, g in enumerate(param_groups):
+        if not isinstance(g, dict) or "params" not in g:
+            raise ValueError("param_groups[%d] must be a dict with 'params'" % gi)
+        unknown = [k for k in g if k != "params" and k not in _GROUP_KEYS and k not in _GROUP_IGNORED]
+        if unknown:
+            raise ValueError("param_groups[%d]: unknown keys %s" % (gi, unknown))
+        check_group_values(g)
+        entries = g["params"]
+        if isinstance(entries, (str, torch.Tensor)):
+            entries = [entries]
+        mine = set()
+        for e in entries:
+            if isinstance(e, str):
+                hit = [e] if e in known else fnmatch.filter(names, e)
+                if not hit:
+                    raise ValueError("param_groups[%d]: %r matches no parameter" % (gi, e))
+            elif isinstance(e, torch.Tensor):
+                if id(e) not in by_id:
+                    raise ValueError("param_groups[%d]: a tensor that is no parameter of the model" % gi)
+                hit = [by_id[id(e)]]
+            else:
+                raise ValueError("param_groups[%d]: params hold names, patterns or parameters, got %r"
+                                 % (gi, type(e).__name__))
+            mine.update(hit)
+        for n in mine:
+            if n in owner:
+                raise ValueError("parameter %s is in param_groups[%d] and [%d]" % (n, owner[n], gi))
+            owner[n] = gi
+        vals = dict(defaults)
+        vals.update({k: g[k] for k in _GROUP_KEYS if k in g})
+        vals["betas"] = tuple(float(b) for b in vals["betas"])
+        vals["decoupled_weight_decay"] = bool(vals["decoupled_weight_decay"])
+        out.append(([n for n in names if n in mine], vals))
+    missing = [n for n in names if n not in owner]
+    if missing:
+        raise ValueError("%d parameters are in no group: %s" % (len(missing), missing[:5]))
+    return out
+
+
+def decay_groups(model, weight_decay, no_decay=("*bias", "*norm*", "embedding.*")):
+    """The usual two groups for `Trainer(param_groups=)`: the weight matrices
+    with `weight_decay`, and everything whose name matches a `no_decay`
+    pattern -- by default every bias (nn.MultiheadAttention's `in_proj_bias`
+    included, which "*.bias" would miss), every LayerNorm gain and bias and
+    the embedding -- with none.  Parameter names, in named_parameters() order."""
+    import fnmatch
+    names = [n for n, _ in model.named_parameters()]
+    skip = [n for n in names if any(fnmatch.fnmatch(n, pat) for pat in no_decay)]
+    keep = [n for n in names if n not in set(skip)]
+    if not keep or not skip:
+        raise ValueError("decay_groups: the patterns %r leave a group empty" % (tuple(no_decay),))
+    return [{"params": keep, "weight_decay": weight_decay}, {"params": skip, "weight_decay": 0.0}]
+
+
 class FusedAdam(torch.optim.Optimizer):
     """`torch.optim.Adam`'s state and param_groups over the Trainer's flat
     moment buffers (train.py:264 builds `Adam(model.parameters(), lr)`).
@@ -199,27 +310,43 @@ class FusedAdam(torch.optim.Optimizer):
       * `state_dict()` / `load_state_dict()` in torch Adam's format, so a
         reference checkpoint's `optimizer_state_dict` (train.py:266-303,
         970-971) resumes here and ours resumes in torch Adam;
-      * `param_groups[0]['lr']` is read every step, so
+      * every group's `lr` is read every step, so
         `ReduceLROnPlateau(trainer.optimizer, ...)` (train.py:663-664, 939)
-        drives the fused step; `weight_decay` and `decoupled_weight_decay`
-        (True: `torch.optim.AdamW`, False: `Adam(weight_decay=)`'s coupled
-        L2) are read every step in the same way, so an AdamW checkpoint
-        resumes here too.
+        and `LambdaLR` drive the fused step; `betas`, `eps`, `weight_decay`
+        and `decoupled_weight_decay` (True: `torch.optim.AdamW`, False:
+        `Adam(weight_decay=)`'s coupled L2) are read every step in the same
+        way, so an AdamW checkpoint resumes here too.
     Per-parameter `exp_avg` / `exp_avg_sq` are views of the flat buffers.
-    There is one parameter group: every parameter decays alike (no
-    per-parameter exclusion); amsgrad and maximize are not implemented."""
+    `groups` (resolve_param_groups' result; None: one group of every
+    parameter) gives torch's parameter groups, at most MAX_PARAM_GROUPS, each
+    with its parameters in named_parameters() order; parameter ids in the
+    state dict are sequential in group order, as torch numbers them.
+    `group_map` (uint8, one byte per 64-element block of the flat buffer, on
+    its device) holds the group of every block, padding of a slot included.
+    All groups share one `step`; amsgrad and maximize are not implemented."""
 
-    def __init__(self, model, m, v, lr, betas, eps, weight_decay=0, decoupled_weight_decay=False):
+    def __init__(self, model, m, v, lr, betas, eps, weight_decay=0, decoupled_weight_decay=False, groups=None):
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False,
                         maximize=False, foreach=None, capturable=False, differentiable=False,
                         fused=None, decoupled_weight_decay=bool(decoupled_weight_decay))
-        super().__init__(list(model.parameters()), defaults)
+        params = dict(model.named_parameters())
+        if groups is None:
+            groups = [(list(params), {})]
+        super().__init__([dict(vals, params=[params[n] for n in names]) for names, vals in groups], defaults)
         self._m, self._v = m, v
-        self._views = []
-        for name, p in model.named_parameters():
-            o = model._offsets[name]
-            n = p.numel()
-            self._views.append((p, m[o: o + n].view(p.shape), v[o: o + n].view(p.shape)))
+        self._views = []  # in group order: the state dict's parameter ids
+        flat = model.flat_parameters()
+        gmap = np.full(flat.numel() // 64, 255, dtype=np.uint8)
+        for gi, (names, _) in enumerate(groups):
+            for name in names:
+                p = params[name]
+                o = model._offsets[name]
+                n = p.numel()
+                self._views.append((p, m[o: o + n].view(p.shape), v[o: o + n].view(p.shape)))
+                gmap[o // 64: (o + n + 63) // 64] = gi
+        if gmap.size and int(gmap.max()) >= len(groups):
+            raise RuntimeError("FusedAdam: a block of the flat buffer belongs to no parameter")
+        self.group_map = torch.from_numpy(gmap).to(flat.device)
         self.t = 0
 
     def step(self, closure=None):
@@ -236,41 +363,46 @@ class FusedAdam(torch.optim.Optimizer):
             for i, (_, ma, va) in enumerate(self._views):
                 state[i] = {"step": torch.tensor(float(self.t)), "exp_avg": ma.detach().clone(),
                             "exp_avg_sq": va.detach().clone()}
-        groups = []
+        groups, first = [], 0
         for g in self.param_groups:
             d = {k: v for k, v in g.items() if k != "params"}
-            d["params"] = list(range(len(self._views)))
+            d["params"] = list(range(first, first + len(g["params"])))
+            first += len(g["params"])
             groups.append(d)
         return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, state_dict):
         groups = state_dict["param_groups"]
-        if len(groups) != 1 or len(groups[0]["params"]) != len(self._views):
-            raise ValueError("optimizer state has %d groups / %s params, expected 1 / %d"
-                             % (len(groups), [len(g["params"]) for g in groups], len(self._views)))
-        if groups[0].get("amsgrad") or groups[0].get("maximize"):
-            raise ValueError("FusedAdam implements Adam / AdamW without amsgrad / maximize")
-        if "weight_decay" in groups[0]:
-            check_weight_decay(groups[0]["weight_decay"])
-        for k in ("lr", "betas", "eps", "weight_decay", "amsgrad"):
-            if k in groups[0]:
-                self.param_groups[0][k] = groups[0][k]
-        # a group without the flag was written by torch.optim.Adam: coupled
-        self.param_groups[0]["decoupled_weight_decay"] = bool(groups[0].get("decoupled_weight_decay", False))
+        ours = [len(g["params"]) for g in self.param_groups]
+        if [len(g["params"]) for g in groups] != ours:
+            raise ValueError("optimizer state has %d groups / %s params, expected %d / %s"
+                             % (len(groups), [len(g["params"]) for g in groups], len(ours), ours))
+        for g in groups:  # before anything is overwritten
+            if g.get("amsgrad") or g.get("maximize"):
+                raise ValueError("FusedAdam implements Adam / AdamW without amsgrad / maximize")
+            if "weight_decay" in g:
+                check_weight_decay(g["weight_decay"])
         st = state_dict["state"]
         steps = set()
-        order = groups[0]["params"]
-        for slot, pid in enumerate(order):
-            s = st.get(pid)
-            _, ma, va = self._views[slot]
-            if s is None:
-                ma.zero_()
-                va.zero_()
-                steps.add(0)
-                continue
-            ma.copy_(s["exp_avg"].reshape(ma.shape).to(ma.device, ma.dtype))
-            va.copy_(s["exp_avg_sq"].reshape(va.shape).to(va.device, va.dtype))
-            steps.add(int(float(s["step"])))
+        slot = 0
+        for mine, g in zip(self.param_groups, groups):
+            for k in ("lr", "betas", "eps", "weight_decay", "amsgrad"):
+                if k in g:
+                    mine[k] = g[k]
+            # a group without the flag was written by torch.optim.Adam: coupled
+            mine["decoupled_weight_decay"] = bool(g.get("decoupled_weight_decay", False))
+            for pid in g["params"]:
+                s = st.get(pid)
+                _, ma, va = self._views[slot]
+                slot += 1
+                if s is None:
+                    ma.zero_()
+                    va.zero_()
+                    steps.add(0)
+                    continue
+                ma.copy_(s["exp_avg"].reshape(ma.shape).to(ma.device, ma.dtype))
+                va.copy_(s["exp_avg_sq"].reshape(va.shape).to(va.device, va.dtype))
+                steps.add(int(float(s["step"])))
         if len(steps) > 1:
             raise ValueError("per-parameter Adam steps differ %s; the fused step shares one" % steps)
         self.t = steps.pop() if steps else 0
@@ -286,7 +418,7 @@ class Trainer:
 
     def __init__(self, model, vocab, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, eos_weight=0.8,
                  group=None, grad_wire_dtype=None, broadcast=True, dp=None, clip_norm=None,
-                 weight_decay=0.0, decoupled_weight_decay=True, ema_decay=None):
+                 weight_decay=0.0, decoupled_weight_decay=True, ema_decay=None, param_groups=None):
         """clip_norm: None (default) is the plain step.  A number c > 0 is
         the guarded step: the global L2 norm of the whole flat gradient is
         taken on the device, Adam runs on the gradient scaled by
@@ -301,7 +433,24 @@ class Trainer:
         torch's names in `optimizer.param_groups[0]` (read every step like
         `lr`).  Decoupled (default, `torch.optim.AdamW`): p *= 1 - lr * wd
         before the update.  Coupled (`torch.optim.Adam(weight_decay=)`):
-        g += wd * p, after the clip scale.  Every parameter decays alike.
+        g += wd * p, after the clip scale.  Without param_groups every
+        parameter decays alike.
+        param_groups: None (default) is one group of every parameter, the
+        step as it was.  Otherwise torch's list of dicts, at most
+        MAX_PARAM_GROUPS: {"params": [...], "lr": ..., "betas": ..., "eps":
+        ..., "weight_decay": ..., "decoupled_weight_decay": ...}, where
+        params holds parameter names as `model.named_parameters()` gives
+        them, fnmatch patterns over those names, or the parameters
+        themselves, and a key left out takes this constructor's argument.
+        Every parameter belongs to exactly one group (`decay_groups` builds
+        the usual two).  The groups live in `optimizer.param_groups` and are
+        read every step; with more than one, every Adam launch of the step is
+        smer_adam_groups on the same slices and streams, which steps each
+        element with its own group's values (`group_map`).  clip_norm stays
+        global (one norm, one scale) and ema_decay is shared.  All groups
+        share one step count, and lr=0 is no freeze: such a group keeps its
+        weights' bits while its moments go on (as in torch) and its
+        gradients are still computed.
         ema_decay: None (default) or 0 <= d < 1: `ema`, a flat fp32 copy of
         the weights, follows them by e += (1 - d) * (p - e) inside the Adam
         pass of every step that is not skipped; it starts as a copy of the
@@ -318,6 +467,11 @@ class Trainer:
         self._clip_norm = check_clip_norm(clip_norm)
         ema_decay = check_ema_decay(ema_decay)
         weight_decay = check_weight_decay(weight_decay)
+        groups = None
+        if param_groups is not None:  # checked before anything is allocated
+            groups = resolve_param_groups(model, param_groups, dict(
+                lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
+                decoupled_weight_decay=bool(decoupled_weight_decay)))
         self.model = model
         self.vocab = vocab
         dev = model.flat_parameters().device
@@ -328,7 +482,8 @@ class Trainer:
         n = model.flat_parameters().numel()
         self.m = torch.zeros(n, device=dev)
         self.v = torch.zeros(n, device=dev)
-        self.optimizer = FusedAdam(model, self.m, self.v, lr, betas, eps, weight_decay, decoupled_weight_decay)
+        self.optimizer = FusedAdam(model, self.m, self.v, lr, betas, eps, weight_decay, decoupled_weight_decay,
+                                   groups=groups)
         self._ema = None
         self._ema_swapped = False
         self.group = group
@@ -345,14 +500,25 @@ class Trainer:
             broadcast_parameters(model, group)
         self.ema_decay = ema_decay  # after the broadcast: the average starts from the shared weights
 
-    # hyper-parameters live in the optimizer's param group (schedulers edit it)
+    # hyper-parameters live in the optimizer's param groups (schedulers edit them)
     @property
     def lr(self):
+        """Group 0's learning rate.  Setting it writes the value to every
+        group: per-group ratios are kept only by editing
+        `optimizer.param_groups[i]["lr"]` or by a scheduler on `optimizer`."""
         return self.optimizer.param_groups[0]["lr"]
 
     @lr.setter
     def lr(self, value):
-        self.optimizer.param_groups[0]["lr"] = float(value)
+        for g in self.optimizer.param_groups:
+            g["lr"] = float(value)
+
+    @property
+    def group_map(self):
+        """uint8, one byte per 64-element block of the flat parameter buffer:
+        the index in `optimizer.param_groups` of the parameter whose slot
+        holds the block (padding included)."""
+        return self.optimizer.group_map
 
     @property
     def clip_norm(self):
@@ -527,7 +693,8 @@ class Trainer:
         bucketer = None
         self.t += 1
         work = eng._bf16 if eng.act_dtype() == torch.bfloat16 and eng._bf16 is not None else None
-        g = self.optimizer.param_groups[0]
+        groups = self.optimizer.param_groups
+        g = groups[0]
         flat = model.flat_parameters()
 
         hp = dict(lr=g["lr"], b1=g["betas"][0], b2=g["betas"][1], eps=g["eps"], step=self.t)
@@ -541,10 +708,23 @@ class Trainer:
             ex = dict(weight_decay=wd, decoupled=bool(g.get("decoupled_weight_decay", False)),
                       ema_decay=self._ema_decay if ema is not None else 0.0)
 
+        # more than one parameter group: every Adam launch of the step is the
+        # grouped kernel instead, same slices on the same streams
+        rows = None
+        if len(groups) > 1:
+            for gr in groups:
+                check_weight_decay(gr.get("weight_decay", 0))
+            rows = ops.adam_group_rows(groups, self.t)
+            gmap = self.optimizer.group_map
+
         def adam(a=None, b=None, ctl=None):
             sl = slice(a, b)
             bufs = (flat[sl], grad[sl], self.m[sl], self.v[sl], work[sl] if work is not None else None)
-            if ex is not None:
+            if rows is not None:
+                ops.adam_groups(*bufs, ctl, gmap, (a or 0) // 64, rows, step=self.t,
+                                ema=ema[sl] if ema is not None else None,
+                                ema_decay=self._ema_decay if ema is not None else 0.0)
+            elif ex is not None:
                 ops.adam_ex(*bufs, ctl, ema=ema[sl] if ema is not None else None, **ex, **hp)
             elif ctl is not None:
                 ops.adam_guarded(*bufs, ctl, **hp)
