@@ -63,6 +63,9 @@
  *                        (model.py:91-92,124-125) and its scatter backward
  *   smer_wce_*           the 7-12 weighted cross-entropy criteria fused into
  *                        one pass (train.py:555-642,726-780)
+ *   smer_wce_fwd_bwd_ex  the same criteria built with label_smoothing=
+ *                        (torch's keyword on the constructors of
+ *                        train.py:555-642), plus the plain term per row
  *   smer_adam            torch.optim.Adam step (train.py:264,786)
  *   smer_grad_sqnorm_*, smer_clip_scale, smer_adam_guarded: global-norm
  *                        gradient clipping and the non-finite step guard
@@ -703,6 +706,24 @@ int smer_wce_denom(int n, const int64_t* y, const float* ce_all, float* denom,
 int smer_wce_fwd_bwd(int dtype, int R, int V, const float* logits, long ldl, const int64_t* y,
                      const float* w, const float* denom, float* row_loss, float* loss_out,
                      void* dlogits, long ldd, float grad_scale, smer_stream_t stream);
+/* smer_wce_fwd_bwd with torch's label_smoothing = ls on every criterion
+ * (CrossEntropyLoss(..., label_smoothing=ls) at train.py:555-642), 0 <= ls < 1
+ * (anything else, NaN included: SMER_ERR_INVALID).  With p = softmax(x_r),
+ * W = sum_c w[c] and V the class count, a row with y_r != 0 gets
+ *   l_r = (1-ls) * n_r + ls/V * sum_c w[c] * (logsumexp(x_r) - x_r[c]),
+ *   n_r = w[y_r] * (logsumexp(x_r) - x_r[y_r]),
+ *   dlogits_r[c] = grad_scale/denom * ((1-ls) * w[y_r] * (p[c] - [c == y_r])
+ *                                      + ls/V * (W * p[c] - w[c]));
+ * a row with y_r == 0 gets l_r = n_r = 0 and a zero gradient.  A target with
+ * w[y_r] == 0 keeps the smoothing term, as in torch.  row_nll (nullable)
+ * receives n_r, the plain term.  loss_out = sum_r l_r / denom.  ls == 0
+ * writes smer_wce_fwd_bwd's bits (row_nll = row_loss).  x_r[c] = -inf with
+ * ls > 0 makes l_r inf (w[c] > 0) or NaN (w[c] == 0: 0 * inf, as in torch),
+ * in that row alone.  Columns >= V of dlogits are not written. */
+int smer_wce_fwd_bwd_ex(int dtype, int R, int V, const float* logits, long ldl, const int64_t* y,
+                        const float* w, const float* denom, float* row_loss, float* loss_out,
+                        void* dlogits, long ldd, float grad_scale, float label_smoothing,
+                        float* row_nll, smer_stream_t stream);
 
 /* torch.optim.Adam step on flat fp32 buffers; p_bf16 (nullable) receives
  * the bf16 working copy.  bc1 = 1-b1^t, bc2_sqrt = sqrt(1-b2^t). */

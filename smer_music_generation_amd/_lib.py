@@ -145,6 +145,8 @@ SIGNATURES = {
     "smer_wce_denom": (c_int, [c_int, P, P, P, P]),
     "smer_wce_fwd_bwd": (c_int, [c_int, c_int, c_int, P, c_long, P, P, P, P, P, P, c_long,
                                  c_float, P]),
+    "smer_wce_fwd_bwd_ex": (c_int, [c_int, c_int, c_int, P, c_long, P, P, P, P, P, P, c_long,
+                                    c_float, c_float, P, P]),
     "smer_adam": (c_int, [c_long, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float,
                           c_float, P]),
     "smer_grad_sqnorm_nparts": (c_long, [c_long]),

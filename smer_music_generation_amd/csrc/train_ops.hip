@@ -53,6 +53,84 @@ __global__ __launch_bounds__(256) void wce_kernel(int R, int V, const float* __r
   }
 }
 
+// smer_wce_fwd_bwd_ex: wce_kernel with torch's label_smoothing = ls on the
+// twelve criteria, and the plain term w[y] * -log_softmax(x)[y] beside the
+// row loss (row_nll, nullable).  Same layout: one wave per row, four rows per
+// workgroup, fixed-order wave reductions.  LS = false is wce_kernel's own
+// code, expression for expression (ls = 0 gives its bits).  LS = true, on a
+// row with y != 0 (an ignored row gets no smoothing term):
+//   row_loss = (1-ls) * nll + (ls/V) * sum_c w[c] * -log_softmax(x)[c]
+//   dlog[c]  = grad_scale/denom * ((1-ls) * w[y] * (p[c] - [c == y])
+//                                  + (ls/V) * (W * p[c] - w[c])),  W = sum_c w[c]
+// Each -log_softmax(x)[c] = log(se) - (x[c] - mx) is a sum of two
+// non-negative terms, as in the plain loss (W * lse - sum w x would cancel at
+// the logits' magnitude).  W is summed by every wave in the same order, so
+// every row sees the same bits.  x[c] = -inf gives w[c] * inf in the sum, as
+// torch does: inf for w[c] > 0 (NaN for w[c] == 0), in that row alone.
+template <typename T, bool LS>
+__global__ __launch_bounds__(256) void wce_ex_kernel(int R, int V, const float* __restrict__ logits,
+                                                     long ldl, const int64_t* __restrict__ y,
+                                                     const float* __restrict__ w,
+                                                     const float* __restrict__ denom,
+                                                     float* __restrict__ row_loss,
+                                                     float* __restrict__ row_nll,
+                                                     T* __restrict__ dlog, long ldd,
+                                                     float grad_scale, float ls) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;
+  const float* x = logits + (long)r * ldl;
+  const long yt = y[r];
+  float mx = -INFINITY;
+  for (int v = lane; v < V; v += 64) mx = fmaxf(mx, x[v]);
+  mx = wave_max(mx);
+  float se = 0.f;
+  for (int v = lane; v < V; v += 64) se += expf(x[v] - mx);
+  se = wave_sum(se);
+  const float wy = yt == 0 ? 0.f : w[yt];
+  const float nll = wy * (logf(se) - (x[yt] - mx));
+  if constexpr (!LS) {
+    if (lane == 0) {
+      row_loss[r] = nll;
+      if (row_nll) row_nll[r] = nll;
+    }
+    if (dlog) {
+      const float coef = grad_scale * wy / *denom;
+      const float inv = 1.f / se;
+      for (int v = lane; v < V; v += 64) {
+        float g = coef * (expf(x[v] - mx) * inv - (v == yt ? 1.f : 0.f));
+        dlog[(long)r * ldd + v] = from_f32<T>(g);
+      }
+    }
+  } else {
+    const bool live = yt != 0;
+    const float lse = logf(se);
+    float W = 0.f, sm = 0.f;
+    for (int v = lane; v < V; v += 64) {
+      const float wv = w[v];
+      W += wv;
+      sm += wv * (lse - (x[v] - mx));
+    }
+    W = wave_sum(W);
+    sm = wave_sum(sm);
+    const float uni = ls / (float)V;
+    if (lane == 0) {
+      row_loss[r] = live ? (1.f - ls) * nll + uni * sm : 0.f;
+      if (row_nll) row_nll[r] = nll;
+    }
+    if (dlog) {
+      const float cy = grad_scale * (1.f - ls) * wy / *denom;
+      const float cu = live ? grad_scale * uni / *denom : 0.f;
+      const float inv = 1.f / se;
+      for (int v = lane; v < V; v += 64) {
+        const float p = expf(x[v] - mx) * inv;
+        float g = cy * (p - (v == yt ? 1.f : 0.f)) + cu * (W * p - w[v]);
+        dlog[(long)r * ldd + v] = from_f32<T>(g);
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void sum_div_kernel(int n, const float* __restrict__ x,
                                                       const float* __restrict__ denom,
                                                       float* __restrict__ out) {
@@ -629,6 +707,44 @@ extern "C" int smer_wce_fwd_bwd(int dtype, int R, int V, const float* logits, lo
   if (loss_out)
     hipLaunchKernelGGL(sum_div_kernel, dim3(1), dim3(256), 0, s, R, row_loss, denom, loss_out);
   SMER_CHECK_LAUNCH("smer_wce_fwd_bwd");
+  return SMER_OK;
+}
+
+template <typename T>
+static void wce_ex_launch(bool ls_on, dim3 grid, hipStream_t s, int R, int V, const float* logits, long ldl,
+                          const int64_t* y, const float* w, const float* denom, float* row_loss,
+                          float* row_nll, void* dlogits, long ldd, float grad_scale, float ls) {
+  if (ls_on)
+    hipLaunchKernelGGL((wce_ex_kernel<T, true>), grid, dim3(256), 0, s, R, V, logits, ldl, y, w, denom,
+                       row_loss, row_nll, (T*)dlogits, ldd, grad_scale, ls);
+  else
+    hipLaunchKernelGGL((wce_ex_kernel<T, false>), grid, dim3(256), 0, s, R, V, logits, ldl, y, w, denom,
+                       row_loss, row_nll, (T*)dlogits, ldd, grad_scale, ls);
+}
+
+extern "C" int smer_wce_fwd_bwd_ex(int dtype, int R, int V, const float* logits, long ldl,
+                                   const int64_t* y, const float* w, const float* denom,
+                                   float* row_loss, float* loss_out, void* dlogits, long ldd,
+                                   float grad_scale, float label_smoothing, float* row_nll,
+                                   smer_stream_t stream) {
+  SMER_REQUIRE(logits && y && w && denom && row_loss, "smer_wce_fwd_bwd_ex: null pointer");
+  SMER_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f,  // also NaN
+               "smer_wce_fwd_bwd_ex: label_smoothing must be in [0, 1)");
+  if (R == 0) return SMER_OK;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((R + 3) / 4);
+  const bool ls_on = label_smoothing > 0.f;
+  if (dtype == SMER_BF16)
+    wce_ex_launch<bf16>(ls_on, grid, s, R, V, logits, ldl, y, w, denom, row_loss, row_nll, dlogits, ldd,
+                        grad_scale, label_smoothing);
+  else if (dtype == SMER_F32)
+    wce_ex_launch<float>(ls_on, grid, s, R, V, logits, ldl, y, w, denom, row_loss, row_nll, dlogits, ldd,
+                         grad_scale, label_smoothing);
+  else
+    return smer_set_error(SMER_ERR_UNSUPPORTED, "smer_wce_fwd_bwd_ex: dtype");
+  if (loss_out)
+    hipLaunchKernelGGL(sum_div_kernel, dim3(1), dim3(256), 0, s, R, row_loss, denom, loss_out);
+  SMER_CHECK_LAUNCH("smer_wce_fwd_bwd_ex");
   return SMER_OK;
 }
 

@@ -1058,6 +1058,20 @@ def wce_fwd_bwd(logits, y, w, denom, row_loss, loss_out=None, dlogits=None, *, V
          float(grad_scale), _stream())
 
 
+def wce_fwd_bwd_ex(logits, y, w, denom, row_loss, loss_out=None, dlogits=None, *, V=None,
+                   grad_scale=1.0, label_smoothing=0.0, row_nll=None):
+    """wce_fwd_bwd with torch's `label_smoothing` on every criterion
+    (smer_wce_fwd_bwd_ex): row_loss and loss_out hold the smoothed loss,
+    row_nll (fp32 [R], optional) the plain term w[y] * -log_softmax(x)[y].
+    label_smoothing = 0 writes wce_fwd_bwd's bits."""
+    R = logits.shape[0]
+    Vv = V if V is not None else logits.shape[1]
+    dt = dtype_code(dlogits.dtype) if dlogits is not None else F32
+    call("smer_wce_fwd_bwd_ex", dt, R, Vv, _p(logits), _ld(logits), _p(y), _p(w), _p(denom),
+         _p(row_loss), _p(loss_out), _p(dlogits), _ld(dlogits) if dlogits is not None else 0,
+         float(grad_scale), float(label_smoothing), _p(row_nll), _stream())
+
+
 def argmax_accuracy(logits, y, cls, ncls, pad, counts):
     """counts[2c], counts[2c+1] += rows / argmax hits of token class c (and
     the total in the last pair) over the rows whose target is not `pad`

@@ -21,7 +21,9 @@ Adam semantics (`train.py:264`), as one stream of gfx950 kernels:
     inside the same Adam pass (smer_adam_ex);
   * optional (`param_groups=`): torch's parameter groups -- lr, betas, eps
     and weight decay per group -- still one Adam pass per slice
-    (smer_adam_groups reads each 64-element block's group from a byte map).
+    (smer_adam_groups reads each 64-element block's group from a byte map);
+  * optional (`label_smoothing=`): torch's label smoothing on the twelve
+    criteria, inside the fused cross-entropy kernel (smer_wce_fwd_bwd_ex).
 """
 from __future__ import annotations
 
@@ -180,6 +182,17 @@ def check_ema_decay(value):
     if not 0.0 <= d < 1.0:  # also NaN
         raise ValueError("ema_decay must be in [0, 1), got %r" % (value,))
     return d
+
+
+def check_label_smoothing(value):
+    """`Trainer.label_smoothing`: a number 0 <= e < 1 (torch's keyword on
+    CrossEntropyLoss).  Returns the float; anything else raises ValueError."""
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError("label_smoothing must be a number in [0, 1), got %r" % (value,))
+    e = float(value)
+    if not 0.0 <= e < 1.0:  # also NaN
+        raise ValueError("label_smoothing must be in [0, 1), got %r" % (value,))
+    return e
 
 
 def check_weight_decay(value):
@@ -418,7 +431,8 @@ class Trainer:
 
     def __init__(self, model, vocab, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, eos_weight=0.8,
                  group=None, grad_wire_dtype=None, broadcast=True, dp=None, clip_norm=None,
-                 weight_decay=0.0, decoupled_weight_decay=True, ema_decay=None, param_groups=None):
+                 weight_decay=0.0, decoupled_weight_decay=True, ema_decay=None, param_groups=None,
+                 label_smoothing=0.0):
         """clip_norm: None (default) is the plain step.  A number c > 0 is
         the guarded step: the global L2 norm of the whole flat gradient is
         taken on the device, Adam runs on the gradient scaled by
@@ -457,6 +471,17 @@ class Trainer:
         weights when ema_decay first becomes a number.  Settable per step.
         See `ema_weights`, `ema_state_dict`, `load_ema_state_dict`.  With
         weight_decay == 0 and ema_decay None the step is the plain one.
+        label_smoothing: 0 (default) is the plain loss, the step as it was.
+        0 < e < 1 is torch's `label_smoothing=e` on each of the twelve
+        CrossEntropyLoss criteria: a row with a target other than pad gets
+        (1 - e) * w[y] * -log p[y] + e / V * sum_c w[c] * -log p[c] with
+        w the summed criterion weights and V the vocabulary size, also where
+        w[y] == 0 (targets 2 and V - 1), exactly as torch; the normaliser
+        sum_i ce_weight_all[y_i] is unchanged.  The smoothing mass goes to all
+        V classes alike, grammar-invalid ones included.  `step` minimises and
+        returns this loss; `eval_step` and `validate` report the plain one.
+        Settable per step like `clip_norm`; a constructor hyper-parameter like
+        eos_weight, not part of `state_dict()`.
         grad_wire_dtype: None / torch.float32 (default, parity) or
         torch.bfloat16 for the DP gradient all-reduce (see GradBucketer).
         broadcast: under DP, copy rank 0's parameters to every rank here.
@@ -465,6 +490,7 @@ class Trainer:
         default: when the process group has more than one rank; True also
         at world size 1 (the real RCCL calls and stream ordering on one GPU)."""
         self._clip_norm = check_clip_norm(clip_norm)
+        self._label_smoothing = check_label_smoothing(label_smoothing)
         ema_decay = check_ema_decay(ema_decay)
         weight_decay = check_weight_decay(weight_decay)
         groups = None
@@ -527,6 +553,14 @@ class Trainer:
     @clip_norm.setter
     def clip_norm(self, value):
         self._clip_norm = check_clip_norm(value)
+
+    @property
+    def label_smoothing(self):
+        return self._label_smoothing
+
+    @label_smoothing.setter
+    def label_smoothing(self, value):
+        self._label_smoothing = check_label_smoothing(value)
 
     @property
     def ema_decay(self):
@@ -662,7 +696,12 @@ class Trainer:
     def step(self, batch, return_parts=False):
         """batch: dict of device tensors input/target_in/target_out/
         input_pad_mask/target_pad_mask (dataset.py:856-862).  Returns the
-        (local-share) loss as a device scalar; no host sync."""
+        (local-share) loss as a device scalar; no host sync.  With
+        label_smoothing > 0 that is the smoothed loss, the quantity being
+        minimised; the per-criterion parts of return_parts=True stay the plain
+        ones (each row's w[y] * -log p[y], no smoothing term), so they compare
+        across runs with different label_smoothing and do not sum to the
+        returned loss."""
         if self._ema_swapped:
             raise RuntimeError("Trainer.step inside ema_weights(): the model holds the averaged weights")
         model = self.model
@@ -686,7 +725,13 @@ class Trainer:
         dlog = torch.zeros(B * T, eng.Vp, dtype=ctx.dt, device=logits.device)
         row_loss = torch.empty(B * T, device=logits.device)
         loss = torch.empty(1, device=logits.device)
-        ops.wce_fwd_bwd(logits, y, self.w_total, denom, row_loss, loss, dlog, V=eng.V)
+        row_nll = row_loss
+        if self._label_smoothing > 0:
+            row_nll = torch.empty(B * T, device=logits.device)
+            ops.wce_fwd_bwd_ex(logits, y, self.w_total, denom, row_loss, loss, dlog, V=eng.V,
+                               label_smoothing=self._label_smoothing, row_nll=row_nll)
+        else:
+            ops.wce_fwd_bwd(logits, y, self.w_total, denom, row_loss, loss, dlog, V=eng.V)
         grad = model.flat_grad()
         grad.zero_()
         hook = None
@@ -794,7 +839,7 @@ class Trainer:
         else:
             eng.mark_params_updated()
         if return_parts:
-            return loss, self.loss_parts(row_loss, y, denom)
+            return loss, self.loss_parts(row_nll, y, denom)
         return loss
 
     def _class_table(self, dev):
@@ -812,14 +857,17 @@ class Trainer:
             ct = self._cls = (tab.to(dev), names)
         return ct
 
-    def eval_step(self, batch):
+    def eval_step(self, batch, smoothed=False):
         """The validation pass of one batch (train.py:1037-1195 `validate`
         body + `accuracy`, train.py:988-1034) on device, no backward: eval
         forward (no dropout), the fused criteria (no gradient written) and the
         argmax accuracy counts.  Returns (loss, {criterion: loss}, counts)
         as device tensors, no host sync; counts int32 [2 * n_classes + 2]
         (rows, hits per token class in `accuracy_from_counts`' class order,
-        then the total)."""
+        then the total).  The loss is the plain one whatever
+        `label_smoothing` is (what perplexity and a scheduler on the
+        validation loss want); smoothed=True returns the training objective
+        instead.  The per-criterion losses are the plain ones either way."""
         model = self.model
         eng = model.engine
         was_training = model.training
@@ -836,8 +884,14 @@ class Trainer:
                 ops.wce_denom(y, self.ce_all, denom)
                 row_loss = torch.empty(B * T, device=logits.device)
                 loss = torch.empty(1, device=logits.device)
-                ops.wce_fwd_bwd(logits, y, self.w_total, denom, row_loss, loss, None, V=eng.V)
-                parts = self.loss_parts(row_loss, y, denom)
+                row_nll = row_loss
+                if smoothed and self._label_smoothing > 0:
+                    row_nll = torch.empty(B * T, device=logits.device)
+                    ops.wce_fwd_bwd_ex(logits, y, self.w_total, denom, row_loss, loss, None, V=eng.V,
+                                       label_smoothing=self._label_smoothing, row_nll=row_nll)
+                else:
+                    ops.wce_fwd_bwd(logits, y, self.w_total, denom, row_loss, loss, None, V=eng.V)
+                parts = self.loss_parts(row_nll, y, denom)
                 cls, names = self._class_table(logits.device)
                 counts = torch.zeros(2 * len(names) + 2, dtype=torch.int32, device=logits.device)
                 ops.argmax_accuracy(logits, y, cls, len(names), self.vocab.pad_index, counts)

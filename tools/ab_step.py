@@ -3,7 +3,8 @@ process (the switches are read once per process), rounds interleaved.
     python tools/ab_step.py c2|c4|c4bf16 ENV_NAME VALUE_A VALUE_B ... [--rounds 2]
     python tools/ab_step.py c2 ENV "A=1,B=2" "A=0" ...   (several switches per value)
     python tools/ab_step.py c2adam ARGS "" "weight_decay=0.01" "weight_decay=0.01,ema_decay=0.999" ...
-        (the C2 step of tools/adam_ex_step.py, each value its comma-separated arguments)"""
+        (the C2 step of tools/adam_ex_step.py, each value its comma-separated arguments)
+    python tools/ab_step.py c2adam ARGS "" "label_smoothing=0.1"   (the smoothed loss kernel's cost)"""
 import json
 import os
 import subprocess

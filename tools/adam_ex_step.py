@@ -2,7 +2,7 @@
 c2adam and rocprofv3 kernel traces): bench.py's model, batch and timed region
 (20 steps after 3 warm-up), the Trainer built with the given keywords.
     python tools/adam_ex_step.py [weight_decay=0.01] [coupled=1] [ema_decay=0.999] [clip_norm=1.0] [groups=0.01]
-                                 [steps=20]
+                                 [label_smoothing=0.1] [steps=20]
 groups=W: param_groups=decay_groups(model, W), the two-group step (smer_adam_groups).
 No argument is bench.py's own step (a default Trainer)."""
 import os
@@ -22,6 +22,8 @@ if "ema_decay" in opts:
     kw["ema_decay"] = float(opts.pop("ema_decay"))
 if "clip_norm" in opts:
     kw["clip_norm"] = float(opts.pop("clip_norm"))
+if "label_smoothing" in opts:
+    kw["label_smoothing"] = float(opts.pop("label_smoothing"))
 groups_wd = float(opts.pop("groups")) if "groups" in opts else None
 if opts:
     sys.exit("unknown option(s) %s" % sorted(opts))
